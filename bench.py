@@ -8,7 +8,7 @@ gradient all-reduce (N > 1), fused SGD step.  N = 1 runs BASELINE.json configs[1
 N > 1 runs configs[2]: SyncBN + RCCL gradient all-reduce, B = 72 per GPU (`--scaling weak`, default) or the reference's
 own semantics, a GLOBAL batch of 72 split over the ranks (`--scaling strong`, train_adamml.py:122).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 Launched under torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE in the environment) every process is one rank.
 Launched plainly with --gpus N > 1 it spawns the N ranks itself, one process per GPU, as the reference's launcher does
@@ -27,6 +27,7 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
@@ -69,7 +70,13 @@ def parse():
                          "Stack produces) and are normalised inside the input kernel: 1 byte per value through HBM instead of 4")
     ap.add_argument("--single-stream", action="store_true", help="profiling aid: no side streams, so per-kernel durations "
                     "in a rocprofv3 trace are not inflated by concurrently running kernels")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy: logits, "
+                         "decisions, loss and a fixed, seeded sample of the parameters the step updated -- for comparing two builds")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def source_stamp():
@@ -109,6 +116,24 @@ def synth_batch(args, b, device, rank):
             xs.append(torch.randn(b, s * 8 * CHANNELS[m], 224, 224, device=device))
     tgt = torch.randint(0, 31, (b,), generator=g).to(device)
     return xs, tgt
+
+
+PARAM_SAMPLE = 1 << 20         # --dump-outputs: parameters kept per updated sub-network (4 MB fp32 each)
+
+
+def timed_outputs(model, last, loss, stage):
+    """Host copies of what the last timed step computed: its logits and decisions, its loss, and -- the step's other result --
+    the flat fp32 parameters of each sub-network it updated, as a fixed seeded sample (the same indices on every run)."""
+    out = {"logits": last["logits"], "decisions": last["decisions"]}
+    if stage != "infer":
+        out["loss"] = loss.reshape(1)
+    for name, fb, on in (("main_params_sample", model._flat_main, model.update_main_net),
+                         ("policy_params_sample", model._flat_policy, model.update_policy_net)):
+        if on and stage != "infer":
+            n = fb.flat.numel()
+            idx = np.sort(np.random.default_rng(0).choice(n, min(n, PARAM_SAMPLE), replace=False))
+            out[name] = fb.flat[torch.from_numpy(idx).to(fb.flat.device)]
+    return {k: v.detach().float().cpu().numpy() for k, v in out.items()}
 
 
 def _timed(fn, warm=1, iters=3):
@@ -270,14 +295,17 @@ def run_rank(args):
         model.use_side_stream = False
     images, target = synth_batch(args, per_gpu, device, rank)
     opt = p_opt = None
+    last = {}          # the arrays the most recent step returned to its caller (--dump-outputs)
 
     def step():
         nonlocal opt, p_opt
         if args.stage == "infer":
             with torch.no_grad():
                 out, sel = ddp(images)
+            last.update(logits=out, decisions=sel)
             return out.sum()
         out, sel = ddp(images)
+        last.update(logits=out, decisions=sel)
         loss = F.cross_entropy(out, target)
         if model.update_policy_net:
             usage = sel.mean(dim=1) ** 2
@@ -316,6 +344,8 @@ def run_rank(args):
     if world > 1:
         dist.barrier()
     dt = time.time() - t0
+    # copied outside the timed window and before the roofline steps below change the weights again
+    dump = timed_outputs(model, last, loss, args.stage) if args.dump_outputs and rank == 0 else None
     step_ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
     med_ms = statistics.median(step_ms)
     if world > 1:
@@ -438,6 +468,10 @@ def run_rank(args):
             "roofline": roof, "cpu_baseline": cpu, "kernel_breakdown": breakdown,
         }
         print(json.dumps(res))
+    if dump is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for k, v in dump.items():
+            np.save(os.path.join(args.dump_outputs, k + ".npy"), v)
     if dist.is_initialized():
         dist.destroy_process_group()
 

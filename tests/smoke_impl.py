@@ -10,11 +10,16 @@ import torch
 import torch.nn.functional as F
 
 
+def rel(x, y):
+    return np.abs(x - y).max() / np.abs(y).max()
+
+
 def run_smoke():
     from adamml_amd import adamml, synth, hip
     from adamml_amd.optim import FlatSGD
     from tests.golden_cases import CASES, CH
     from tests.oracle_harness import manifest, load_golden, case_inputs, case_gumbel, oracle_case
+    from tests.parity_bounds import bound, emu_gate
     if not torch.cuda.is_available():
         raise RuntimeError("smoke() needs an MI355X (no CPU fallback)")
     hip.load()
@@ -68,9 +73,14 @@ def run_smoke():
     F.cross_entropy(logits, target).backward()
     torch.cuda.synchronize()
     assert np.array_equal(np.round(sel.detach().cpu().numpy()), np.round(gold2["train_main.decisions"])), "full-size decisions differ from the reference"
-    g2 = gold2["train_main.logits"]
-    e2 = np.abs(logits.detach().cpu().numpy() - g2).max() / np.abs(g2).max()
-    ep = np.abs(model.last_policy_logits.detach().cpu().numpy() - gold2["train_main.policy_logits"]).max() / np.abs(gold2["train_main.policy_logits"]).max()
+    emu2 = load_golden("adamml_c2_bf16emu")
+    lg, pl = logits.detach().cpu().numpy(), model.last_policy_logits.detach().cpu().numpy()
+    e2, ep = rel(lg, gold2["train_main.logits"]), rel(pl, gold2["train_main.policy_logits"])
     print("smoke: full size (B=4, S=5, 224^2 / 256^2) logits |HIP-reference| %.4f, policy logits %.4f of scale | decisions match" % (e2, ep))
-    # 1.3 x measured (logits 3.09e-2; policy logits, two 52-layer random-weight MobileNetV2 stacks in front of them, 5.60e-2): reproducible
-    assert e2 <= 4.0e-2 and ep <= 7.3e-2, (e2, ep)
+    # the gates of tests/test_parity_fullsize_gpu.py::test_c2_adamml_fullsize for the same step: relative to the oracle's bf16-storage
+    # emulation (tests/parity_bounds.emu_gate; the emulation itself sits 4.04e-2 / 7.4e-2 from the fp32 golden), and the re-based regression
+    # figures of tests/parity_bounds.json (1.3 x measured; reproducible: order-fixed sums) held as hard bounds here
+    emu_gate("c2.train_main.logits", "logits", e2, rel(lg, emu2["train_main.logits"]), rel(emu2["train_main.logits"], gold2["train_main.logits"]))
+    emu_gate("c2.train_main.plog", "plog", ep, rel(pl, emu2["train_main.policy_logits"]),
+             rel(emu2["train_main.policy_logits"], gold2["train_main.policy_logits"]))
+    assert e2 <= bound("c2.train_main.logits") and ep <= bound("c2.train_main.plog"), (e2, ep)
