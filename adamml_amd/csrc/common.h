@@ -29,7 +29,11 @@ int adamml_launch_split_reduce_grouped(const float* ws, float* out, size_t n, in
 // branch-free per element (the runtime `act` is folded into two scalars once per call site).
 __device__ __forceinline__ float act_lo(int act) { return act == ACT_NONE ? -INFINITY : 0.f; }
 __device__ __forceinline__ float act_hi(int act) { return act == ACT_RELU6 ? 6.f : INFINITY; }
-__device__ __forceinline__ float clamp_act(float v, float lo, float hi) { return __builtin_fminf(__builtin_fmaxf(v, lo), hi); }
+// (NaN-propagating maximum / minimum, v_maximum3_f32 / v_minimum3_f32: fmaxf / fminf return the non-NaN operand, which turned a NaN
+// pre-activation into 0 under ReLU -- a poisoned BatchNorm then vanished from everything downstream instead of reaching the loss, as in torch)
+__device__ __forceinline__ float clamp_act(float v, float lo, float hi) {
+    return __builtin_elementwise_minimum(__builtin_elementwise_maximum(v, lo), hi);
+}
 __device__ __forceinline__ float apply_act(float v, int act) { return clamp_act(v, act_lo(act), act_hi(act)); }
 // derivative mask of the activation evaluated at pre-activation value v
 __device__ __forceinline__ float mask_act(float v, float lo, float hi) { return (v > lo && v < hi) ? 1.f : 0.f; }

@@ -412,7 +412,7 @@ __global__ __launch_bounds__(NW * 64, 1) void conv1x1_fadd_tpool_kernel(FTP p) {
                         unsigned cd = code[b][i];
 #pragma unroll
                         for (int j = 0; j < 8; ++j)
-                            if (v[j] > best[b][i][j]) { best[b][i][j] = v[j]; cd = (cd & ~(3u << (2 * j))) | (tapbits & (3u << (2 * j))); }   // first maximum in scan order
+                            if (v[j] > best[b][i][j] || __builtin_isnan(v[j])) { best[b][i][j] = v[j]; cd = (cd & ~(3u << (2 * j))) | (tapbits & (3u << (2 * j))); }   // first maximum in scan order
                         code[b][i] = cd;
                     }
                     if constexpr (ODD) {

@@ -331,8 +331,8 @@ __global__ __launch_bounds__(NQ * 64, NQ == 4 ? 2 : 1) void conv1x1_fadd_tpool_s
                 unsigned cd = 0u;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {                               // first maximum in scan order: taps 0, 1, 2
-                    if (v1[j] > bst[j]) { bst[j] = v1[j]; cd = (cd & ~(3u << (2 * j))) | (1u << (2 * j)); }
-                    if (v2[j] > bst[j]) { bst[j] = v2[j]; cd = (cd & ~(3u << (2 * j))) | (2u << (2 * j)); }
+                    if (v1[j] > bst[j] || __builtin_isnan(v1[j])) { bst[j] = v1[j]; cd = (cd & ~(3u << (2 * j))) | (1u << (2 * j)); }
+                    if (v2[j] > bst[j] || __builtin_isnan(v2[j])) { bst[j] = v2[j]; cd = (cd & ~(3u << (2 * j))) | (2u << (2 * j)); }
                     if (!(bst[j] > rlo && bst[j] < rhi)) cd |= 3u << (2 * j);                   // act'(maximum) == 0: no gradient through this window
                 }
                 if (FULL || px < npx) *reinterpret_cast<bf16x8*>(ob + (unsigned)((px * C + zch * 8) * 2)) = f32_to_bf8(bst);

@@ -772,7 +772,7 @@ __global__ __launch_bounds__(NTHREADS, conv_gemm_wg_per_cu(BC, MODE, PD, RES, DU
                             const f32x8 v = bf8_to_f32(vb[tt * NPX + s]);
 #pragma unroll
                             for (int i = 0; i < 8; ++i)
-                                if (v[i] > best[i]) { best[i] = v[i]; code = (code & ~(3u << (2 * i))) | ((unsigned)k << (2 * i)); }   // first maximum in scan order
+                                if (v[i] > best[i] || __builtin_isnan(v[i])) { best[i] = v[i]; code = (code & ~(3u << (2 * i))) | ((unsigned)k << (2 * i)); }   // first maximum in scan order
                         }
 #pragma unroll
                         for (int i = 0; i < 8; ++i)
@@ -1837,8 +1837,9 @@ static int conv_launch(const adamml_conv_desc_t* d, const void* x, const void* w
     if (!cls && !fadd && !res && !dual && !cat && !pf && !bn_z && adamml_conv1x1_narrow_fwd_supported(d))
         return adamml_conv1x1_narrow_fwd_launch(d, x, w_packed, in_scale, in_shift, y, stats, stream);
     // expanding 1x1 convs of ResNet layers 3-4 (K = 256 / 512 -> >= 2 K channels; plain forward, stride-2 downsample forward, plain or
-    // accumulating data gradient): activation-stationary streaming kernel (conv1x1_wide.hip)
-    if (!cls && !fadd && !res && !dual && !cat && !pf && !bn_z && adamml_conv1x1_wide_expand_supported(d))
+    // accumulating data gradient): activation-stationary streaming kernel (conv1x1_wide.hip; it has no accumulating form of a lazy input:
+    // that call stays with conv_gemm_kernel)
+    if (!cls && !fadd && !res && !dual && !cat && !pf && !bn_z && !(d->accumulate && in_scale) && adamml_conv1x1_wide_expand_supported(d))
         return adamml_conv1x1_wide_expand_launch(d, x, w_packed, in_scale, in_shift, y, stats, stream);
     // ... their data gradients with the BatchNorm-fused epilogue (bn_z) or accumulating into the output
     if (!cls && !fadd && !res && !dual && !cat && !pf && !in_scale && (bn_z ? stats != nullptr && !d->accumulate : d->accumulate != 0) &&

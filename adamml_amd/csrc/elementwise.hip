@@ -525,7 +525,7 @@ __global__ void maxpool_fwd_kernel(const bf16_t* x, const float* scale, const fl
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
                     const float t = ok ? clamp_act(fmaf(v[i], tsc[i], tsh[i]), tlo, thi) : -INFINITY;
-                    if (t > best[i]) {
+                    if (t > best[i] || __builtin_isnan(t)) {       // (a NaN tap wins, as in torch)
                         best[i] = t; bi[i] = kh * 3 + kw;
                         if (ZSEL) zs[i] = raw[kh * 3 + kw][i];
                     }
@@ -543,8 +543,8 @@ __global__ void maxpool_fwd_kernel(const bf16_t* x, const float* scale, const fl
 // Column walker of the same pool: a thread owns one 8-channel chunk of one output COLUMN and walks down `rows` output rows.  Input row
 // 2oh+1 is both the bottom row of window oh and the top row of window oh+1, so its three transformed taps are carried over: six new
 // loads per output instead of nine (the per-output form is bound by its nine L1 requests per 16 bytes of output, not by HBM), and the
-// two rows of the next window are in flight while the current one is reduced.  Same scan order (kh, kw ascending, strict >): same
-// arg-max taps.
+// two rows of the next window are in flight while the current one is reduced.  Same scan order (kh, kw ascending, strict >, a NaN tap
+// always taken): same arg-max taps.
 template <bool ZSEL>
 __global__ __launch_bounds__(NT) void maxpool_fwd_walk_kernel(const bf16_t* x, const float* scale, const float* shift, int gs, int act, bf16_t* y,
                                                               uint8_t* idx, bf16_t* zsel, int N, int H, int W, int C, int OH, int OW, int rows,
@@ -616,17 +616,17 @@ __global__ __launch_bounds__(NT) void maxpool_fwd_walk_kernel(const bf16_t* x, c
         for (int kw = 0; kw < 3; ++kw)
 #pragma unroll
             for (int i = 0; i < 8; ++i)
-                if (ttop[kw][i] > best[i]) { best[i] = ttop[kw][i]; bi[i] = kw; if (ZSEL) zs[i] = top.v[kw][i]; }
+                if (ttop[kw][i] > best[i] || __builtin_isnan(ttop[kw][i])) { best[i] = ttop[kw][i]; bi[i] = kw; if (ZSEL) zs[i] = top.v[kw][i]; }
 #pragma unroll
         for (int kw = 0; kw < 3; ++kw)
 #pragma unroll
             for (int i = 0; i < 8; ++i)
-                if (tmid[kw][i] > best[i]) { best[i] = tmid[kw][i]; bi[i] = 3 + kw; if (ZSEL) zs[i] = mid.v[kw][i]; }
+                if (tmid[kw][i] > best[i] || __builtin_isnan(tmid[kw][i])) { best[i] = tmid[kw][i]; bi[i] = 3 + kw; if (ZSEL) zs[i] = mid.v[kw][i]; }
 #pragma unroll
         for (int kw = 0; kw < 3; ++kw)
 #pragma unroll
             for (int i = 0; i < 8; ++i)
-                if (tbot[kw][i] > best[i]) { best[i] = tbot[kw][i]; bi[i] = 6 + kw; if (ZSEL) zs[i] = bot.v[kw][i]; }
+                if (tbot[kw][i] > best[i] || __builtin_isnan(tbot[kw][i])) { best[i] = tbot[kw][i]; bi[i] = 6 + kw; if (ZSEL) zs[i] = bot.v[kw][i]; }
         const size_t o = ((((size_t)n * OH + oh) * OW + ow) * cpr + ch) * 8;
         *reinterpret_cast<bf16x8*>(y + o) = f32_to_bf8(best);
         if (ZSEL) *reinterpret_cast<bf16x8*>(zsel + o) = zs;
@@ -823,7 +823,7 @@ __global__ void temporal_pool_fwd_kernel(const bf16_t* x, const float* scale, co
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const float tv = clamp_act(fmaf(v[i], tsc[i], tsh[i]), tlo, thi);
-                accv[i] = mode == 0 ? fmaxf(accv[i], ok ? tv : -INFINITY) : accv[i] + (ok ? tv : 0.f);
+                accv[i] = mode == 0 ? __builtin_elementwise_maximum(accv[i], ok ? tv : -INFINITY) : accv[i] + (ok ? tv : 0.f);
             }
         }
         if (mode == 1) accv *= (1.f / 3.f);
@@ -872,7 +872,7 @@ __global__ __launch_bounds__(NT) void temporal_pool_fwd_walk_kernel(const bf16_t
                 const int t = 2 * to + k;
                 if (t < 0 || t >= T) continue;                   // (compile-time)
 #pragma unroll
-                for (int i = 0; i < 8; ++i) acc[i] = mode == 0 ? fmaxf(acc[i], v[t][i]) : acc[i] + v[t][i];
+                for (int i = 0; i < 8; ++i) acc[i] = mode == 0 ? __builtin_elementwise_maximum(acc[i], v[t][i]) : acc[i] + v[t][i];
             }
             if (mode == 1) acc *= (1.f / 3.f);
             __builtin_nontemporal_store(f32_to_bf8(acc), reinterpret_cast<bf16x8*>(y + ((nb * To + to) * hwc8 + in) * 8));
