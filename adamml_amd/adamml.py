@@ -5,7 +5,7 @@ import os
 import torch
 import torch.nn as nn
 
-from . import hip, interleave, plan
+from . import audio, hip, interleave, plan
 from .backbone import FlatBuffers, StockDDPAware
 from .common import MeanStdMixin
 from .joint_resnet_mobilenetv2 import joint_resnet_mobilenetv2
@@ -24,7 +24,7 @@ def _frames(t):
 class AdaMML(nn.Module, MeanStdMixin, StockDDPAware):
 
     def __init__(self, policy_net, main_net, num_frames, num_segments, modality, rng_policy, rng_threshold, num_classes,
-                 input_channels=None):
+                 input_channels=None, resampling_rate=24000, audio_length=1.28):
         super().__init__()
         self._install_ddp_probe()
         self.rng_policy = rng_policy
@@ -35,6 +35,9 @@ class AdaMML(nn.Module, MeanStdMixin, StockDDPAware):
         self.num_frames_per_segment = num_frames
         self.modality = modality
         self.input_channels = input_channels
+        # waveform input of the sound modality (data_layer): the rate and clip length of the loader (utils/video_dataset.py:93-132)
+        self.resampling_rate = resampling_rate
+        self.audio_length = audio_length
         if 'rgbdiff' in modality and 'flow' in modality:
             self.num_modality = len(modality) - 1
         else:
@@ -65,6 +68,9 @@ class AdaMML(nn.Module, MeanStdMixin, StockDDPAware):
         for idx, (x_, m) in enumerate(zip(x, self.modality)):
             hip.require_gpu(x_)
             if m == 'sound':
+                if x_.dim() == 3:
+                    # MI355X extension: raw waveforms [B, S, L] -> log-power spectrograms [B, S, F, T] on this stream (audio.py)
+                    x_ = self._sound_spectrogram(x_)
                 if x_.size(-1) != x_.size(-2):
                     # legacy "consecutive segments stacked along the last dim" layout (:49-51)
                     x_ = torch.stack(x_.chunk(num_segments, dim=-1), dim=1).reshape(x_.size(0), -1, x_.size(-2),
@@ -103,6 +109,18 @@ class AdaMML(nn.Module, MeanStdMixin, StockDDPAware):
                 m_x.append(clip_to_nhwc(x_, num_segments, f, c, cpad=self._main_cpad(m, x_.size(-2), x_.size(-1))))
         return p_x, m_x, num_segments
 
+    def _sound_spectrogram(self, wave):
+        """[B, S, L] fp32 waveforms of round(resampling_rate * audio_length) samples -> [B, S, F, T] spectrograms (load_sound)."""
+        need = int(round(self.resampling_rate * self.audio_length))
+        if wave.size(-1) != need:
+            raise ValueError("AdaMML: sound waveforms of %d samples, expected round(%g Hz * %g s) = %d"
+                             % (wave.size(-1), self.resampling_rate, self.audio_length, need))
+        spec = audio.log_spectrogram(wave, sample_rate=self.resampling_rate)
+        if spec.size(-1) != spec.size(-2):
+            raise ValueError("AdaMML: the sound spectrogram is %d x %d; the sound backbones take a square image"
+                             % (spec.size(-2), spec.size(-1)))
+        return spec
+
     def _sound_f32_ok(self, idx, x_):
         """Every consumer of modality `idx` (its main net, its policy backbone) reads a [B, S, H, W] fp32 tensor directly."""
         nets = []
@@ -113,7 +131,8 @@ class AdaMML(nn.Module, MeanStdMixin, StockDDPAware):
         return bool(nets) and all(hasattr(n, "accepts_f32") and n.accepts_f32(x_) for n in nets)
 
     def forward(self, x, num_segments=None, gumbel_exponential=None):
-        """x: list over modality of [N, S*F*C, H, W] fp32 GPU tensors.  Returns (logits [N, classes], decisions [N,S,M]).
+        """x: list over modality of [N, S*F*C, H, W] fp32 GPU tensors (sound may also be raw waveforms [N, S, L] fp32: data_layer).
+        Returns (logits [N, classes], decisions [N,S,M]).
         gumbel_exponential (optional, [S, M*N, 2]) replaces the device-side Exponential(1) draw for parity runs."""
         num_segments = num_segments if num_segments else self.num_segments
         dev = x[0].device
@@ -358,4 +377,5 @@ def adamml(groups, modality, input_channels, num_segments, rng_policy, rng_thres
                                         learnable_lf_weights=learnable_lf_weights)
     return AdaMML(policy_net, main_net, num_frames=groups, num_segments=num_segments, modality=modality,
                   rng_policy=rng_policy, rng_threshold=rng_threshold, num_classes=num_classes,
-                  input_channels=input_channels)
+                  input_channels=input_channels, resampling_rate=kwargs.get('resampling_rate', 24000),
+                  audio_length=kwargs.get('audio_length', 1.28))

@@ -1253,6 +1253,41 @@ def clip_u8_to_nhwc(x, num_segments, frames, channels, mean, std, out_hw=None, f
     return y
 
 
+def spectrogram_basis(n_fft, win):
+    """Windowed DFT basis of adamml_log_spectrogram, [win, 2F] fp32 (F = n_fft // 2 + 1): [m, k] = w[m] cos(2 pi k m / n_fft),
+    [m, F + k] = w[m] sin(2 pi k m / n_fft), w the periodic Hann window of length win.  Evaluated in float64 from the exactly reduced
+    integer argument (k m) mod n_fft, then rounded once to float32.  (The window's offset (n_fft - win) // 2 inside the n_fft frame
+    multiplies every bin by one phase factor, which the power does not see.)"""
+    import numpy as np
+    f = n_fft // 2 + 1
+    m = np.arange(win, dtype=np.int64)
+    w = 0.5 - 0.5 * np.cos(2.0 * np.pi * m / win)
+    ang = 2.0 * np.pi * ((m[:, None] * np.arange(f, dtype=np.int64)[None, :]) % n_fft) / n_fft
+    return np.concatenate([w[:, None] * np.cos(ang), w[:, None] * np.sin(ang)], axis=1).astype(np.float32)
+
+
+_spec_basis = {}
+
+
+def log_spectrogram(wave, n_fft, win, hop, eps):
+    """Raw waveforms [N, L] fp32 (contiguous, on the GPU) -> log-power spectrograms [N, F, T] fp32 (adamml_log_spectrogram).
+    The basis is built once per (device, n_fft, win) and kept."""
+    hip.require_gpu(wave)
+    if wave.dtype != torch.float32 or wave.dim() != 2 or not wave.is_contiguous():
+        raise RuntimeError("log_spectrogram: expected a contiguous [N, L] float32 tensor, got %s %s" % (wave.dtype, tuple(wave.shape)))
+    n, length = wave.shape
+    key = (wave.device, n_fft, win)
+    basis = _spec_basis.get(key)
+    if basis is None and 2 <= n_fft <= 512 and 1 <= win <= n_fft:
+        basis = _spec_basis[key] = torch.from_numpy(spectrogram_basis(n_fft, win)).to(wave.device)
+    # (other sizes: no basis, and the library's argument check names what is wrong)
+    f = n_fft // 2 + 1
+    t = 1 + (length + 2 * (n_fft // 2) - n_fft) // hop if hop >= 1 and length >= 1 else 0
+    y = torch.empty(n, f, max(t, 0), dtype=torch.float32, device=wave.device)
+    call("adamml_log_spectrogram", ptr(wave), ptr(basis), ptr(y), n, length, n_fft, win, hop, float(eps))
+    return y
+
+
 def clip_u8_rgbdiff_to_nhwc(x, num_segments, frames, mean, std, out_hw=None, frame_step=1, diffs=5):
     """RGB-diff input computed on the GPU (utils/video_dataset.py:32-38,75-84): decoded RGB frames [B, H, W, S*F*(diffs+1)*3]
     uint8 -- diffs+1 consecutive frames per frame group -> [S, B*Fk, OH, OW, pad8(3*diffs)] bf16 difference channels,

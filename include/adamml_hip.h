@@ -427,6 +427,19 @@ ADAMML_API int adamml_clip_u8_to_nhwc(const uint8_t* x, void* y, int B, int S, i
 ADAMML_API int adamml_clip_u8_rgbdiff_to_nhwc(const uint8_t* x, void* y, int B, int S, int F, int D, int H, int W, int OH, int OW, int frame_step,
                                    int c_pad, const float* mean, const float* std, int n_mean, hipStream_t stream);
 
+/* Sound input computed on the GPU from raw waveforms (utils/video_dataset.py:93-132 load_sound: librosa.stft(n_fft, window='hann',
+ * win_length=win, hop_length=hop, center=True, pad_mode='constant'), then log(|X|^2 + eps)).  wave [N, L] fp32 -> y [N, F, T] fp32
+ * with F = n_fft/2 + 1 (frequency = row) and T = 1 + (L + 2*(n_fft/2) - n_fft) / hop (time = column): the [H, W] image Stack +
+ * ToTorchFormatTensor(div=False) hand to the model.  Frame t covers clip samples t*hop - n_fft/2 + (n_fft - win)/2 + m, m < win
+ * (zero outside [0, L)); y[k, t] = log(Re^2 + Im^2 + eps) in fp32 (exact-fp32 matrix cores, accurate logf).
+ * basis: caller-owned [win][2F] fp32, built once by the caller: basis[m][k] = w[m] cos(2 pi ((k m) mod n_fft) / n_fft) and
+ * basis[m][F + k] = w[m] sin(...), w[m] = 0.5 - 0.5 cos(2 pi m / win) (periodic Hann), evaluated in fp64 and rounded to fp32
+ * (adamml_amd/runtime.py spectrogram_basis).  A NaN sample gives NaN (an Inf one a non-finite value) in every bin of exactly the frames
+ * whose support holds it.  Bounds: 2 <= n_fft <= 512, 1 <= win <= n_fft, hop >= 1, L >= 1, eps >= 0, checked before the pointers;
+ * N == 0 is a no-op. */
+ADAMML_API int adamml_log_spectrogram(const float* wave, const float* basis, float* y, int N, int L, int n_fft, int win, int hop, float eps,
+                           hipStream_t stream);
+
 /* y[M,N] = act(x[M,K] @ w[N,K]^T + bias) in fp32 with arbitrary strides (nn.Linear / LSTMCell gates and their
  * gradients: policy_net.py:228-231,278-279,351-362; resnet.py:215; sound_mobilenet_v2.py:158) */
 ADAMML_API int adamml_gemm_f32(const float* a, int64_t a_sm, int64_t a_sk, const float* b, int64_t b_sn, int64_t b_sk, float* c,
