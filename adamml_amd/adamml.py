@@ -5,7 +5,7 @@ import os
 import torch
 import torch.nn as nn
 
-from . import audio, hip, interleave, plan
+from . import audio, hip, interleave, plan, video
 from .backbone import FlatBuffers, StockDDPAware
 from .common import MeanStdMixin
 from .joint_resnet_mobilenetv2 import joint_resnet_mobilenetv2
@@ -66,6 +66,12 @@ class AdaMML(nn.Module, MeanStdMixin, StockDDPAware):
         p_x, m_x = [], []
         f = self.num_frames_per_segment
         for idx, (x_, m) in enumerate(zip(x, self.modality)):
+            if isinstance(x_, video.Frames):
+                # MI355X extension: decoded videos + their sampled geometry -> the uint8 arrays `Stack` would return (crop / scale /
+                # flip of the reference's augmentor, byte-exact, on this stream: video.py); from here the uint8 branch below
+                if m == 'sound' or x_.modality != m:
+                    raise ValueError("AdaMML: %s Frames given for the %s modality" % (x_.modality, m))
+                x_ = video.augment(x_)
             hip.require_gpu(x_)
             if m == 'sound':
                 if x_.dim() == 3:
@@ -131,7 +137,8 @@ class AdaMML(nn.Module, MeanStdMixin, StockDDPAware):
         return bool(nets) and all(hasattr(n, "accepts_f32") and n.accepts_f32(x_) for n in nets)
 
     def forward(self, x, num_segments=None, gumbel_exponential=None):
-        """x: list over modality of [N, S*F*C, H, W] fp32 GPU tensors (sound may also be raw waveforms [N, S, L] fp32: data_layer).
+        """x: list over modality of [N, S*F*C, H, W] fp32 GPU tensors (sound may also be raw waveforms [N, S, L] fp32, rgb / flow /
+        rgbdiff decoded videos as a video.Frames: data_layer).
         Returns (logits [N, classes], decisions [N,S,M]).
         gumbel_exponential (optional, [S, M*N, 2]) replaces the device-side Exponential(1) draw for parity runs."""
         num_segments = num_segments if num_segments else self.num_segments

@@ -34,5 +34,5 @@ extern "C" int adamml_set_deterministic(int on) {
 }
 extern "C" int adamml_get_deterministic(void) { return 1; }
 
-extern "C" int adamml_version(void) { return 102; }
+extern "C" int adamml_version(void) { return 103; }
 extern "C" const char* adamml_last_error_string(void) { return g_err; }

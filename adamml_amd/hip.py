@@ -92,6 +92,7 @@ SIGNATURES = {
     "adamml_clip_u8_to_nhwc": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P],
     "adamml_clip_u8_rgbdiff_to_nhwc": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P],
     "adamml_log_spectrogram": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
+    "adamml_video_resample_u8": [_P, _L, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P],
     "adamml_gemm_f32": [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _I, _I, _I, _I, _I, _P],
     "adamml_sgd_step": [_P, _P, _P, _Z, _F, _F, _F, _I, _I, _P],
     "adamml_adam_step": [_P, _P, _P, _P, _Z, _F, _F, _F, _F, _F, _I, _P],

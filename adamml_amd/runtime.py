@@ -1288,6 +1288,20 @@ def log_spectrogram(wave, n_fft, win, hop, eps):
     return y
 
 
+def video_resample_u8(src, meta, n, oh, ow, k_in, k_out, diffs=0):
+    """Packed decoded videos (flat uint8 buffer + int32 descriptors and tables, adamml_amd/video.py Frames) -> [N, OH, OW, K_out]
+    uint8 on the current stream (adamml_video_resample_u8): Pillow's 8-bit BILINEAR crop / scale / flip, byte-exact."""
+    for t, dt, what in ((src, torch.uint8, "src"), (meta, torch.int32, "meta")):
+        hip.require_gpu(t)
+        if t.dtype != dt or t.dim() != 1 or not t.is_contiguous():
+            raise RuntimeError("video_resample_u8: %s must be a contiguous 1-D %s tensor, got %s %s" % (what, dt, t.dtype, tuple(t.shape)))
+    if meta.device != src.device:
+        raise RuntimeError("video_resample_u8: src on %s but meta on %s" % (src.device, meta.device))
+    y = torch.empty(max(n, 0), max(oh, 0), max(ow, 0), max(k_out, 0), dtype=torch.uint8, device=src.device)
+    call("adamml_video_resample_u8", ptr(src), src.numel(), ptr(meta), meta.numel(), ptr(y), n, oh, ow, k_in, k_out, diffs)
+    return y
+
+
 def clip_u8_rgbdiff_to_nhwc(x, num_segments, frames, mean, std, out_hw=None, frame_step=1, diffs=5):
     """RGB-diff input computed on the GPU (utils/video_dataset.py:32-38,75-84): decoded RGB frames [B, H, W, S*F*(diffs+1)*3]
     uint8 -- diffs+1 consecutive frames per frame group -> [S, B*Fk, OH, OW, pad8(3*diffs)] bf16 difference channels,

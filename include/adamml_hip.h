@@ -440,6 +440,27 @@ ADAMML_API int adamml_clip_u8_rgbdiff_to_nhwc(const uint8_t* x, void* y, int B, 
 ADAMML_API int adamml_log_spectrogram(const float* wave, const float* basis, float* y, int N, int L, int n_fft, int win, int hop, float eps,
                            hipStream_t stream);
 
+/* Crop / scale / flip of decoded video frames on the GPU, byte-exact to Pillow's 8-bit BILINEAR resample (the visual transforms of
+ * utils/utils.py:110-150 get_augmentor before Stack: GroupMultiScaleCrop, GroupRandomScale + GroupRandomCrop, GroupScale +
+ * GroupCenterCrop, GroupRandomHorizontalFlip).  src: N videos in one flat buffer of src_bytes bytes, video i channels-last
+ * [H_i, W_i, K_in] at its own byte offset and row stride (the frames concatenated along the channel axis, as Stack does).
+ * y: [N, OH, OW, K_out] uint8, exactly the arrays Stack returns, stacked over the batch.
+ * meta: int32 [meta_len].  meta[10 i .. 10 i + 9] describes video i: offset low 32 bits, offset high 32 bits, H, W, row stride in
+ * bytes, column table index, column table stride, row table index, row table stride, flags (bit 0: store 255 - v on the even
+ * output channels -- the x images of a flipped flow video, ImageOps.invert).  A table of stride s holds one entry of s ints per
+ * output column (OW entries) or row (OH entries): first source index, tap count n <= min(s - 2, 32), then n int32 coefficients
+ * (Pillow's precompute_coeffs + normalize_coeffs_8bpc: int(0.5 + k * 2^22), each in [0, 2^22]).  Per output pixel and channel:
+ * h = clamp((2^21 + sum_x kx * src) >> 22, 0, 255) for each row tap, then clamp((2^21 + sum_y ky * h) >> 22, 0, 255) -- the
+ * horizontal pass first, clipped to a byte, as Pillow does.  An unchanged axis is one tap of 2^22; a flip is the reversed
+ * column table (adamml_amd/video.py builds and validates the tables).
+ * diffs = D > 0 (rgbdiff): K_in = G*3*(D+1) holds D+1 consecutive native RGB frames per frame group and K_out = G*3*D; each source
+ * sample is (next - cur + 255) >> 1 (utils/video_dataset.py:32-38 compute_img_diff), formed before the horizontal pass.
+ * diffs = 0: K_out == K_in.  Every source row / column index is clamped into its video's [0, H) x [0, W), every address into
+ * [0, src_bytes) and every table read into [0, meta_len): no table content makes the kernel read outside its buffers.
+ * Bounds: 0 <= N <= 65535, OH, OW, K_in, K_out >= 1, meta_len >= 10 N, checked before the pointers; N == 0 is a no-op. */
+ADAMML_API int adamml_video_resample_u8(const uint8_t* src, int64_t src_bytes, const int32_t* meta, int meta_len, uint8_t* y, int N, int OH,
+                             int OW, int K_in, int K_out, int diffs, hipStream_t stream);
+
 /* y[M,N] = act(x[M,K] @ w[N,K]^T + bias) in fp32 with arbitrary strides (nn.Linear / LSTMCell gates and their
  * gradients: policy_net.py:228-231,278-279,351-362; resnet.py:215; sound_mobilenet_v2.py:158) */
 ADAMML_API int adamml_gemm_f32(const float* a, int64_t a_sm, int64_t a_sk, const float* b, int64_t b_sn, int64_t b_sk, float* c,
