@@ -1,7 +1,8 @@
 """float64 references of the convolution kernels and the per-element error model they are checked with.
 
 Plain CPU module (it never touches torch.cuda): the GPU conformance rows (tests/test_conv_conformance_gpu.py) and the CPU
-sensitivity test (tests/test_conv_ref_cpu.py) both import it.
+sensitivity test (tests/test_conv_ref_cpu.py) both import it; tests/elementwise_ref.py builds the references of the BatchNorm, pooling,
+depthwise and stem kernels on the same helpers.
 
 Operands.  A reference is built from the exact operand values a kernel multiplies, not from an approximation of them:
 `lazy_operand` reproduces the lazily normalised read bf16(clamp(fmaf(z, scale, shift))) -- the fma in float64, rounded once to
@@ -58,8 +59,10 @@ def group_vec(v, g, gstride, c):
     return v[g * gstride: g * gstride + c]
 
 
-def lazy_operand(z, scale=None, shift=None, act=0, groups=1, gstride=0, cin_true=None):
-    """Exact operand values of an NHWC bf16 input [groups*N, H, W, C] as a kernel reads it -> float64 NHWC on the CPU."""
+def lazy_operand(z, scale=None, shift=None, act=0, groups=1, gstride=0, cin_true=None, round_bf16=True):
+    """Exact operand values of an NHWC bf16 input [groups*N, H, W, C] as a kernel reads it -> float64 NHWC on the CPU.
+    round_bf16 = False: the float32 value clamp(fmaf(z, scale, shift)) itself, for the kernels that compare, mask or accumulate it
+    without rounding it to bf16 (pools, global average pool, depthwise convs: tests/elementwise_ref.py)."""
     v = z.detach().cpu().double()
     C = v.shape[-1]
     if scale is not None:
@@ -71,7 +74,7 @@ def lazy_operand(z, scale=None, shift=None, act=0, groups=1, gstride=0, cin_true
             y = (v[g * n:(g + 1) * n] * s + t).to(torch.float32).double()
             if lo > -math.inf or hi < math.inf:
                 y = torch.clamp(y, min=lo if lo > -math.inf else None, max=hi if hi < math.inf else None)
-            out[g * n:(g + 1) * n] = bf16(y)
+            out[g * n:(g + 1) * n] = bf16(y) if round_bf16 else y
         v = out
     if cin_true is not None and cin_true < C:
         v = v.clone()
@@ -144,17 +147,23 @@ def bn_dgrad_sums_ref(gp, z, vec, groups=1):
     return out, ab
 
 
-def tolerance(ref, ab, n, rho, extra=None):
-    t = rho * ref.abs() + C_ACC * math.sqrt(n) * U32 * ab
+def acc_factor(n, acc=None):
+    """coefficient of 2^-24 * abs_i: C_ACC * sqrt(n) (the probabilistic bound of a length-n float32 sum) unless the caller counted the
+    float32 roundings of a short expression itself (acc = that count: the deterministic bound, tests/elementwise_ref.py)"""
+    return C_ACC * math.sqrt(n) if acc is None else (acc if torch.is_tensor(acc) else float(acc))
+
+
+def tolerance(ref, ab, n, rho, extra=None, acc=None):
+    t = rho * ref.abs() + acc_factor(n, acc) * U32 * ab
     return t if extra is None else t + extra
 
 
-def err_ratio(h, ref, ab, n, rho, extra=None):
+def err_ratio(h, ref, ab, n, rho, extra=None, acc=None):
     """max over the elements of |h - ref| / tol (NaN anywhere in h where ref is finite -> inf)"""
     h = h.detach().cpu().double()
     err = (h - ref).abs()
     err = torch.where(torch.isnan(err), torch.full_like(err, math.inf), err)
-    tol = tolerance(ref, ab, n, rho, extra)
+    tol = tolerance(ref, ab, n, rho, extra, acc)
     # (tol == 0 only where ref and abs are exactly 0: padding rows; any non-zero h there is an error)
     r = err / torch.where(tol > 0, tol, torch.full_like(tol, 1e-300))
     return r.max().item() if r.numel() else 0.0
@@ -166,29 +175,32 @@ def ulp_bf16(x):
     return torch.pow(2.0, e - 7)
 
 
-def rounding_bias(h, ref, ab, n, extra=None):
+def rounding_bias(h, ref, ab, n, extra=None, acc=None):
     """mean of (h - ref) * sign(ref) / ulp(ref) over the elements whose accumulation term is below 1/4 ulp -> (bias, count)"""
     h = h.detach().cpu().double().reshape(-1)
+    af = acc_factor(n, acc)
+    if torch.is_tensor(af):
+        af = af.expand(ref.shape).reshape(-1)
     ref, ab = ref.reshape(-1), ab.reshape(-1)
     nz = ref != 0
     u = torch.ones_like(ref)
     u[nz] = ulp_bf16(ref[nz])
-    acc = C_ACC * math.sqrt(n) * U32 * ab + (0 if extra is None else extra.reshape(-1))
-    sel = nz & (acc <= 0.25 * u) & torch.isfinite(h)
+    at = af * U32 * ab + (0 if extra is None else extra.reshape(-1))
+    sel = nz & (at <= 0.25 * u) & torch.isfinite(h)
     if int(sel.sum()) == 0:
         return 0.0, 0
     d = ((h[sel] - ref[sel]) * torch.sign(ref[sel]) / u[sel]).clamp(-1, 1)
     return d.mean().item(), int(sel.sum())
 
 
-def check(h, ref, ab, n, rho=RHO_BF16, extra=None, what="", bias=None):
+def check(h, ref, ab, n, rho=RHO_BF16, extra=None, what="", bias=None, acc=None):
     """Assert the per-element bound (and, for bf16 outputs of >= 10^4 elements, the rounding bias); returns max err / tol."""
-    r = err_ratio(h, ref, ab, n, rho, extra)
+    r = err_ratio(h, ref, ab, n, rho, extra, acc)
     assert r <= 1.0, "%s: max err/tol %.3g (n = %d)" % (what, r, n)
     if bias is None:
         bias = rho == RHO_BF16 and ref.numel() >= BIAS_MIN_ELEMENTS and extra is None
     if bias:
-        b, cnt = rounding_bias(h, ref, ab, n, extra)
+        b, cnt = rounding_bias(h, ref, ab, n, extra, acc)
         assert cnt >= 1000, "%s: only %d elements qualify for the rounding-bias check" % (what, cnt)
         assert abs(b) <= BIAS_LIMIT, "%s: rounding bias %.3f ulp over %d elements" % (what, b, cnt)
     return r
