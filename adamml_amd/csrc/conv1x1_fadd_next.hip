@@ -446,8 +446,7 @@ __global__ __launch_bounds__(NW * 64, 1) void conv1x1_fadd_tpool_kernel(FTP p) {
 
 // d: the forward descriptor of conv3 (1x1, 64 -> 256); next_cout: output channels of the next block's conv1 (64) or 0
 bool adamml_conv1x1_fadd_next_supported(const adamml_conv_desc_t* d, int next_cout) {
-    static const int on = getenv("ADAMML_FADD_NEXT") ? atoi(getenv("ADAMML_FADD_NEXT")) : 1;            // A/B aid
-    return on && d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && d->up <= 1 && d->Cin == C3IN && d->Cout == CB &&
+    return d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && d->up <= 1 && d->Cin == C3IN && d->Cout == CB &&
            (next_cout == 0 || next_cout == C1OUT);
 }
 
@@ -493,8 +492,7 @@ int adamml_conv1x1_fadd_next_launch(const adamml_conv_desc_t* d, const void* x, 
 
 // d: the forward descriptor of conv3 (1x1, 64 -> 256, N = clips * frames images per group)
 bool adamml_conv1x1_fadd_tpool_supported(const adamml_conv_desc_t* d, int frames) {
-    static const int on = getenv("ADAMML_FADD_TPOOL_STREAM") ? atoi(getenv("ADAMML_FADD_TPOOL_STREAM")) : 1;      // A/B aid
-    return on && d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && d->up <= 1 && d->Cin == C3IN && d->Cout == CB &&
+    return d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && d->up <= 1 && d->Cin == C3IN && d->Cout == CB &&
            (frames == 2 || frames == 4 || frames == 8) && d->N % frames == 0;
 }
 

@@ -365,13 +365,13 @@ __global__ __launch_bounds__(NQ * 64, NQ == 4 ? 2 : 1) void conv1x1_fadd_tpool_s
 
 int fs_blocks(long P, int groups) {
     const long ntile = (P + TPX - 1) / TPX;
-    static const long cap0 = getenv("ADAMML_FADD_STREAM_CAP") ? atol(getenv("ADAMML_FADD_STREAM_CAP")) : 256;    // A/B aid
-    long cap = cap0 / (groups < 1 ? 1 : groups);
+    constexpr long CAP = 256;                                            // one workgroup per CU over all groups
+    long cap = CAP / (groups < 1 ? 1 : groups);
     if (cap < 1) cap = 1;
     return (int)(ntile < cap ? ntile : cap);
 }
 
-bool fs_on() { const char* e = getenv("ADAMML_FADD_STREAM"); return !(e && atoi(e) == 0); }                      // A/B aid, read at every call
+bool fs_on() { const char* e = getenv("ADAMML_FADD_STREAM"); return !(e && atoi(e) == 0); }                      // test hook, read at every call
 
 }  // namespace
 
@@ -402,7 +402,7 @@ int adamml_conv1x1_fadd_stream_launch(const adamml_conv_desc_t* d, const void* x
 
 // d: the forward descriptor of conv3 (N = clips * frames images per group)
 int adamml_conv1x1_fadd_tpool_stream_supported(const adamml_conv_desc_t* d, int frames) {
-    const char* e = getenv("ADAMML_FADD_TPOOL_SLICE");                                                             // A/B aid, read at every call
+    const char* e = getenv("ADAMML_FADD_TPOOL_SLICE");                                                             // test hook, read at every call
     const int mode = e ? atoi(e) : 1;                                                                              // 0: off, 1: layer 2, 2: layers 1 and 2
     if (!mode || !d) return 0;
     const bool l2 = d->Cin == 128 && d->Cout == 512, l1 = mode >= 2 && d->Cin == 64 && d->Cout == 256;

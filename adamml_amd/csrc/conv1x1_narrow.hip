@@ -655,8 +655,7 @@ int narrow_wgrad_launch(const NW1P& p, int groups, int nblk, hipStream_t stream)
 static int narrow_ks(int Cin) { return (Cin + 31) / 32; }
 
 bool adamml_conv1x1_narrow_fwd_supported(const adamml_conv_desc_t* d) {
-    static const int on = getenv("ADAMML_NARROW_STREAM") ? atoi(getenv("ADAMML_NARROW_STREAM")) : 1;      // A/B aid: 0 = conv_gemm_kernel
-    if (!on || d->KH != 1 || d->KW != 1 || d->stride != 1 || d->pad != 0 || d->up > 1 || d->accumulate) return false;
+    if (d->KH != 1 || d->KW != 1 || d->stride != 1 || d->pad != 0 || d->up > 1 || d->accumulate) return false;
     if (d->Cin % 8 || d->Cout % 8) return false;
     const int ks = narrow_ks(d->Cin), co = d->Cout;
     return (ks == 1 && (co == 16 || co == 96 || co == 144 || co == 192)) || (ks == 3 && co == 24) || (ks == 5 && (co == 24 || co == 32)) ||
@@ -685,8 +684,7 @@ int adamml_conv1x1_narrow_fwd_launch(const adamml_conv_desc_t* d, const void* x,
 
 // ---- weight gradient: (Cout, Cin) pairs with an instance = the same layers
 bool adamml_conv1x1_narrow_wgrad_supported(const adamml_conv_desc_t* d, int cin_true) {
-    static const int on = getenv("ADAMML_NARROW_STREAM") ? atoi(getenv("ADAMML_NARROW_STREAM")) : 1;
-    if (!on || d->KH != 1 || d->KW != 1 || d->stride != 1 || d->pad != 0 || d->up > 1 || cin_true != d->Cin) return false;
+    if (d->KH != 1 || d->KW != 1 || d->stride != 1 || d->pad != 0 || d->up > 1 || cin_true != d->Cin) return false;
     const int co = d->Cout, ci = d->Cin;
     return (co == 96 && ci == 16) || (co == 16 && ci == 32) || (co == 24 && ci == 96) || (co == 144 && ci == 24) || (co == 24 && ci == 144) ||
            (co == 32 && ci == 144) || (co == 192 && ci == 32) || (co == 32 && ci == 192);
@@ -729,8 +727,7 @@ static bool narrow_dual_expansion(const adamml_conv_desc_t* d) {
 }
 
 bool adamml_conv1x1_narrow_dual_supported(const adamml_conv_desc_t* d) {
-    static const int on = getenv("ADAMML_NARROW_STREAM") ? atoi(getenv("ADAMML_NARROW_STREAM")) : 1;
-    if (!on || d->KH != 1 || d->KW != 1 || d->stride != 1 || d->pad != 0 || d->up > 1) return false;
+    if (d->KH != 1 || d->KW != 1 || d->stride != 1 || d->pad != 0 || d->up > 1) return false;
     // measured (round 6, three alternating pairs on one box): Sound-MobileNetV2 15.5 ms with, 15.6 ms without; step 108.05 / 108.06 / 107.46 ms with,
     // 107.66 / 107.76 / 107.80 ms without -- the pass it saves is paid back by the second operand stream of the K = 96 .. 192 loader.  Off by
     // default; ADAMML_NARROW_DUAL_EXP=1 enables it (the instances are tested either way: tests/test_kernels_gpu.py)
@@ -782,8 +779,7 @@ int adamml_conv1x1_narrow_dual_launch(const adamml_conv_desc_t* d, const void* g
 // ---- plain-loader data gradient of the EXPANSION convs (K = d->Cin = 96 / 144 / 192 gradient channels -> 16 / 24 / 32) with the BatchNorm-fused
 // epilogue (adamml_conv_bwd_data_bn) or accumulating into dx.  d: the data-gradient-shaped descriptor conv_launch works with.
 bool adamml_conv1x1_narrow_dgrad_epi_supported(const adamml_conv_desc_t* d) {
-    static const int on = getenv("ADAMML_NARROW_STREAM") ? atoi(getenv("ADAMML_NARROW_STREAM")) : 1;
-    if (!on || d->KH != 1 || d->KW != 1 || d->stride != 1 || d->pad != 0 || d->up > 1) return false;
+    if (d->KH != 1 || d->KW != 1 || d->stride != 1 || d->pad != 0 || d->up > 1) return false;
     const int ks = narrow_ks(d->Cin), co = d->Cout;
     return d->Cin % 8 == 0 && ((ks == 3 && co == 16) || (ks == 5 && (co == 24 || co == 32)) || (ks == 6 && co == 32));
 }

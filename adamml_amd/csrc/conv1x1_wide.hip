@@ -376,7 +376,7 @@ int wide_all_launch(WXP& p, int groups, hipStream_t stream) {
 }
 
 
-bool wide_on() {           // A/B aid: ADAMML_WIDE_STREAM=0 = conv_gemm_kernel.  Read at every call (no cached state: a test flips it within one process)
+bool wide_on() {           // test hook: ADAMML_WIDE_STREAM=0 = conv_gemm_kernel.  Read at every call (no cached state: a test flips it within one process)
     const char* e = getenv("ADAMML_WIDE_STREAM");
     return !(e && e[0] == '0');
 }

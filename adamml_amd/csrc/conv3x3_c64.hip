@@ -73,7 +73,6 @@ struct C3P {
     int N, H, W, R, tiles_per_img, tiles_per_group, total_tiles, tpb;
     int PW, PR, npt;         // patch width / rows (pixels); pixel tiles per tile
     int in_gstride;
-    int wswz;                // 1: weight rows stored with the chunk swizzle (A/B aid ADAMML_C64_WSWZ)
     size_t gxy;              // elements per group of x and y (same shape)
 };
 
@@ -156,7 +155,7 @@ __global__ __launch_bounds__(NT3, 1) void conv3x3_c64_kernel(C3P p) {
         // 16-byte chunk ch of row co sits at position ch ^ wswz(co): with the 73-chunk row pitch the 16 lanes of a gfx950 ds_read_b128 service
         // group (rows {0-3, 12-15} at chunk c and rows {4-11} at chunk c + 1, or the complement) then touch 16 distinct 16-byte bank units;
         // unswizzled they touched 9 (2-way conflicts on every weight fragment read: SQ_LDS_BANK_CONFLICT 34-41 % of the LDS cycles, round 2)
-        *reinterpret_cast<bf16x8*>(s_w + co * WROW3 + (ch ^ (((co >> 2) ^ (co >> 3)) & p.wswz)) * 16) = *reinterpret_cast<const bf16x8*>(p.w + (size_t)co * KT3 + ch * 8);
+        *reinterpret_cast<bf16x8*>(s_w + co * WROW3 + (ch ^ (((co >> 2) ^ (co >> 3)) & 1)) * 16) = *reinterpret_cast<const bf16x8*>(p.w + (size_t)co * KT3 + ch * 8);
     }
     for (int i = tid; i < 8 * 128; i += NT3) cs[i] = 0.f;
     float* csw = cs + wave * 128;
@@ -285,7 +284,7 @@ __global__ __launch_bounds__(NT3, 1) void conv3x3_c64_kernel(C3P p) {
             const int r = q / p.W, c = q - r * p.W;
             pixoff[j] = (r * p.PW + c) * PP + lg * 16;
         }
-        const char* wbase = s_w + li * WROW3 + (lg ^ (((li >> 2) ^ (li >> 3)) & p.wswz)) * 16;
+        const char* wbase = s_w + li * WROW3 + (lg ^ (((li >> 2) ^ (li >> 3)) & 1)) * 16;
         const bool last_live = (wave + 24) * 16 < npx;
         C64_TS(3);
         // Two copies of the loop, for waves with 4 and with 3 live pixel tiles (dead ones of a short strip read valid patch addresses and are
@@ -642,11 +641,7 @@ __global__ __launch_bounds__(NT3, 1) void conv3x3_c64_wgrad_kernel(C3WP p) {
 
 }  // namespace
 
-// d: the FORWARD-shaped descriptor of the conv that is executed (for a data gradient: H/W of dz == H/W of dx).
-static int c3_pitch() {
-    static const int pp = getenv("ADAMML_C64_PITCH") ? atoi(getenv("ADAMML_C64_PITCH")) : 144;      // A/B aid: 144 | 160
-    return pp == 160 ? 160 : 144;
-}
+constexpr int PITCH3 = 144;             // patch pixel pitch in bytes (144 | 160: see conv3x3_c64_kernel)
 
 // rows per strip of the forward / data-gradient kernel: the largest R <= 512 / W (preferring, among the top four, one that divides H)
 // whose patch fits beside the resident weights at pixel pitch `pitch`; 0 when none does
@@ -671,7 +666,7 @@ bool adamml_conv3x3_c64_supported(const adamml_conv_desc_t* d) {
     if (d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad != 1 || d->Cin != 64 || d->Cout != 64 || (d->up > 1)) return false;
     if (d->OH != d->H || d->OW != d->W || d->accumulate) return false;
     if (d->W < 8 || d->W > MAXPX3 / 2) return false;        // at least 2 rows per tile
-    return c3_rows(d, 144) >= 2 && c3_rows(d, c3_pitch()) >= 2;
+    return c3_rows(d, PITCH3) >= 2;
 }
 
 int adamml_conv3x3_c64_launch(const adamml_conv_desc_t* d, const void* x, const void* w_packed, const float* in_scale,
@@ -681,10 +676,7 @@ int adamml_conv3x3_c64_launch(const adamml_conv_desc_t* d, const void* x, const 
     p.x = (const bf16_t*)x; p.w = (const bf16_t*)w_packed; p.in_scale = in_scale; p.in_shift = in_shift; p.y = (bf16_t*)y;
     p.stats = stats; p.bn_z = (const bf16_t*)bn_z; p.bn_vec = bn_vec; p.bn_act = bn_act; p.act = d->act;
     p.N = d->N; p.H = d->H; p.W = d->W;
-    const int pitch = c3_pitch();
-    const int R = c3_rows(d, pitch);
-    static const int wswz = getenv("ADAMML_C64_WSWZ") ? atoi(getenv("ADAMML_C64_WSWZ")) & 1 : 1;
-    p.wswz = wswz;
+    const int R = c3_rows(d, PITCH3);
     p.R = R; p.PR = R + 2; p.PW = d->W + 2;
     p.npt = (R * d->W + 31) / 32 * 2;            // staged rows cover whole 32-pixel statistic steps
     const int groups = d->groups < 1 ? 1 : d->groups;
@@ -695,26 +687,19 @@ int adamml_conv3x3_c64_launch(const adamml_conv_desc_t* d, const void* x, const 
     p.in_gstride = d->in_gstride;
     p.gxy = (size_t)d->N * d->H * d->W * C64;
     p.tpb = ceil_div(p.total_tiles, 1024);
-    const size_t patch = (size_t)p.PR * p.PW * pitch, stage = (size_t)p.npt * 16 * SROW3;
+    const size_t patch = (size_t)p.PR * p.PW * PITCH3, stage = (size_t)p.npt * 16 * SROW3;
     const size_t lds = C64 * WROW3 + CS3_BYTES + (patch > stage ? patch : stage);
     static AdamLdsOnce attr_once;                    // (per device: common.h)
     const int attr_dev = adamml_current_device();
     if (!attr_once.test(attr_dev)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_c64_kernel<false, 144>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_c64_kernel<true, 144>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_c64_kernel<false, 160>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_c64_kernel<true, 160>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_c64_kernel<false, PITCH3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_c64_kernel<true, PITCH3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return adamml_set_error(ADAMML_ELAUNCH, "conv3x3_c64: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
         attr_once.set(attr_dev);
     }
     const dim3 grid(ceil_div(p.total_tiles, p.tpb));
-    if (pitch == 160) {
-        if (p.bn_z) hipLaunchKernelGGL((conv3x3_c64_kernel<true, 160>), grid, dim3(NT3), C64_LDS(lds), stream, p);
-        else hipLaunchKernelGGL((conv3x3_c64_kernel<false, 160>), grid, dim3(NT3), C64_LDS(lds), stream, p);
-    } else {
-        if (p.bn_z) hipLaunchKernelGGL((conv3x3_c64_kernel<true, 144>), grid, dim3(NT3), C64_LDS(lds), stream, p);
-        else hipLaunchKernelGGL((conv3x3_c64_kernel<false, 144>), grid, dim3(NT3), C64_LDS(lds), stream, p);
-    }
+    if (p.bn_z) hipLaunchKernelGGL((conv3x3_c64_kernel<true, PITCH3>), grid, dim3(NT3), C64_LDS(lds), stream, p);
+    else hipLaunchKernelGGL((conv3x3_c64_kernel<false, PITCH3>), grid, dim3(NT3), C64_LDS(lds), stream, p);
     return adamml_check_launch("conv3x3_c64");
 }
 
@@ -727,7 +712,7 @@ static int c3_geometry(const adamml_conv_desc_t* d, int* R_out) {
     return ceil_div(d->H, R);
 }
 
-// (128 channels: the four-quadrant form; ADAMML_C64_WGRAD_Q=0 disables it, read at every call: A/B aid)
+// (128 channels: the four-quadrant form; ADAMML_C64_WGRAD_Q=0 disables it, read at every call: test hook)
 static bool c3_wgrad_quad(const adamml_conv_desc_t* d, int cin_true) {
     const char* e = getenv("ADAMML_C64_WGRAD_Q");
     if (e && atoi(e) == 0) return false;

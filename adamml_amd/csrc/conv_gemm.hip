@@ -1769,8 +1769,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce4_kernel(const float* ws, flo
 
 // picks the 16-byte form whenever the index count allows it
 void launch_wgrad_reduce(const float* ws, float* dw, size_t n, int nsplit, int taps, int cin, int store, int groups, hipStream_t stream) {
-    static const bool wide = !(getenv("ADAMML_REDUCE4") && getenv("ADAMML_REDUCE4")[0] == '0');       // A/B aid
-    if (wide && n % 4 == 0 && (reinterpret_cast<uintptr_t>(ws) & 15) == 0)
+    if (n % 4 == 0 && (reinterpret_cast<uintptr_t>(ws) & 15) == 0)
         hipLaunchKernelGGL(wgrad_reduce4_kernel, dim3((unsigned)((n / 4 + 15) / 16), groups), dim3(256), 0, stream, ws, dw, n, nsplit, taps, cin, store);
     else
         hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n + 15) / 16), groups), dim3(256), 0, stream, ws, dw, n, nsplit, taps, cin, store);
@@ -1930,11 +1929,10 @@ static int conv_launch(const adamml_conv_desc_t* d, const void* x, const void* w
     const bool deep = (long)grid.x * grid.y <= 768 && nk >= 8 && mode != 1;
     if (fadd) {
         if (mode != 0 || res || dual || cat || stats) return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_fwd_bn_add: only 1x1 / stride-1 convs");
-        static const int fadd_glds = getenv("ADAMML_FADD_GLDS") ? atoi(getenv("ADAMML_FADD_GLDS")) : 2;     // 0: register ring, 1: LDS-DMA, 2: + EID
-        if (fadd_glds && (!in_scale || p.K <= 512)) {
+        if (!in_scale || p.K <= 512) {
             // operands by LDS-DMA (a lazily normalised input is transformed at the fragment: LZF); with an identity operand, that one is
             // requested at the start of each tile (EID)
-            const bool eid = fadd_glds > 1 && p.res_out;
+            const bool eid = p.res_out != nullptr;
             if (tp) {
 #define LAUNCH_TP(TV)                                                                                                                                        \
                 do {                                                                                                                                         \
@@ -1966,7 +1964,6 @@ static int conv_launch(const adamml_conv_desc_t* d, const void* x, const void* w
     }
     if (res) {
         if (mode != 0) return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_data_res: only 1x1 / stride-1 convs");
-        static const bool res_eid = !(getenv("ADAMML_RES_EID") && getenv("ADAMML_RES_EID")[0] == '0');
         if (pf) {
             if (BC != 128 || d->Cout % 128 || pf->C != 64 || in_scale || !p.res_mask || !p.accumulate || p.bn_z || p.bn_z2 || !stats)
                 return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_data_res_prod: needs Cout %% 128 == 0, a 64-channel product operand, "
@@ -1984,7 +1981,7 @@ static int conv_launch(const adamml_conv_desc_t* d, const void* x, const void* w
             return adamml_check_launch("conv_bwd_data_res_prod (reduce)");
         }
         if (in_scale) return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_data_res: the gradient operand is never lazy");
-        if (res_eid && p.res_mask && p.accumulate && !p.bn_z && !p.bn_z2) {
+        if (p.res_mask && p.accumulate && !p.bn_z && !p.bn_z2) {
             // the algebraic backward's form (identity gradient + 1-bit mask, sum(g') only): identity-side loads at the start of each tile
             if (BC == 64) hipLaunchKernelGGL((conv_gemm_kernel<64, 0, 1, true, false, false, false, true, 1>), grid, block, 0, stream, p);
             else hipLaunchKernelGGL((conv_gemm_kernel<128, 0, 1, true, false, false, false, true, 1>), grid, block, 0, stream, p);
@@ -2006,11 +2003,10 @@ static int conv_launch(const adamml_conv_desc_t* d, const void* x, const void* w
         else hipLaunchKernelGGL((conv_gemm_kernel<128, 0, 2, false, true>), grid, block, 0, stream, p);       // (a third ring slot of g, z and weights does not fit 256 registers at 128-wide tiles)
         return adamml_check_launch("conv_bwd_data_dual");
     }
-    static const bool glds_on = !(getenv("ADAMML_CONV_GLDS") && getenv("ADAMML_CONV_GLDS")[0] == '0');
     // (the fragment-side lazy transform, LZF, is NOT used for the plain forward convs: measured 5-10 % slower than the register-staged
     // loader -- layer-1 conv3 1.77 vs 1.61 ms, layer 2 0.59 vs 0.54, layer 3 0.23 vs 0.21: each pixel half is transformed by two waves,
     // between the ds_read and the MFMA; it only pays together with the early identity loads of the FADD kernel)
-    const bool glds = glds_on && !in_scale && mode != 2;
+    const bool glds = !in_scale && mode != 2;
     // the epilogue is a template parameter (EPI) of the LDS-DMA and one-step instances; deep-prefetch and MODE 2 keep the run-time form
     const int epi = bn_z ? 1 : (p.accumulate ? 2 : 0);
 #define LAUNCH_EPI(BCV, MODEV, GL)                                                                                                          \
@@ -2130,9 +2126,7 @@ extern "C" int adamml_conv_fwd_bn_add_tpool_supported(const adamml_conv_desc_t* 
     if (!adamml_conv_fwd_bn_add_supported(d)) return 0;
     if (!(frames == 2 || frames == 4 || frames == 8) || d->N % frames || d->Cout % 128 || act != ADAMML_ACT_RELU) return 0;
     if (lazy_input && d->Cin > 512) return 0;                         // (the fragment-side lazy transform keeps its vectors in LDS)
-    static const bool on = !(getenv("ADAMML_FADD_TPOOL") && getenv("ADAMML_FADD_TPOOL")[0] == '0') &&
-                           !(getenv("ADAMML_FADD_GLDS") && atoi(getenv("ADAMML_FADD_GLDS")) < 2);
-    return on ? 1 : 0;
+    return 1;
 }
 
 // which kernel serves adamml_conv_fwd_bn_add_tpool (a label for profilers): 0 = the tile kernel's TP instance, 1 = the round-5 streaming kernel
@@ -2288,11 +2282,6 @@ bool adamml_alg_stream_supported(int Cout, int Cin);
 int adamml_alg_stream_launch(const adamml_conv_desc_t* d, const void* g, const void* a, const float* a_scale, const float* a_shift,
                              const void* w_alg, const float* epi_add, void* dx, int accumulate, const void* z_in, const float* bn_vec,
                              int act, double* sums, hipStream_t stream);
-static bool alg_stream_enabled() {           // ADAMML_ALG_STREAM=0: A/B aid (falls back to the CAT instance of conv_gemm_kernel)
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("ADAMML_ALG_STREAM"); on = (e && e[0] == '0') ? 0 : 1; }
-    return on == 1;
-}
 
 // ---- algebraic BatchNorm backward through a 1x1 conv z = W a followed by a linear BatchNorm (dz = A g' + B z + C per channel):
 //   dx = (W^T diag(A)) g' + (W^T diag(B) W) a + W^T C,   dW = A (.) (g'^T a) + B (.) (W G) + C (x) s,  G = a^T a, s = sum_p a
@@ -2421,7 +2410,7 @@ extern "C" int adamml_conv_bwd_data_alg(const adamml_conv_desc_t* d, const void*
     gd.OH = d->H; gd.OW = d->W; gd.Cout = d->Cin;
     gd.stride = 1; gd.up = 1; gd.pad = 0;
     gd.act = d->act; gd.accumulate = accumulate ? 1 : 0; gd.in_gstride = d->in_gstride;
-    if (adamml_alg_stream_supported(d->Cout, d->Cin) && alg_stream_enabled())
+    if (adamml_alg_stream_supported(d->Cout, d->Cin))
         return adamml_alg_stream_launch(d, g, a, a_scale, a_shift, w_alg, epi_add, dx, accumulate, z_in, bn_vec, act, sums, stream);
     CatIn c{a, d->Cin, (size_t)d->Cin * (d->Cout + d->Cin), epi_add};
     return conv_launch(&gd, g, w_alg, a_scale, a_shift, dx, sums, z_in, bn_vec, act, stream, nullptr, nullptr, nullptr, &c);
@@ -2666,10 +2655,7 @@ static int wgrad_launch(const adamml_conv_desc_t* d, const void* dz, const void*
         p.pix_per_block = pl.per_block;
         p.dz_scale = ex ? ex->dz_scale : nullptr; p.dz_shift = ex ? ex->dz_shift : nullptr;
         p.dz_act = ex ? ex->dz_act : 0; p.dz_gstride = ex ? ex->dz_gstride : 0;
-        static const bool glds_on = !(getenv("ADAMML_WGRAD_GLDS") && getenv("ADAMML_WGRAD_GLDS")[0] == '0');
-        static const bool lzb_on = !(getenv("ADAMML_WGRAD_LZB") && getenv("ADAMML_WGRAD_LZB")[0] == '0');
-        static const bool ragged256 = !(getenv("ADAMML_WGRAD_RAGGED") && getenv("ADAMML_WGRAD_RAGGED")[0] == '0');   // measured +4 % (layer-2 3x3)
-        if (glds_on && lzb_on && ws && in_scale && !(ex && ex->dz_scale) && pl.BM == 128 && pl.BN == 128 && d->KH * d->KW == 1 && d->pad == 0) {
+        if (ws && in_scale && !(ex && ex->dz_scale) && pl.BM == 128 && pl.BN == 128 && d->KH * d->KW == 1 && d->pad == 0) {
             // 1x1 conv with a lazily normalised input: LDS-DMA staging of the raw tensor, transform at the B fragment (LZB); same tile choice
             if (d->Cout % 256 == 0 && pl.n_tiles <= 64) {
                 p.n_cotiles = d->Cout / 256; p.n_tiles = p.n_cotiles * ceil_div(pl.NK, 128);
@@ -2680,7 +2666,7 @@ static int wgrad_launch(const adamml_conv_desc_t* d, const void* dz, const void*
             } else
             hipLaunchKernelGGL((conv_wgrad_glds_kernel<128, 128, 3, true>), grid, block, 0, stream, p);
         } else
-        if (glds_on && ws && !in_scale && !(ex && ex->dz_scale) && pl.BM == 128 && pl.BN == 128) {
+        if (ws && !in_scale && !(ex && ex->dz_scale) && pl.BM == 128 && pl.BN == 128) {
             // both operands plain in memory: LDS-DMA staging
             // 256-wide tiles halve the operand bytes fetched per MAC (this kernel is bound by the L1 load path: 16 KB per 128 x 128 x 32
             // step = 256 cycles of 64 B/clk against 256 cycles of MFMA).  Measured (tools/bench_conv.py, B = 72, TFLOP/s 128^2 -> wide):
@@ -2690,8 +2676,8 @@ static int wgrad_launch(const adamml_conv_desc_t* d, const void* dz, const void*
             if (d->Cout % 256 == 0 && pl.n_tiles <= 64) {
                 p.n_cotiles = d->Cout / 256; p.n_tiles = p.n_cotiles * ceil_div(pl.NK, 128);
                 hipLaunchKernelGGL((conv_wgrad_glds_kernel<256, 128, 2>), dim3(pl.nsplit * p.n_tiles * groups), block, 0, stream, p);
-            } else if (d->Cout == 128 && (pl.NK % 256 == 0 || (ragged256 && pl.NK > 512))) {
-                // (NK % 256 != 0: the last tile is half empty -- 3x3 / 128 -> 128: 5 tiles of 256 instead of 9 of 128)
+            } else if (d->Cout == 128 && (pl.NK % 256 == 0 || pl.NK > 512)) {
+                // (NK % 256 != 0: the last tile is half empty -- 3x3 / 128 -> 128: 5 tiles of 256 instead of 9 of 128; measured +4 %)
                 p.n_tiles = p.n_cotiles * ceil_div(pl.NK, 256);
                 hipLaunchKernelGGL((conv_wgrad_glds_kernel<128, 256, 2>), dim3(pl.nsplit * p.n_tiles * groups), block, 0, stream, p);
             } else

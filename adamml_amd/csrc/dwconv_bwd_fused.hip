@@ -422,7 +422,7 @@ __global__ __launch_bounds__(NT, 2) void dwconv_bwd_fused_s2_kernel(DwBP p) {
 
 // pixels per thread: 3 (256 registers, none spilled; 4 spills 78 of them, 2 re-reads every halo column)
 int fused_segw() {
-    static const int v = getenv("ADAMML_DWB_SEGW") ? atoi(getenv("ADAMML_DWB_SEGW")) : 3;          // A/B aid
+    static const int v = getenv("ADAMML_DWB_SEGW") ? atoi(getenv("ADAMML_DWB_SEGW")) : 3;          // test hook
     return v == 2 ? 2 : 3;
 }
 
@@ -436,8 +436,8 @@ int fused_blocks(const adamml_conv_desc_t* d, int* rows_per_thread, int* nseg, i
     const int rows = d->stride == 2 ? (d->H + 1) / 2 : d->H;
     *nseg = d->stride == 2 ? ceil_div((d->W + 1) / 2, fused_qw()) : ceil_div(d->W, fused_segw());
     const int groups = d->groups < 1 ? 1 : d->groups;
-    static const long min_blocks = getenv("ADAMML_DWB_MIN_BLOCKS") ? atol(getenv("ADAMML_DWB_MIN_BLOCKS")) : 256;       // A/B aids
-    static const int max_rows = getenv("ADAMML_DWB_MAX_ROWS") ? atoi(getenv("ADAMML_DWB_MAX_ROWS")) : 24;
+    constexpr long min_blocks = 256;
+    constexpr int max_rows = 24;
     int nb_rows = ceil_div(rows, max_rows);
     while (ceil_div(rows, nb_rows) > 3 && (long)groups * d->N * nb_rows * *nseg * nchunk < min_blocks * NT) ++nb_rows;
     const int rpt = ceil_div(rows, nb_rows);
@@ -447,9 +447,8 @@ int fused_blocks(const adamml_conv_desc_t* d, int* rows_per_thread, int* nseg, i
     const long nb = (threads + NT - 1) / NT;
     // NT * nblk must be a multiple of nchunk (a thread keeps its channel chunk across tasks): 45 | nblk covers every C / 4 of the
     // MobileNetV2s; every workgroup publishes one [9][C] partial, so at most one workgroup per 144 pixels of a group
-    static const long cap0 = getenv("ADAMML_DWB_CAP") ? atol(getenv("ADAMML_DWB_CAP")) : 2160;
+    constexpr long cap0 = 2160, px_per_wg = 144;
     long cap = cap0 / groups / 45 * 45 > 0 ? cap0 / groups / 45 * 45 : 45;
-    static const long px_per_wg = getenv("ADAMML_DWB_PX_PER_WG") ? atol(getenv("ADAMML_DWB_PX_PER_WG")) : 144;
     const long by_work = ((long)d->N * d->H * d->W / px_per_wg + 44) / 45 * 45;
     if (by_work < cap) cap = by_work > 45 ? by_work : 45;
     int nblk = nb >= cap ? (int)cap : (int)((nb + 44) / 45 * 45);
@@ -460,8 +459,7 @@ int fused_blocks(const adamml_conv_desc_t* d, int* rows_per_thread, int* nseg, i
 }  // namespace
 
 extern "C" int adamml_dwconv_bwd_fused_supported(const adamml_conv_desc_t* d) {
-    static const bool on = !(getenv("ADAMML_DW_BWD_FUSED") && atoi(getenv("ADAMML_DW_BWD_FUSED")) == 0);                // A/B aid
-    return on && d && d->KH == 3 && d->KW == 3 && d->Cin == d->Cout && d->Cin % 8 == 0 && d->Cin <= 960 && d->pad == 1 &&
+    return d && d->KH == 3 && d->KW == 3 && d->Cin == d->Cout && d->Cin % 8 == 0 && d->Cin <= 960 && d->pad == 1 &&
            ((d->stride == 1 && d->OH == d->H && d->OW == d->W) || (d->stride == 2 && d->OH == (d->H - 1) / 2 + 1 && d->OW == (d->W - 1) / 2 + 1)) &&
            (size_t)d->N * d->H * d->W * d->Cin * 2 < ((size_t)1 << 32) ? 1 : 0;       // (32-bit byte offsets within a group)
 }

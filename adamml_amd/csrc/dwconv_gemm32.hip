@@ -775,14 +775,14 @@ static unsigned dw_walk_grid(DwP& p, int segw, int groups) {
     // rows walked per thread: long walks amortise the 2-row window prologue and the statistics epilogue (a workgroup of 3-row walks
     // spends as long publishing its sums as computing; the late 16^2 / 8^2 layers ran at half their no-statistics rate), whole image
     // columns where OH <= 24, equal row blocks otherwise; split further only while the grid is below one workgroup per CU
-    static const long min_blocks = getenv("ADAMML_DW_MIN_BLOCKS") ? atol(getenv("ADAMML_DW_MIN_BLOCKS")) : 256;     // A/B aids
-    static const int max_rows = getenv("ADAMML_DW_MAX_ROWS") ? atoi(getenv("ADAMML_DW_MAX_ROWS")) : 24;
+    constexpr long min_blocks = 256;
+    constexpr int max_rows = 24;
     p.nrb = ceil_div(p.OH, max_rows);
     while (ceil_div(p.OH, p.nrb) > 3 && (long)groups * p.N * p.nrb * p.nseg * (p.C / 4) < min_blocks * NT) ++p.nrb;
     p.rows_per_thread = ceil_div(p.OH, p.nrb);
     p.nrb = ceil_div(p.OH, p.rows_per_thread);
     const int nchunk = p.C / 4;
-    static const int cw_min = getenv("ADAMML_DW_CW_MIN") ? atoi(getenv("ADAMML_DW_CW_MIN")) : 16;         // A/B aid (1024: whole channel rows)
+    constexpr int cw_min = 16;
     int best = 0, best_active = 0;
     for (int pass = 0; pass < 2 && !best; ++pass)           // pass 0: divisors in [cw_min, 64], fewest idle threads; pass 1: the largest divisor <= 64
         for (int cw = pass ? 1 : cw_min; cw <= 64 && cw <= nchunk; ++cw) {
@@ -790,7 +790,6 @@ static unsigned dw_walk_grid(DwP& p, int segw, int groups) {
             const int act = pass ? cw : cw * (NT / cw);
             if (act > best_active || (act == best_active && cw > best)) { best = cw; best_active = act; }
         }
-    if (cw_min >= 1024 && nchunk <= NT) best = nchunk;
     p.cw = best; p.tpb = NT / best > 0 ? NT / best : 1; p.nct = nchunk / best;
     const long strips = (long)p.N * p.nrb * p.nseg;
     return (unsigned)(p.nct * ((strips + p.tpb - 1) / p.tpb));
@@ -858,7 +857,7 @@ static int dw_bwd_data_launch(const adamml_conv_desc_t* d, const void* dz, const
         }
         return adamml_check_launch("dwconv_bwd_data");
     }
-    static const bool quads = !(getenv("ADAMML_DW_S2_QUADS") && atoi(getenv("ADAMML_DW_S2_QUADS")) == 0);       // A/B aid
+    static const bool quads = !(getenv("ADAMML_DW_S2_QUADS") && atoi(getenv("ADAMML_DW_S2_QUADS")) == 0);       // test hook
     if (d->stride == 2 && d->pad == 1 && (quads || bn_z)) {
         p.P = (size_t)d->N * ((d->H + 1) / 2) * ((d->W + 1) / 2);
         int nblk = dw_blocks(p.P, p.C, &p.ppb);           // (16 / 32 / 64 passes per thread instead of 8: no gain, 4.2-4.7 TB/s incl. the z read)
@@ -896,8 +895,8 @@ static int dw_wgrad_blocks(const adamml_conv_desc_t* d, int* rows_per_thread, in
     *nseg = (d->OW + segw - 1) / segw;
     const int groups = d->groups < 1 ? 1 : d->groups;
     // equal row blocks of at most max_rows rows, split further only while the grid is short of threads (as dw_walk_grid)
-    static const long min_blocks = getenv("ADAMML_DWW_MIN_BLOCKS") ? atol(getenv("ADAMML_DWW_MIN_BLOCKS")) : 256;      // A/B aids
-    static const int max_rows = getenv("ADAMML_DWW_MAX_ROWS") ? atoi(getenv("ADAMML_DWW_MAX_ROWS")) : 24;
+    constexpr long min_blocks = 256;
+    constexpr int max_rows = 24;
     int nb_rows = ceil_div(d->OH, max_rows);
     while (ceil_div(d->OH, nb_rows) > 3 && (long)groups * d->N * nb_rows * *nseg * nchunk < min_blocks * NT) ++nb_rows;
     const int rpt = ceil_div(d->OH, nb_rows);
@@ -1028,8 +1027,7 @@ extern "C" int adamml_gemm_f32(const float* a, int64_t a_sm, int64_t a_sk, const
     if (!a || !b || !c) return adamml_set_error(ADAMML_EINVAL, "gemm_f32: null argument");
     if (M <= 0 || N <= 0) return ADAMML_OK;
     GemmP p{a, a_sm, a_sk, b, b_sn, b_sk, c, c_sm, c_sn, bias, act, accumulate, M, N, K};
-    static const int use_mfma = getenv("ADAMML_GEMM_MFMA") ? atoi(getenv("ADAMML_GEMM_MFMA")) : 1;          // A/B aid
-    if (use_mfma && a_sk == 1 && b_sk == 1 && K >= 16 && (K & 3) == 0 && (a_sm & 3) == 0 && (b_sn & 3) == 0 &&
+    if (a_sk == 1 && b_sk == 1 && K >= 16 && (K & 3) == 0 && (a_sm & 3) == 0 && (b_sn & 3) == 0 &&
         ((uintptr_t)a & 15) == 0 && ((uintptr_t)b & 15) == 0) {
         hipLaunchKernelGGL(gemm_f32_mfma_kernel, dim3(ceil_div(N, 64), ceil_div(M, 32)), dim3(NT), 0, stream, p);
         return adamml_check_launch("gemm_f32 (mfma)");

@@ -1556,11 +1556,9 @@ static int bn_act_add_launch(const void* z, const float* scale, const float* shi
     if (!P) return ADAMML_OK;
     if (groups < 1) groups = 1;
     size_t ppb, nblk;
-    static const int aa_passes = getenv("ADAMML_ACTADD_PASSES") ? atoi(getenv("ADAMML_ACTADD_PASSES")) : 0;          // A/B aid (16: the row walk)
     const int rows = NT / (C / 8) > 0 ? NT / (C / 8) : 1;
-    ppb = (size_t)rows * (aa_passes > 0 ? aa_passes : (idn && (size_t)groups * P * C * 2 > ((size_t)512 << 20) ? 4 : 8));      // one-shot workgroups (two-pass form: 8 rows)
+    ppb = (size_t)rows * (idn && (size_t)groups * P * C * 2 > ((size_t)512 << 20) ? 4 : 8);      // one-shot workgroups (two-pass form: 8 rows)
     nblk = (P + ppb - 1) / ppb;
-    if (aa_passes >= 16) rowwalk_grid(P, C, groups, 8192, &ppb, &nblk);
     if ((size_t)groups * P * C * 2 > ((size_t)256 << 20))
         hipLaunchKernelGGL(bn_act_add_kernel<true>, dim3((unsigned)nblk, groups), dim3(NT), 0, stream, (const bf16_t*)z, scale, shift, z_gstride,
                            act, (const bf16_t*)idn, id_scale, id_shift, id_gstride, (bf16_t*)out, mask_out, P, C, ppb);
@@ -1676,8 +1674,6 @@ extern "C" int adamml_bn_bwd_apply(const void* g, const void* z, const float* ve
     const int rows = NT / (C / 8) > 0 ? NT / (C / 8) : 1;
     ppb = (size_t)rows * ((size_t)groups * P * C * 2 > ((size_t)512 << 20) ? 4 : 8);
     nblk = (P + ppb - 1) / ppb;
-    static const bool walk = getenv("ADAMML_BNAPPLY_WALK") && atoi(getenv("ADAMML_BNAPPLY_WALK"));          // A/B aid: the long row walk
-    if (walk) rowwalk_grid(P, C, groups, 8192, &ppb, &nblk);
     if ((size_t)groups * P * C * 2 > ((size_t)256 << 20))
         hipLaunchKernelGGL((bn_bwd_apply_kernel<true, 4>), dim3((unsigned)nblk, groups), dim3(NT), 0, stream, (const bf16_t*)g, (const bf16_t*)z,
                            vec, act, coef, (bf16_t*)dz, P, C, ppb);
@@ -1693,8 +1689,8 @@ extern "C" int adamml_maxpool2d_fwd(const void* x, const float* scale, const flo
     const size_t n = (size_t)N * OH * OW * (C / 8);
     if (!n) return ADAMML_OK;
     if (groups < 1) groups = 1;
-    static const int walk = getenv("ADAMML_MAXPOOL_WALK") ? atoi(getenv("ADAMML_MAXPOOL_WALK")) : 8;          // output rows per thread; 0: per-output kernel (A/B aid)
-    if (walk > 0 && OH >= 2 * walk) {
+    constexpr int walk = 8;          // output rows per thread
+    if (OH >= 2 * walk) {
         const int nrb = (OH + walk - 1) / walk;
         const size_t nth = (size_t)N * nrb * OW * (C / 8);
         const dim3 grid((unsigned)((nth + NT - 1) / NT), groups);
@@ -1903,8 +1899,7 @@ extern "C" int adamml_clip_u8_to_nhwc(const uint8_t* x, void* y, int B, int S, i
     NormVec nv;
     nv.n = n_mean;
     for (int i = 0; i < 4; ++i) { nv.mean[i] = i < n_mean ? mean[i] : 0.f; nv.std[i] = i < n_mean ? std[i] : 1.f; }
-    static const int fast = getenv("ADAMML_U8_FAST") ? atoi(getenv("ADAMML_U8_FAST")) : 1;            // A/B aid: 0 = the generic kernel
-    if (fast && C == 3 && F == 8 && n_mean == 3 && S >= 1 && S <= 5 && ((uintptr_t)x & 7) == 0) {
+    if (C == 3 && F == 8 && n_mean == 3 && S >= 1 && S <= 5 && ((uintptr_t)x & 7) == 0) {
         bool ok = false;
         switch (S) {
             case 1: ok = launch_u8_rgb<1>(x, (bf16_t*)y, B, H, W, OH, OW, frame_step, c_pad, nv, div255, n, stream); break;

@@ -258,13 +258,13 @@ __global__ __launch_bounds__(NQ * 64, NQ == 4 ? 2 : 1) void res_prod_stream_kern
 
 int rps_blocks(long P, int groups, int per_cu) {
     const long ntile = (P + TPX - 1) / TPX;
-    static const long cap0 = getenv("ADAMML_RPS_CAP") ? atol(getenv("ADAMML_RPS_CAP")) : 256;                    // A/B aid: CUs
-    long cap = cap0 * per_cu / (groups < 1 ? 1 : groups);
+    constexpr long CUS = 256;
+    long cap = CUS * per_cu / (groups < 1 ? 1 : groups);
     if (cap < 1) cap = 1;
     return (int)(ntile < cap ? ntile : cap);
 }
 
-bool rps_on() { const char* e = getenv("ADAMML_RES_PROD_STREAM"); return !(e && atoi(e) == 0); }                 // A/B aid, read at every call
+bool rps_on() { const char* e = getenv("ADAMML_RES_PROD_STREAM"); return !(e && atoi(e) == 0); }                 // test hook, read at every call
 
 bool rps_1x1(const adamml_conv_desc_t* d) {
     return d && d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && d->up <= 1 && (long)d->N * d->OH * d->OW >= 4096;

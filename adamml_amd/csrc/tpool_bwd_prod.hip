@@ -256,8 +256,8 @@ int tpp_launch(const TPP& p, int groups, int nblk, hipStream_t stream) {
 int tpp_blocks(int NB, int HW, int C, int groups) {
     const long ntask = (long)NB * ((HW + 15) / 16);
     // one partial [C][Cin] per workgroup: two workgroups per CU over all groups at C = 256 (four waves each), one at C = 512
-    static const long cap0 = getenv("ADAMML_TPP_CAP") ? atol(getenv("ADAMML_TPP_CAP")) : 512;                    // A/B aid
-    long cap = (C == 256 ? cap0 : cap0 / 2) / (groups < 1 ? 1 : groups);
+    constexpr long CAP = 512;
+    long cap = (C == 256 ? CAP : CAP / 2) / (groups < 1 ? 1 : groups);
     if (cap < 1) cap = 1;
     return (int)(ntask < cap ? ntask : cap);
 }
@@ -265,9 +265,8 @@ int tpp_blocks(int NB, int HW, int C, int groups) {
 }  // namespace
 
 extern "C" int adamml_temporal_pool_bwd_code_prod_supported(int T, int C, int Cin) {
-    static const bool on = !(getenv("ADAMML_TPOOL_BWD_PROD") && atoi(getenv("ADAMML_TPOOL_BWD_PROD")) == 0);            // A/B aid
     // (the stage-2 form, T = 4 / C = 512 / Cin = 128 with eight waves and 4 x 8 accumulator tiles, does not fit the register file: not built)
-    return on && T == 8 && C == 256 && Cin == 64 ? 1 : 0;
+    return T == 8 && C == 256 && Cin == 64 ? 1 : 0;
 }
 
 extern "C" size_t adamml_temporal_pool_bwd_code_prod_workspace(int NB, int T, int HW, int C, int Cin, int groups) {

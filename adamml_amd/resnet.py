@@ -3,8 +3,6 @@ libadamml_hip (bf16 MFMA implicit-GEMM convs with fused BatchNorm statistics).
 
 Mirrors the interface and state_dict of models/resnet.py:116-259 (class ResNet, factory resnet()).
 """
-import os
-
 import torch
 import torch.nn as nn
 
@@ -33,9 +31,6 @@ class _Bottleneck(nn.Module):
         self.bn3 = nn.BatchNorm2d(planes * 4)
         self.downsample = downsample
         self.stride = stride
-
-
-STEM_PAD4 = os.environ.get("ADAMML_STEM_PAD4", "1") != "0"      # 4-channel input pixels for the 7x7 stem kernels (A/B aid)
 
 
 class ResNet(HipBackbone, MeanStdMixin, StockDDPAware):
@@ -153,7 +148,7 @@ class ResNet(HipBackbone, MeanStdMixin, StockDDPAware):
         input channels) serves the shape -- it reads 8 bytes per pixel, and 4-channel pixels halve the bytes of the re-layout store
         and of the stem's forward / weight-gradient loads -- else the generic 8-channel multiple."""
         cs = self._stem
-        if cs.stem and STEM_PAD4:
+        if cs.stem:
             from ctypes import byref
             d = cs.desc((1, h, w, 4), 0, 1, 0)
             if hip.load().adamml_conv_stem_supported(byref(d)):

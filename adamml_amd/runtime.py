@@ -8,7 +8,6 @@ never materialised except at residual adds.  BatchNorm statistics, scale/shift a
 """
 import collections
 import math
-import os
 import torch
 import torch.distributed as dist
 
@@ -305,10 +304,8 @@ def _bn_backward(rt, out, y, vec, bn, act, count, defer_apply=False):
         gy, idx, zsel, poh, pow_ = out.pool_grad
         out.pool_grad = None
         sums = rt.bwd_arena.take(G * 2 * C * STAT_SLOTS)
-        if zsel is not None:                # sums over the windows: each pooled gradient lands on exactly one input pixel
-            call("adamml_bn_bwd_reduce", ptr(gy), ptr(zsel), ptr(vec), act, ptr(sums), n // G * poh * pow_, C, G)
-        else:
-            call("adamml_maxpool2d_bwd_bn_reduce", ptr(gy), ptr(idx), ptr(y), ptr(vec), act, ptr(sums), n // G, oh, ow, C, poh, pow_, G)
+        # sums over the windows (g_y, z_sel): each pooled gradient lands on exactly one input pixel
+        call("adamml_bn_bwd_reduce", ptr(gy), ptr(zsel), ptr(vec), act, ptr(sums), n // G * poh * pow_, C, G)
         sums, nslots = rt.sync.reduce(sums, C, G)
         coef = torch.empty(G, 3, C, dtype=torch.float32, device=y.device)
         train_bn = bn.weight.requires_grad
@@ -438,7 +435,7 @@ def conv_bn(rt, x, cs, bn, act, sole_consumer=False, last_consumer=False):
     if rt.training:
         out = Lazy(y, vec[0, 0], vec[0, 1], act, gs=4 * C)
         out.vec = vec
-        out.alg = bool(ALG_BN and rt.tape.need_grad and act == ACT_NONE and not cs.depthwise and not stem and x.requires_grad
+        out.alg = bool(rt.tape.need_grad and act == ACT_NONE and not cs.depthwise and not stem and x.requires_grad
                        and cs.weight.requires_grad and _alg_supported(cs, d))
     else:
         out = Lazy(y, vec[0], vec[1], act)
@@ -449,18 +446,18 @@ def conv_bn(rt, x, cs, bn, act, sole_consumer=False, last_consumer=False):
             if out.alg and out.pool_grad is None:
                 _conv1x1_backward_alg(rt, out, x, y, vec, bn, cs, d, count, sole_consumer, macs, in_b, out_b, w_b, kern)
                 return
-            if DUAL_DGRAD and act == ACT_NONE and not cs.depthwise and not stem and out.pool_grad is None and x.requires_grad \
+            if act == ACT_NONE and not cs.depthwise and not stem and out.pool_grad is None and x.requires_grad \
                     and rt.training and hip.load().adamml_conv_bwd_data_dual_supported(byref(d)):
                 _conv1x1_backward_dual(rt, out, x, y, vec, bn, cs, d, count, sole_consumer, macs, in_b, out_b, w_b, kern_dual)
                 return
-            if DUAL_DGRAD and act != ACT_NONE and out.pre_sums is not None and not cs.depthwise and not stem and out.pool_grad is None \
+            if act != ACT_NONE and out.pre_sums is not None and not cs.depthwise and not stem and out.pool_grad is None \
                     and x.requires_grad and rt.training and cs.kh * cs.kw == 1 and nar[2]:
                 # expansion conv of an inverted residual (round 6): its gradient arrives ALREADY masked by its ReLU6 (the depthwise conv's fused
                 # backward applied the mask and accumulated the sums), so the BatchNorm-backward apply is the same affine A g' + B z + C as for
                 # a linear BatchNorm and folds into the narrow streaming data gradient's loader the same way
                 _conv1x1_backward_dual(rt, out, x, y, vec, bn, cs, d, count, sole_consumer, macs, in_b, out_b, w_b, kern_dual)
                 return
-            if cs.depthwise and DW_FUSED and out.pool_grad is None and out.pre_sums is not None and rt.training and sole_consumer \
+            if cs.depthwise and out.pool_grad is None and out.pre_sums is not None and rt.training and sole_consumer \
                     and cs.weight.requires_grad and x.requires_grad and x.grad is None and x.src is None and x.vec is not None \
                     and x.pre_sums is None and x.scale is not None and x.scale.data_ptr() == x.vec.data_ptr() \
                     and hip.load().adamml_dwconv_bwd_fused_supported(byref(d)):
@@ -498,7 +495,7 @@ def conv_bn(rt, x, cs, bn, act, sole_consumer=False, last_consumer=False):
                     acc = 0
                 hip.next_meta = (2 * macs, in_b * (1 + acc) + out_b + w_b, kern if cs.depthwise else kern_acc[0 if acc else 1], role_b)
                 tgt = x.src if x.src is not None else x
-                if cs.depthwise and DW_BNZ and sole_consumer and acc == 0 and tgt.vec is not None and tgt.pre_sums is None \
+                if cs.depthwise and sole_consumer and acc == 0 and tgt.vec is not None and tgt.pre_sums is None \
                         and hip.load().adamml_dwconv_bwd_data_bn_supported(byref(d)):
                     # the expansion's BatchNorm-backward sums come out of this data gradient (mask applied here): no reduction pass
                     sums = rt.bwd_arena.take(G * 2 * d.Cin * STAT_SLOTS)
@@ -516,7 +513,7 @@ def conv_bn(rt, x, cs, bn, act, sole_consumer=False, last_consumer=False):
                                                        + (1 if (fb and not (fb and idn.alg)) else 0)) + out_b + w_b, kern, R_FUSED)
                     fbk = fb and not fb_alg
                     ain = z.alg_in
-                    if (RES_PROD and z.alg and ain is not None and (not fb or fb_alg) and acc == 1 and rmask is not None and ain[0].data is not None
+                    if (z.alg and ain is not None and (not fb or fb_alg) and acc == 1 and rmask is not None and ain[0].data is not None
                             and hip.load().adamml_conv_bwd_data_res_prod_supported(byref(d), ain[1].Cin)):
                         # the product g'^T a of the algebraic backward of the conv that produced z (its input a = ain[0]) is accumulated
                         # from the gradient tile inside this kernel: no separate pass over g' and a
@@ -555,13 +552,10 @@ def conv_bn(rt, x, cs, bn, act, sole_consumer=False, last_consumer=False):
     return out
 
 
-STEM1_F32 = os.environ.get("ADAMML_STEM1_F32", "1") != "0"     # fp32 spectrogram straight into the MobileNetV2 stems (A/B aid)
-
-
 def stem1_supported(cs, x):
     """x: the fp32 one-channel input [B, G, H, W] as the caller supplies it (models/adamml.py:49-53: G = segments).  True when the
     3x3 / stride-2 stem described by cs can read it directly (adamml_conv_stem1_fwd)."""
-    if not STEM1_F32 or x.dtype != torch.float32 or x.dim() != 4 or cs.kh != 3 or cs.stride != 2 or cs.pad != 1 or cs.weight.shape[1] != 1:
+    if x.dtype != torch.float32 or x.dim() != 4 or cs.kh != 3 or cs.stride != 2 or cs.pad != 1 or cs.weight.shape[1] != 1:
         return False
     d = ConvDesc(x.shape[0], x.shape[2], x.shape[3], 8, (x.shape[2] - 1) // 2 + 1, (x.shape[3] - 1) // 2 + 1, cs.cout, 3, 3, 2, 1, 1, 0, 0,
                  x.shape[1], 0)
@@ -659,7 +653,7 @@ def _gram_colsum(rt, x, d):
     n, h, w_, _ = x.shape
     Gm = torch.empty(G, Cin, Cin, dtype=torch.float32, device=dev)
     sv = torch.empty(G, Cin, dtype=torch.float32, device=dev)
-    if GRAM_KERNEL and hip.load().adamml_gram_colsum_supported(Cin):
+    if hip.load().adamml_gram_colsum_supported(Cin):
         # one streaming pass (csrc/gram.hip) instead of the generic weight-gradient kernel with dz = x plus a column-sum pass
         P = n // G * h * w_
         wsg = hip.scratch(hip.load().adamml_gram_colsum_workspace(P, Cin, G), dev)
@@ -675,14 +669,7 @@ def _gram_colsum(rt, x, d):
     return Gm, sv
 
 
-TPOOL_PROD = os.environ.get("ADAMML_TPOOL_BWD_PROD", "1") != "0"   # temporal-pool backward + the product g'^T a in one pass (A/B aid)
-RES_PROD = os.environ.get("ADAMML_RES_PROD", "1") != "0"     # g'^T a accumulated inside the residual-backward data gradient (A/B aid)
-POOL_ZSEL = os.environ.get("ADAMML_POOL_ZSEL", "1") != "0"   # stem BatchNorm-backward sums over the pool windows (g_y, z_sel) (A/B aid)
-DW_FUSED = os.environ.get("ADAMML_DW_BWD_FUSED", "1") != "0"    # whole stride-1 depthwise backward in one pass (csrc/dwconv_bwd_fused.hip; A/B aid)
-DW_BNZ = os.environ.get("ADAMML_DW_BNZ", "1") != "0"         # BatchNorm-backward sums of the expansion inside the depthwise data gradient (A/B aid)
-GRAM_KERNEL = os.environ.get("ADAMML_GRAM_KERNEL", "1") != "0"     # dedicated Gram + column-sum kernel (A/B aid)
-ALG_BN = os.environ.get("ADAMML_ALG_BN", "1") != "0"     # algebraic BatchNorm backward through expanding 1x1 convs (A/B aid)
-ALG_MAX_COUT = int(os.environ.get("ADAMML_ALG_MAX_COUT", "512"))     # measured: at Cout = 1024 (layer 3) the small per-group products cost more than the saved passes (146.1 vs 144.6 ms)
+ALG_MAX_COUT = 512     # measured: at Cout = 1024 (layer 3) the small per-group products cost more than the saved passes (146.1 vs 144.6 ms)
 ALG_GEMM_CIN = 256     # from this input width on, the small per-group matrix products go through adamml_gemm_f32
 
 
@@ -761,9 +748,6 @@ def _conv1x1_backward_alg(rt, out, x, y, vec, bn, cs, d, count, sole_consumer, m
             # W G_g for all groups as one GEMM: [Cout, Cin] x [Cin, G*Cin]
             wg_pre = gemm_f32(w2d, Gm.permute(1, 0, 2).reshape(Cin, G * Cin), trans_b=False)
         call("adamml_alg_wgrad_combine", ptr(w2), ptr(aff), ptr(P), ptr(Gm), ptr(wg_pre), ptr(sv), ptr(cs.weight.grad), Cout, Cin, G)
-
-
-DUAL_DGRAD = True     # 1x1 / linear-BatchNorm layers: BatchNorm-backward apply folded into the data-gradient loader
 
 
 def _conv1x1_backward_dual(rt, out, x, y, vec, bn, cs, d, count, sole_consumer, macs, in_b, out_b, w_b, kern):
@@ -875,16 +859,12 @@ def _add_backward(rt, out, out_t, z, idn, act, idn_sole, P, C):
         _accum_grad(idn, g2)
 
 
-FUSE_ADD = os.environ.get("ADAMML_FUSE_ADD", "1") != "0"     # conv3 + BatchNorm + residual add in one kernel (A/B aid)
-FUSE_TPOOL = os.environ.get("ADAMML_FUSE_TPOOL", "1") != "0"     # ... and the temporal max-pool behind the last block of a stage (A/B aid)
-
-
 def conv_bn_add_supported(rt, x, cs, need_grad, idn=None):
     """Can `conv (1x1) -> BatchNorm -> (+ identity) -> activation` run as conv_bn_add?  Eval mode: every 1x1 / stride-1 conv (the
     BatchNorm is a known affine map).  Train mode: the statistics must come from the Gram matrix of the conv INPUT, which only
     pays for expanding convs (bottleneck conv3 of layers 1-2: same shapes as the algebraic BatchNorm backward, whose products it
     shares), and the backward must be the algebraic one (it never reads the raw conv output)."""
-    if not FUSE_ADD or cs.depthwise or cs.stem or x.shape[3] != cs.cin:
+    if cs.depthwise or cs.stem or x.shape[3] != cs.cin:
         return False
     if idn is not None and idn.act != ACT_NONE:
         return False             # the epilogue applies the identity's scale / shift only: a pending activation needs add_act's check
@@ -893,7 +873,7 @@ def conv_bn_add_supported(rt, x, cs, need_grad, idn=None):
         return False
     if not rt.training:
         return not need_grad
-    if not (ALG_BN and _alg_supported(cs, d)):
+    if not _alg_supported(cs, d):
         return False
     return (not need_grad) or (x.requires_grad and cs.weight.requires_grad)
 
@@ -901,13 +881,10 @@ def conv_bn_add_supported(rt, x, cs, need_grad, idn=None):
 def conv_bn_add_tpool_supported(rt, x, cs, idn, act, frames, mode):
     """Can conv_bn_add additionally run the temporal max-pool that is the block output's ONLY consumer in its epilogue
     (adamml_conv_fwd_bn_add_tpool)?  The identity must be a plain tensor (the last block of a stage has no downsample branch)."""
-    if not FUSE_TPOOL or mode != "max" or idn is None or idn.scale is not None or frames not in (2, 4, 8) or x.shape[0] % (rt.groups * frames):
+    if mode != "max" or idn is None or idn.scale is not None or frames not in (2, 4, 8) or x.shape[0] % (rt.groups * frames):
         return False
     d = cs.desc(x.shape, x.act, rt.groups, x.gs)
     return bool(hip.load().adamml_conv_fwd_bn_add_tpool_supported(byref(d), frames, act, 1 if x.scale is not None else 0))
-
-
-FADD_NEXT = os.environ.get("ADAMML_FADD_NEXT", "1") != "0"     # conv3 + bn3 + add + ReLU and the NEXT block's conv1 in one streaming kernel (A/B aid)
 
 
 def conv_bn_add(rt, x, cs, bn, idn, act, idn_sole=False, tpool=0, next_cs=None):
@@ -970,7 +947,7 @@ def conv_bn_add(rt, x, cs, bn, idn, act, idn_sole=False, tpool=0, next_cs=None):
         mask_t = torch.empty(G * d.N, d.OH, d.OW, C // 8, dtype=torch.uint8, device=dev) if (need_grad and act != ACT_NONE) else None
         hip.next_meta = (2 * macs, in_b + (2 if idn is not None else 1) * out_b + w_b + (out_b / 16 if mask_t is not None else 0), kern, R_FUSED)
         nxt = None
-        if (FADD_NEXT and next_cs is not None and rt.training and next_cs.kh * next_cs.kw == 1 and next_cs.stride == 1
+        if (next_cs is not None and rt.training and next_cs.kh * next_cs.kw == 1 and next_cs.stride == 1
                 and not next_cs.depthwise and next_cs.cin == C and hip.load().adamml_conv_fwd_bn_add_next_supported(byref(d), next_cs.weight.shape[0])):
             # the NEXT block's conv1 consumes the block-output tile while it is still in LDS (csrc/conv1x1_fadd_next.hip): conv_bn(out, next_cs)
             # finds its raw output and statistics here and launches nothing
@@ -1034,7 +1011,7 @@ def conv_bn_add(rt, x, cs, bn, idn, act, idn_sole=False, tpool=0, next_cs=None):
             gx = torch.empty(full_shape, dtype=torch.bfloat16, device=dev)
             sa = rt.bwd_arena.take(G * 2 * C * STAT_SLOTS)
             lib = hip.load()
-            if TPOOL_PROD and z.alg and x.requires_grad and cs.weight.requires_grad and _alg_supported(cs, d) \
+            if z.alg and x.requires_grad and cs.weight.requires_grad and _alg_supported(cs, d) \
                     and lib.adamml_temporal_pool_bwd_code_prod_supported(tpool, C, d.Cin):
                 # the expanded gradient AND the product g'^T a the algebraic backward of conv3 needs first, from one pass (the product
                 # kernel read the 4.6 GB of g' back)
@@ -1069,7 +1046,7 @@ def maxpool3x3s2(rt, x, sole_consumer=False):
     idx = torch.empty(n, oh, ow, C, dtype=torch.uint8, device=x.data.device)
     G = rt.groups
     fuse_bn = sole_consumer and rt.tape.need_grad and x.requires_grad and x.vec is not None
-    zsel = torch.empty_like(y) if fuse_bn and POOL_ZSEL else None
+    zsel = torch.empty_like(y) if fuse_bn else None
     call("adamml_maxpool2d_fwd", ptr(x.data), ptr(x.scale), ptr(x.shift), x.gs, x.act, ptr(y), ptr(idx), ptr(zsel), n // G, h, w, C, oh, ow, G)
     out = Lazy(y)
     if rt.tape.need_grad:

@@ -85,7 +85,7 @@ ADAMML_API int adamml_conv1x1_narrow_supported(const adamml_conv_desc_t* d, int 
  * models/resnet.py:94-113 at the widths of models/resnet.py:150-154): 1 when the launch of FORWARD descriptor d behind kind 0:
  * adamml_conv_fwd, 3: adamml_conv_bwd_data without accumulation, 4: adamml_conv_bwd_data accumulating runs there instead of on the
  * tile-loop implicit GEMM (other kinds: 0).  Outputs are bit-identical either way (same K order and rounding points); the forward
- * statistics differ in summation order only.  ADAMML_WIDE_STREAM=0 in the environment disables the kernels (A/B aid; read at every call). */
+ * statistics differ in summation order only.  ADAMML_WIDE_STREAM=0 in the environment disables the kernels (test hook; read at every call). */
 ADAMML_API int adamml_conv1x1_wide_supported(const adamml_conv_desc_t* d, int kind);
 /* Forward 1x1 / stride-1 conv with BatchNorm + residual add + activation in its epilogue (a bottleneck's conv3 + bn3 + add +
  * ReLU, models/resnet.py:104-112; a MobileNetV2 projection + add) -- for the cases where the BatchNorm vectors are known before

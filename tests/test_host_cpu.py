@@ -44,6 +44,32 @@ def test_library_exports_every_declared_symbol(built):
     assert lib.adamml_set_deterministic(1) == 0 and lib.adamml_set_deterministic(0) == 0 and lib.adamml_get_deterministic() == 1
 
 
+def test_environment_switch_registry_matches_the_code():
+    """DESIGN.md appendix B is the complete registry of the ADAMML_* variables the product reads: the names adamml_amd/**/*.py takes from
+    os.environ plus the names adamml_amd/csrc/* passes to getenv are exactly its operational and test-hook groups (the infrastructure
+    group holds what only bench.py, the tests and tools/ read)."""
+    import glob
+    pkg = os.path.join(ROOT, "adamml_amd")
+    read = set()
+    for f in glob.glob(os.path.join(pkg, "**", "*.py"), recursive=True):
+        for line in open(f):
+            if "os.environ" in line:
+                read |= set(re.findall(r"[\"'](ADAMML_[A-Z0-9_]+)[\"']", line))
+    for f in glob.glob(os.path.join(pkg, "csrc", "*")):
+        read |= set(re.findall(r"getenv\(\s*\"(ADAMML_[A-Z0-9_]+)\"", open(f).read()))
+    doc = open(os.path.join(ROOT, "DESIGN.md")).read()
+    groups = {}
+    for part in doc[doc.index("## Appendix B"):].split("\n### ")[1:]:
+        title, _, body = part.partition("\n")
+        rows = [ln.split("|")[1] for ln in body.splitlines() if ln.startswith("| `ADAMML_")]
+        groups[title.strip()] = {n for cell in rows for n in re.findall(r"`(ADAMML_[A-Z0-9_]+)`", cell)}
+    assert set(groups) == {"Operational", "Test hooks", "Infrastructure"}, sorted(groups)
+    assert all(groups.values())
+    assert not (groups["Operational"] & groups["Test hooks"]) and not ((groups["Operational"] | groups["Test hooks"]) & groups["Infrastructure"])
+    listed = groups["Operational"] | groups["Test hooks"]
+    assert read == listed, "read but not listed: %s; listed but not read: %s" % (sorted(read - listed), sorted(listed - read))
+
+
 def _build(c):
     from adamml_amd import adamml
     mod = c["modality"]

@@ -1,6 +1,6 @@
-"""Algebraic data gradient at the benchmark shapes (B=72 x 5 segments): layer 1 (Cout 256 -> Cin 64: streaming kernel vs the CAT instance of
-conv_gemm_kernel, run with ADAMML_ALG_STREAM=0 / 1) or, `python tools/bench_alg.py 2`, layer 2 (Cout 512 -> Cin 128: CAT instance)."""
-import os, sys, torch
+"""Algebraic data gradient at the benchmark shapes (B=72 x 5 segments): layer 1 (Cout 256 -> Cin 64: the streaming
+kernel) or, `python tools/bench_alg.py 2`, layer 2 (Cout 512 -> Cin 128: CAT instance)."""
+import sys, torch
 from ctypes import byref
 sys.path.insert(0, ".")
 from adamml_amd.hip import call, ptr, STAT_SLOTS, ConvDesc
@@ -28,4 +28,4 @@ for mode in ("bn", "acc"):
     t = s.elapsed_time(e) / 5
     X, m = g.numel() * 2 / 1e9, a.numel() * 2 / 1e9
     gb = X + 3 * m if mode == "bn" else X + 3 * m
-    print("ADAMML_ALG_STREAM=%s %s: %.3f ms  %.0f GB/s (%.1f GB)" % (os.environ.get("ADAMML_ALG_STREAM", "1"), mode, t, gb / t * 1e3, gb))
+    print("%s: %.3f ms  %.0f GB/s (%.1f GB)" % (mode, t, gb / t * 1e3, gb))

@@ -1,6 +1,5 @@
 """Last bottleneck of ResNet-50 layer 1 at the benchmark shape (5 groups x 72 clips x 8 frames of 56 x 56): conv3 + bn3 + add + ReLU + temporal
-max-pool in one kernel (adamml_conv_fwd_bn_add_tpool).  ADAMML_FADD_TPOOL_STREAM=0 selects conv_gemm_kernel's TP instance, the default
-the streaming kernel of csrc/conv1x1_fadd_next.hip (one process per form: the switch is read once).  GPU box only."""
+max-pool in one kernel (adamml_conv_fwd_bn_add_tpool), served at this shape by the streaming kernel of csrc/conv1x1_fadd_next.hip.  GPU box only."""
 import os
 import sys
 from ctypes import byref
@@ -41,4 +40,4 @@ for r in range(3):
     e1.record()
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / 10
-    print("round %d  ADAMML_FADD_TPOOL_STREAM=%s  %.3f ms   (%.2f GB: %.0f GB/s)" % (r, os.environ.get("ADAMML_FADD_TPOOL_STREAM", "1"), ms, gb, gb / ms * 1e3))
+    print("round %d  %.3f ms   (%.2f GB: %.0f GB/s)" % (r, ms, gb, gb / ms * 1e3))

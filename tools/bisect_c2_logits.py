@@ -4,7 +4,9 @@ statistics changed.)  Runs the adamml_c2 train_main forward of tests/test_parity
 command line (each in its own process: the switches are read at import / first use) and prints |HIP - fp32 golden|, |HIP - emulation| for
 the logits and the policy logits.
 
-    python tools/bisect_c2_logits.py "" ADAMML_NARROW_STREAM=0 ADAMML_FADD_NEXT=0 ADAMML_GEMM_MFMA=0 ADAMML_FADD_TPOOL_STREAM=0 ADAMML_WIDE_STREAM=0
+    python tools/bisect_c2_logits.py "" ADAMML_WIDE_STREAM=0 ADAMML_RES_PROD_STREAM=0 ADAMML_FADD_STREAM=0 ADAMML_FADD_TPOOL_SLICE=0
+
+(the test hooks of DESIGN.md appendix B; a kernel family without a hook is bisected between two builds: ADAMML_HIP_LIB)
 """
 import os
 import subprocess

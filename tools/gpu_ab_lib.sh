@@ -15,7 +15,7 @@ for which in prev new; do
   ADAMML_HIP_LIB=$PWD/$lib timeout 300 python tools/bench_dual_mb.py > $out/dual_$which.txt 2>&1
   ADAMML_HIP_LIB=$PWD/$lib timeout 300 python tools/explore_stream.py 72 1 alg 10 > $out/stream_$which.txt 2>&1
   ADAMML_HIP_LIB=$PWD/$lib timeout 300 python tools/bench_nets.py > $out/nets_$which.txt 2>&1
-  ADAMML_HIP_LIB=$PWD/$lib ADAMML_ALG_STREAM=0 timeout 300 python tools/bench_alg.py > $out/alg1_$which.txt 2>&1
+  ADAMML_HIP_LIB=$PWD/$lib timeout 300 python tools/bench_alg.py > $out/alg1_$which.txt 2>&1
   ADAMML_HIP_LIB=$PWD/$lib timeout 300 python tools/bench_alg.py 2 > $out/alg2_$which.txt 2>&1
   ADAMML_HIP_LIB=$PWD/$lib timeout 600 python tools/bench_conv.py 2>&1 | grep -v amdgpu > $out/conv_$which.txt
 done
