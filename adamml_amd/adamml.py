@@ -66,7 +66,7 @@ class AdaMML(nn.Module, MeanStdMixin, StockDDPAware):
         p_x, m_x = [], []
         f = self.num_frames_per_segment
         for idx, (x_, m) in enumerate(zip(x, self.modality)):
-            if isinstance(x_, video.Frames):
+            if isinstance(x_, (video.Frames, video.EncodedFrames)):
                 # MI355X extension: decoded videos + their sampled geometry -> the uint8 arrays `Stack` would return (crop / scale /
                 # flip of the reference's augmentor, byte-exact, on this stream: video.py); from here the uint8 branch below
                 if m == 'sound' or x_.modality != m:

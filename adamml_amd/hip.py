@@ -93,6 +93,7 @@ SIGNATURES = {
     "adamml_clip_u8_rgbdiff_to_nhwc": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P],
     "adamml_log_spectrogram": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
     "adamml_video_resample_u8": [_P, _L, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P],
+    "adamml_jpeg_decode_u8": [_P, _L, _P, _I, _P, _L, _P, _P, _L, _I, _P],
     "adamml_gemm_f32": [_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _I, _I, _I, _I, _I, _P],
     "adamml_sgd_step": [_P, _P, _P, _Z, _F, _F, _F, _I, _I, _P],
     "adamml_adam_step": [_P, _P, _P, _P, _Z, _F, _F, _F, _F, _F, _I, _P],
@@ -174,6 +175,8 @@ def load():
     lib.adamml_dwconv_bwd_fused_supported.restype = c_int
     lib.adamml_dwconv_bwd_fused_workspace.argtypes = [_DESC]
     lib.adamml_dwconv_bwd_fused_workspace.restype = c_size_t
+    lib.adamml_jpeg_decode_workspace.argtypes = [_L]
+    lib.adamml_jpeg_decode_workspace.restype = c_size_t
     lib.adamml_conv_stem_supported.argtypes = [_DESC]
     lib.adamml_conv_stem_supported.restype = c_int
     lib.adamml_plan_run.argtypes = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int]

@@ -1279,6 +1279,32 @@ def video_resample_u8(src, meta, n, oh, ow, k_in, k_out, diffs=0):
     return y
 
 
+_jpeg_ws = {}
+
+
+def jpeg_decode_u8(src, meta, n, out_bytes, total_blocks, out=None):
+    """Packed JPEG files (entropy-coded bytes + int32 descriptors, segments and tables: adamml_amd/jpeg.py Batch) -> (flat uint8
+    buffer of out_bytes bytes, int32 status [N]) on the current stream (adamml_jpeg_decode_u8), byte-exact to Pillow.  `out`: an
+    existing buffer to decode into; a fresh one is zero-filled.  The workspace is kept per device and stream and grown on demand."""
+    for t, dt, what in ((src, torch.uint8, "src"), (meta, torch.int32, "meta")) + (((out, torch.uint8, "out"),) if out is not None else ()):
+        hip.require_gpu(t)
+        if t.dtype != dt or t.dim() != 1 or not t.is_contiguous():
+            raise RuntimeError("jpeg_decode_u8: %s must be a contiguous 1-D %s tensor, got %s %s" % (what, dt, t.dtype, tuple(t.shape)))
+    if meta.device != src.device or (out is not None and out.device != src.device):
+        raise RuntimeError("jpeg_decode_u8: src on %s but meta on %s" % (src.device, meta.device))
+    if out is not None and out.numel() < out_bytes:
+        raise RuntimeError("jpeg_decode_u8: out holds %d bytes, the batch needs %d" % (out.numel(), out_bytes))
+    y = torch.zeros(max(out_bytes, 1), dtype=torch.uint8, device=src.device) if out is None else out
+    status = torch.empty(max(n, 0), dtype=torch.int32, device=src.device)
+    need = hip.load().adamml_jpeg_decode_workspace(int(total_blocks))
+    key = (src.device, hip._stream())
+    ws = _jpeg_ws.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _jpeg_ws[key] = torch.empty(max(need, 192), dtype=torch.uint8, device=src.device)
+    call("adamml_jpeg_decode_u8", ptr(src), src.numel(), ptr(meta), meta.numel(), ptr(y), y.numel(), ptr(status), ptr(ws), need, n)
+    return y, status
+
+
 def clip_u8_rgbdiff_to_nhwc(x, num_segments, frames, mean, std, out_hw=None, frame_step=1, diffs=5):
     """RGB-diff input computed on the GPU (utils/video_dataset.py:32-38,75-84): decoded RGB frames [B, H, W, S*F*(diffs+1)*3]
     uint8 -- diffs+1 consecutive frames per frame group -> [S, B*Fk, OH, OW, pad8(3*diffs)] bf16 difference channels,

@@ -9,7 +9,12 @@ Stack) on the GPU, byte-exact to the reference's PIL transforms.
 `Augmentor.sample` restates GroupMultiScaleCrop (v1), GroupRandomScale + GroupRandomCrop (v2), GroupScale + GroupCenterCrop (val)
 and GroupRandomHorizontalFlip, consuming Python's `random` and numpy's global RNG in the reference's order.  The resampling is
 Pillow's 8-bit BILINEAR: integer coefficient tables built here in float64 (`coeffs`), applied by the HIP kernel
-adamml_video_resample_u8.  AdaMML.forward takes a `Frames` for rgb, flow and rgbdiff."""
+adamml_video_resample_u8.  AdaMML.forward takes a `Frames` for rgb, flow and rgbdiff.
+
+    batch = EncodedFrames([jpeg_files_of_video_i, ...], [geo_i, ...], pin_memory=True)   # the frames' JPEG files, not decoded
+
+hands over the files instead: `augment` first decodes them on the GPU (adamml_amd/jpeg.py, byte-exact to PIL.Image.open) into each
+video's [H, W, K_in] array and then runs the same resampling kernel on full-frame descriptors."""
 import copy
 import math
 import random
@@ -17,9 +22,9 @@ import random
 import numpy as np
 import torch
 
-from . import hip, runtime
+from . import hip, jpeg, runtime
 
-__all__ = ['Augmentor', 'Frames', 'Geometry', 'augment', 'augmentor_for', 'coeffs', 'resized_size', 'check_table', 'KMAX']
+__all__ = ['Augmentor', 'EncodedFrames', 'Frames', 'Geometry', 'augment', 'augmentor_for', 'coeffs', 'resized_size', 'check_table', 'KMAX']
 
 PRECISION_BITS = 22      # Pillow's Resample.c, 8 bits per channel
 # Taps per table entry (include/adamml_hip.h): the bilinear support of a downscale by s is s on each side, so KMAX = 32 covers every
@@ -319,9 +324,125 @@ class Frames:
         return "Frames(%s, N=%d, %dx%d, K %d -> %d, %s)" % (self.modality, self.n, self.out_h, self.out_w, self.k_in, self.k_out, self.device)
 
 
+class EncodedFrames:
+    """A batch of N videos for `augment` as their JPEG files: the decoding happens on the GPU too (adamml_amd/jpeg.py), byte-exact
+    to PIL.Image.open, straight into each video's interleaved [H_i, W_i, K_in] array.
+
+    videos: per video the list of its frames' JPEG byte strings in Stack's channel order (rgb: one colour file per frame; flow: the
+    greyscale x and y files alternating; rgbdiff: the diffs + 1 consecutive colour frames of every frame group); geometries:
+    `Augmentor.sample` of each video.  Every file of a video must have the size its Geometry was sampled for.  A file the GPU
+    decoder does not handle raises jpeg.Unsupported naming the video and file: decode that batch with Pillow into a `Frames`."""
+
+    def __init__(self, videos, geometries, diffs=5, pin_memory=False):
+        videos, geometries = [list(v) for v in videos], list(geometries)
+        if len(videos) != len(geometries):
+            raise ValueError("EncodedFrames: %d videos but %d geometries" % (len(videos), len(geometries)))
+        if not videos:
+            raise ValueError("EncodedFrames: empty batch")
+        for i, g in enumerate(geometries):
+            if not isinstance(g, Geometry):
+                raise TypeError("EncodedFrames: geometry %d is a %s, expected Augmentor.sample's Geometry" % (i, type(g).__name__))
+        g0 = geometries[0]
+        self.n, self.out_h, self.out_w, self.modality = len(videos), g0.crop, g0.crop, g0.modality
+        ch = 1 if self.modality == 'flow' else 3
+        files, infos, places, self.file_of, k_in, offset = [], [], [], [], None, 0
+        meta = [np.zeros(self.n * DESC, np.int32)]
+        nmeta, tab_at = self.n * DESC, {}
+        for i, (v, g) in enumerate(zip(videos, geometries)):
+            if (g.crop, g.modality) != (g0.crop, g0.modality):
+                raise ValueError("EncodedFrames: video %d has crop %d / modality %s, video 0 %d / %s" % (i, g.crop, g.modality, g0.crop, g0.modality))
+            k_in = len(v) * ch if k_in is None else k_in
+            if not v or len(v) * ch != k_in:
+                raise ValueError("EncodedFrames: video %d has %d files, video 0 %d" % (i, len(v), k_in // ch))
+            for j, f in enumerate(v):
+                try:
+                    inf = jpeg.parse(f)
+                except jpeg.Unsupported as e:
+                    raise jpeg.Unsupported("EncodedFrames: video %d, file %d: %s" % (i, j, e)) from None
+                if (inf.height, inf.width) != (g.height, g.width):
+                    raise ValueError("EncodedFrames: video %d, file %d is %d x %d but the geometry was sampled for %d x %d"
+                                     % (i, j, inf.width, inf.height, g.width, g.height))
+                if inf.channels != ch:
+                    raise ValueError("EncodedFrames: video %d, file %d has %d components, the %s modality stacks files of %d"
+                                     % (i, j, inf.channels, self.modality, ch))
+                files.append(f)
+                infos.append(inf)
+                places.append(jpeg.Placement(offset, g.width * k_in, k_in, j * ch))
+                self.file_of.append((i, j))
+            desc = meta[0][i * DESC:(i + 1) * DESC]
+            for j, (first, taps, k) in enumerate(g.tables()):           # the tables on the full frame, as they are
+                stride = 2 + int(taps.max())
+                ent = np.zeros((first.shape[0], stride), np.int32)
+                ent[:, 0], ent[:, 1], ent[:, 2:] = first, taps, k[:, :stride - 2]
+                key = ent.tobytes()
+                if key not in tab_at:
+                    tab_at[key] = nmeta
+                    meta.append(ent.reshape(-1))
+                    nmeta += ent.size
+                desc[5 + 2 * j], desc[6 + 2 * j] = tab_at[key], stride
+            desc[0], desc[1] = split_offset(offset)
+            desc[2], desc[3], desc[4] = g.height, g.width, g.width * k_in
+            desc[9] = 1 if (g.flip and self.modality == 'flow') else 0
+            offset += _align(g.height * g.width * k_in)
+        self.k_in = k_in
+        self.diffs = int(diffs) if self.modality == 'rgbdiff' else 0
+        if self.modality == 'rgbdiff':
+            if self.diffs < 1 or k_in % (3 * (self.diffs + 1)):
+                raise ValueError("EncodedFrames: rgbdiff needs (diffs + 1) = %d RGB frames per frame group, got %d files" % (self.diffs + 1, k_in // 3))
+            self.k_out = k_in // (self.diffs + 1) * self.diffs
+        else:
+            self.k_out = k_in
+        self.batch = jpeg.Batch(files, places, offset, pin_memory=pin_memory, infos=infos)
+        self.meta = torch.from_numpy(np.concatenate(meta))
+        if pin_memory:
+            self.meta = self.meta.pin_memory()
+        self.geometries = geometries
+
+    @property
+    def device(self):
+        return self.meta.device
+
+    @property
+    def shape(self):
+        """Shape of `augment`'s output: [N, OH, OW, K_out]."""
+        return torch.Size((self.n, self.out_h, self.out_w, self.k_out))
+
+    def size(self, dim=None):
+        return self.shape if dim is None else self.shape[dim]
+
+    def to(self, device, non_blocking=False):
+        out = copy.copy(self)
+        out.batch = self.batch.to(device, non_blocking=non_blocking)
+        out.meta = self.meta.to(device, non_blocking=non_blocking)
+        return out
+
+    def pin_memory(self):
+        out = copy.copy(self)
+        out.batch, out.meta = self.batch.pin_memory(), self.meta.pin_memory()
+        return out
+
+    def decode(self):
+        """The decoded videos as one flat uint8 buffer on the GPU (video i is [H_i, W_i, K_in] at the offset of its descriptor).
+        Waits for the decode status (one small device-to-host copy) and raises if a file's stream was damaged."""
+        y, status = jpeg.decode(self.batch)
+        bad = torch.nonzero(status).flatten().tolist()
+        if bad:
+            i, j = self.file_of[bad[0]]
+            raise RuntimeError("EncodedFrames: video %d, file %d has a damaged JPEG stream (decode status %d; %d files of the batch affected)"
+                               % (i, j, int(status[bad[0]]), len(bad)))
+        return y
+
+    def __repr__(self):
+        return "EncodedFrames(%s, N=%d, %dx%d, K %d -> %d, %s)" % (self.modality, self.n, self.out_h, self.out_w, self.k_in, self.k_out,
+                                                                   self.device)
+
+
 def augment(frames):
     """[N, OH, OW, K_out] uint8 on the GPU: exactly the arrays the reference's augmentor + Stack produce for these videos and
-    geometries.  Runs on the current stream; no host synchronisation."""
+    geometries.  Runs on the current stream; a `Frames` needs no host synchronisation, an `EncodedFrames` one (its decode status)."""
+    if isinstance(frames, EncodedFrames):
+        return runtime.video_resample_u8(frames.decode(), frames.meta, frames.n, frames.out_h, frames.out_w, frames.k_in, frames.k_out,
+                                         frames.diffs)
     if not isinstance(frames, Frames):
         raise TypeError("augment: expected a video.Frames, got %s" % type(frames).__name__)
     return runtime.video_resample_u8(frames.data, frames.meta, frames.n, frames.out_h, frames.out_w, frames.k_in, frames.k_out, frames.diffs)

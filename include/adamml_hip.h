@@ -461,6 +461,40 @@ ADAMML_API int adamml_log_spectrogram(const float* wave, const float* basis, flo
 ADAMML_API int adamml_video_resample_u8(const uint8_t* src, int64_t src_bytes, const int32_t* meta, int meta_len, uint8_t* y, int N, int OH,
                              int OW, int K_in, int K_out, int diffs, hipStream_t stream);
 
+/* Baseline JPEG frames decoded on the GPU, byte-exact to libjpeg(-turbo) as Pillow uses it (utils/video_dataset.py:51-66 opens
+ * every frame with PIL.Image.open): Huffman decode, dequantise, the integer "islow" IDCT (jidctint, CONST_BITS 13, PASS1_BITS 2),
+ * "fancy" h2v2 chroma upsampling and the fixed-point YCbCr -> RGB of jdcolor.  SOF0 only (8-bit, Huffman, one scan); 1 component
+ * (greyscale) or 3 components YCbCr sampled 1x1,1x1,1x1 (4:4:4) or 2x2,1x1,1x1 (4:2:0).  adamml_amd/jpeg.py parses and packs.
+ * src: the entropy-coded bytes of every segment of every image (a scan split at its RSTn markers, markers and the trailing EOI
+ * excluded, byte stuffing FF 00 left in place) in one flat buffer of src_bytes bytes: a multiple of 16 in [16, 2^31 - 16],
+ * 16-byte aligned.  y: y_bytes bytes; an image's pixel (r, c), channel k goes to byte
+ *   offset + r * row stride + c * pixel stride + channel offset + k     (k = 0 for greyscale; R, G, B = 0, 1, 2)
+ * so the frames of a video can land interleaved as [H, W, K_in] for adamml_video_resample_u8.  Bytes no image covers are not written.
+ * status: int32 [N], written by the call: 0 = clean, else bits 1 (a segment's decoding ran past its end or into a marker), 2 (no
+ * Huffman code matches, or a DC category above 11), 4 (an AC run carried the coefficient index past 63), 8 (a descriptor word had
+ * to be clamped), 16 (a segment still held 8 or more data bits after its last MCU: the pixels are decoded, but the stream is not
+ * what its header says).  From the block in which bit 1, 2 or 4 arises, the segment's remaining blocks have all-zero coefficients (that
+ * block keeps what was stored before the cause; for bit 1 it is decoded to its end from the zero bits the reader then supplies).
+ * The DC predictor saturates at [-32768, 32767] (no valid stream comes near: 8-bit DC values are within +-2047).
+ * meta: int32 [meta_len].  meta[22 i .. 22 i + 21] describes image i:
+ *    0 H, 1 W (each clamped to [1, 65535]; H * W above 2^26 decodes as 1 x 1),  2 components (1 or 3),  3 luma sampling factor on
+ *    both axes (1 or 2; 1 for greyscale),  4 index of its segment records,  5 segment count (clamped to its MCU count),
+ *    6-8 index of the quantisation table of component 0-2 (64 words, natural order),  9-11 index of the DC Huffman table of
+ *    component 0-2,  12-14 of the AC table (80 words: BITS[16], then HUFFVAL[256] as 64 little-endian words, zero padded),
+ *    15-16 output byte offset (low, high 32 bits),  17 row stride,  18 pixel stride,  19 channel offset (bytes),
+ *    20-21 first 8 x 8 block of the image in the workspace (low, high): an image owns mw * mh * (3 | 6 | 1) consecutive blocks
+ *    (4:4:4 | 4:2:0 | greyscale), mw x mh its MCU grid (an MCU is 8 hs x 8 hs pixels).
+ * A segment record is 4 words: byte offset into src, byte length, first MCU, MCU count.  Unused component words are ignored.
+ * Every table and record index is clamped into [0, meta_len - its size], every src address into [0, src_bytes), every block into
+ * the workspace and every output address into [0, y_bytes); every loop bound is a constant or a clamped descriptor word: the
+ * kernels terminate and stay inside their buffers whatever meta and src hold.
+ * workspace: adamml_jpeg_decode_workspace(total blocks of the batch) bytes, 16-byte aligned: 192 per block (int16 coefficients
+ * + uint8 component planes); the call uses workspace_bytes / 192 blocks.
+ * Bounds: 0 <= N <= 65535, meta_len >= 22 N + 80, y_bytes >= 1, workspace_bytes >= 192, checked before the pointers; N == 0 is a no-op. */
+ADAMML_API size_t adamml_jpeg_decode_workspace(int64_t total_blocks);
+ADAMML_API int adamml_jpeg_decode_u8(const uint8_t* src, int64_t src_bytes, const int32_t* meta, int meta_len, uint8_t* y, int64_t y_bytes,
+                          int32_t* status, void* workspace, int64_t workspace_bytes, int N, hipStream_t stream);
+
 /* y[M,N] = act(x[M,K] @ w[N,K]^T + bias) in fp32 with arbitrary strides (nn.Linear / LSTMCell gates and their
  * gradients: policy_net.py:228-231,278-279,351-362; resnet.py:215; sound_mobilenet_v2.py:158) */
 ADAMML_API int adamml_gemm_f32(const float* a, int64_t a_sm, int64_t a_sk, const float* b, int64_t b_sn, int64_t b_sk, float* c,
