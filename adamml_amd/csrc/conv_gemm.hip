@@ -2396,6 +2396,10 @@ extern "C" int adamml_alg_wgrad_combine(const float* w, const float* aff, const 
     return adamml_check_launch("alg_wgrad_combine");
 }
 
+extern "C" int adamml_conv_bwd_data_alg_streams(const adamml_conv_desc_t* d) {
+    return d && d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && adamml_alg_stream_supported(d->Cout, d->Cin) ? 1 : 0;
+}
+
 extern "C" int adamml_conv_bwd_data_alg(const adamml_conv_desc_t* d, const void* g, const void* a, const float* a_scale, const float* a_shift,
                                         const void* w_alg, const float* epi_add, void* dx, int accumulate, const void* z_in,
                                         const float* bn_vec, int act, double* sums, hipStream_t stream) {

@@ -1021,14 +1021,18 @@ extern "C" int adamml_conv_stem1_bwd_weight(const adamml_conv_desc_t* d, const v
     return adamml_check_launch("conv_stem1_bwd_weight");
 }
 
+extern "C" int adamml_gemm_f32_uses_mfma(const float* a, int64_t a_sm, int64_t a_sk, const float* b, int64_t b_sn, int64_t b_sk, int K) {
+    return a_sk == 1 && b_sk == 1 && K >= 16 && (K & 3) == 0 && (a_sm & 3) == 0 && (b_sn & 3) == 0 && ((uintptr_t)a & 15) == 0 &&
+           ((uintptr_t)b & 15) == 0 ? 1 : 0;
+}
+
 extern "C" int adamml_gemm_f32(const float* a, int64_t a_sm, int64_t a_sk, const float* b, int64_t b_sn, int64_t b_sk, float* c,
                                int64_t c_sm, int64_t c_sn, const float* bias, int act, int accumulate, int M, int N, int K,
                                hipStream_t stream) {
     if (!a || !b || !c) return adamml_set_error(ADAMML_EINVAL, "gemm_f32: null argument");
     if (M <= 0 || N <= 0) return ADAMML_OK;
     GemmP p{a, a_sm, a_sk, b, b_sn, b_sk, c, c_sm, c_sn, bias, act, accumulate, M, N, K};
-    if (a_sk == 1 && b_sk == 1 && K >= 16 && (K & 3) == 0 && (a_sm & 3) == 0 && (b_sn & 3) == 0 &&
-        ((uintptr_t)a & 15) == 0 && ((uintptr_t)b & 15) == 0) {
+    if (adamml_gemm_f32_uses_mfma(a, a_sm, a_sk, b, b_sn, b_sk, K)) {
         hipLaunchKernelGGL(gemm_f32_mfma_kernel, dim3(ceil_div(N, 64), ceil_div(M, 32)), dim3(NT), 0, stream, p);
         return adamml_check_launch("gemm_f32 (mfma)");
     }

@@ -1288,9 +1288,20 @@ __global__ void clip_to_nhwc4_kernel(const float* x, bf16_t* y, int B, int S, in
 // Decoded-frame input path (utils/video_transforms.py:302-343 Stack -> ToTorchFormatTensor -> GroupNormalize, then
 // models/adamml.py:42-67): x [B][H][W][S*F*C] uint8 -- the HW(FC) array `Stack` produces, one byte per value instead of the
 // four of the normalised fp32 tensor -- to y [S][B*Fk][OH][OW][c_pad] bf16 with value ((u8 / 255) - mean[c % nm]) / std[c % nm]
-// in fp32 exactly as the reference evaluates it, bilinear (align_corners = False) when OH != H.  A thread owns one output
+// with the normalisation in fp32 exactly as the reference evaluates it, bilinear (align_corners = False) when OH != H: the four taps are
+// combined by bilerp4() below -- three explicit fmaf, the same in both uint8 kernels, not the unfused sum torch evaluates (they agree to the
+// roundings tests/abi_ref.py counts).  The source coordinate `sh * (oh + 0.5f) - 0.5f` may still be contracted per kernel; an index
+// only depends on that where the coordinate lands within an ulp of an integer.  A thread owns one output
 // pixel for every (segment, frame): it reads the 1..4 source pixels' contiguous S*F*C bytes and writes S*Fk chunks.
 struct NormVec { float mean[4], std[4]; int n; };
+// The four-tap bilinear expression of the two uint8 kernels below, with its roundings pinned: under the default -ffp-contract=fast the
+// compiler chose WHICH products of `lh0 * (lw0 * a + lw1 * b) + lh1 * (..)` to fuse per kernel, and the table-driven RGB kernel and the
+// generic kernel then differed in the last bf16 bit of a few elements (tests/test_abi_conformance_gpu.py, the clip_u8_to_nhwc[rgb-*] rows).
+__device__ __forceinline__ float bilerp4(float lh0, float lh1, float lw0, float lw1, float p00, float p01, float p10, float p11) {
+#pragma clang fp contract(off)
+    const float top = fmaf(lw1, p01, lw0 * p00), bot = fmaf(lw1, p11, lw0 * p10);
+    return fmaf(lh1, bot, lh0 * top);
+}
 // DIFF: the source holds C/3 + 1 consecutive RGB frames per frame group and the C output channels are the C/3 RGB differences
 // of neighbours, quantised exactly as utils/video_dataset.py:32-38 does (uint8((next - cur + 255) * 0.5), truncation).
 template <bool DIFF>
@@ -1338,7 +1349,7 @@ __global__ void clip_u8_to_nhwc_kernel(const uint8_t* x, bf16_t* y, int B, int S
                                 if (div255) t = t / 255.f;
                                 return (t - m) / sd;
                             };
-                            val = resize ? lh0 * (lw0 * nrm(p00) + lw1 * nrm(p01)) + lh1 * (lw0 * nrm(p10) + lw1 * nrm(p11)) : nrm(p00);
+                            val = resize ? bilerp4(lh0, lh1, lw0, lw1, nrm(p00), nrm(p01), nrm(p10), nrm(p11)) : nrm(p00);
                         }
                         v[i] = val;
                     }
@@ -1404,8 +1415,8 @@ __global__ __launch_bounds__(NT) void clip_u8_rgb_kernel(const uint8_t* x, bf16_
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
                     if (RESIZE)
-                        v[c] = lh0 * (lw0 * lut[c][byte_of(0, off + c)] + lw1 * lut[c][byte_of(1, off + c)]) +
-                               lh1 * (lw0 * lut[c][byte_of(2, off + c)] + lw1 * lut[c][byte_of(3, off + c)]);
+                        v[c] = bilerp4(lh0, lh1, lw0, lw1, lut[c][byte_of(0, off + c)], lut[c][byte_of(1, off + c)], lut[c][byte_of(2, off + c)],
+                                       lut[c][byte_of(3, off + c)]);
                     else
                         v[c] = lut[c][byte_of(0, off + c)];
                 }
@@ -1873,13 +1884,17 @@ extern "C" int adamml_colsum_f32(const float* a, float* out, int rows, int cols,
     return adamml_check_launch("colsum_f32");
 }
 
+extern "C" int adamml_clip_to_nhwc_four_pixel(const float* x, const void* y, int H, int W, int OH, int OW, int c_pad) {
+    return c_pad == 4 && OH == H && OW == W && (W & 3) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0 ? 1 : 0;
+}
+
 extern "C" int adamml_clip_to_nhwc(const float* x, void* y, int B, int S, int F, int C, int H, int W, int OH, int OW,
                                    int frame_step, int c_pad, hipStream_t stream) {
     if ((c_pad % 8 && c_pad != 4) || c_pad < C || frame_step < 1) return adamml_set_error(ADAMML_EINVAL, "clip_to_nhwc: bad c_pad/frame_step");
     const int Fk = (F + frame_step - 1) / frame_step;
     const size_t n = (size_t)S * B * Fk * OH * OW;
     if (!n) return ADAMML_OK;
-    if (c_pad == 4 && OH == H && OW == W && (W & 3) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0) {
+    if (adamml_clip_to_nhwc_four_pixel(x, y, H, W, OH, OW, c_pad)) {
         hipLaunchKernelGGL(clip_to_nhwc4_kernel, dim3(grid_for(n / 4)), dim3(NT), 0, stream, x, (bf16_t*)y, B, S, F, C, H, W, frame_step, Fk);
         return adamml_check_launch("clip_to_nhwc (4-pixel)");
     }
@@ -1961,7 +1976,9 @@ extern "C" int adamml_sgd_step(float* p, const float* g, float* mom, size_t n, f
 extern "C" int adamml_adam_step(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
                                 float weight_decay, int step, hipStream_t stream) {
     if (!n) return ADAMML_OK;
-    const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
+    // bias corrections in double: 1 - powf(beta2, step) in fp32 cancels (beta2 = 0.999, step 2: half an ulp of the power near 1 is
+    // 1.5e-5 of bc2); the kernel receives them rounded once to fp32, as before
+    const float bc1 = (float)(1.0 - pow((double)beta1, (double)step)), bc2 = (float)(1.0 - pow((double)beta2, (double)step));
     hipLaunchKernelGGL(adam_step_kernel, dim3(grid_for(n)), dim3(NT), 0, stream, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay,
                        bc1, bc2);
     return adamml_check_launch("adam_step");

@@ -147,6 +147,12 @@ def load():
     lib.adamml_conv_bwd_data_res_streams.restype = c_int
     lib.adamml_conv_fwd_bn_add_tpool_streams.argtypes = [_DESC, _I]
     lib.adamml_conv_fwd_bn_add_tpool_streams.restype = c_int
+    lib.adamml_gemm_f32_uses_mfma.argtypes = [_P, _L, _L, _P, _L, _L, _I]
+    lib.adamml_gemm_f32_uses_mfma.restype = c_int
+    lib.adamml_clip_to_nhwc_four_pixel.argtypes = [_P, _P, _I, _I, _I, _I, _I]
+    lib.adamml_clip_to_nhwc_four_pixel.restype = c_int
+    lib.adamml_conv_bwd_data_alg_streams.argtypes = [_DESC]
+    lib.adamml_conv_bwd_data_alg_streams.restype = c_int
     lib.adamml_conv_fused_input_supported.argtypes = [_DESC]
     lib.adamml_conv_fused_input_supported.restype = c_int
     lib.adamml_conv1x1_narrow_supported.argtypes = [_DESC, c_int]

@@ -181,6 +181,10 @@ ADAMML_API int adamml_alg_pack(const float* w, const float* aff, const float* m_
                     hipStream_t stream);
 ADAMML_API int adamml_alg_wgrad_combine(const float* w, const float* aff, const float* P, const float* G, const float* wg_pre, const float* s, float* dw,
                              int Cout, int Cin, int groups, hipStream_t stream);
+/* 1 when an adamml_conv_bwd_data_alg launch of FORWARD descriptor d is served by the barrier-free streaming kernel of
+ * csrc/conv1x1_stream.hip (the ResNet-50 layer-1 shape: 64 -> 256 channels) rather than the concatenated-input tile kernel -- a label for
+ * profilers and tests.  The two differ in one rounding point: the tile kernel stages the GEMM result as bf16 before epi_add is added. */
+ADAMML_API int adamml_conv_bwd_data_alg_streams(const adamml_conv_desc_t* d);
 ADAMML_API int adamml_conv_bwd_data_alg(const adamml_conv_desc_t* d, const void* g, const void* a, const float* a_scale, const float* a_shift,
                              const void* w_alg, const float* epi_add, void* dx, int accumulate, const void* z_in, const float* bn_vec,
                              int act, double* sums, hipStream_t stream);
@@ -409,6 +413,9 @@ ADAMML_API int adamml_colsum_f32(const float* a, float* out, int rows, int cols,
 
 /* AdaMML.data_layer (models/adamml.py:42-67): NCHW fp32 clip tensor [B, S*F*C, H, W] -> per-segment NHWC bf16
  * frames [S][B*Fk][OH][OW][c_pad] with optional bilinear resize (align_corners=False) and frame stride. */
+/* 1 when adamml_clip_to_nhwc with these arguments runs the four-pixels-per-thread kernel (c_pad 4, no resize, W % 4 == 0, x and y 16-byte
+ * aligned) rather than the generic one; same values -- a label for profilers and tests. */
+ADAMML_API int adamml_clip_to_nhwc_four_pixel(const float* x, const void* y, int H, int W, int OH, int OW, int c_pad);
 ADAMML_API int adamml_clip_to_nhwc(const float* x, void* y, int B, int S, int F, int C, int H, int W, int OH, int OW,
                         int frame_step, int c_pad, hipStream_t stream);
 
@@ -497,6 +504,9 @@ ADAMML_API int adamml_jpeg_decode_u8(const uint8_t* src, int64_t src_bytes, cons
 
 /* y[M,N] = act(x[M,K] @ w[N,K]^T + bias) in fp32 with arbitrary strides (nn.Linear / LSTMCell gates and their
  * gradients: policy_net.py:228-231,278-279,351-362; resnet.py:215; sound_mobilenet_v2.py:158) */
+/* 1 when adamml_gemm_f32 with these operands runs on the matrix cores (both operands K-contiguous and 16-byte aligned, row strides and
+ * K multiples of 4, K >= 16), 0 when the VALU tile kernel serves it -- a label for profilers and tests. */
+ADAMML_API int adamml_gemm_f32_uses_mfma(const float* a, int64_t a_sm, int64_t a_sk, const float* b, int64_t b_sn, int64_t b_sk, int K);
 ADAMML_API int adamml_gemm_f32(const float* a, int64_t a_sm, int64_t a_sk, const float* b, int64_t b_sn, int64_t b_sk, float* c,
                     int64_t c_sm, int64_t c_sn, const float* bias, int act, int accumulate, int M, int N, int K,
                     hipStream_t stream);

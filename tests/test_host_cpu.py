@@ -44,6 +44,64 @@ def test_library_exports_every_declared_symbol(built):
     assert lib.adamml_set_deterministic(1) == 0 and lib.adamml_set_deterministic(0) == 0 and lib.adamml_get_deterministic() == 1
 
 
+# entry points no test module has to name, with the reason (everything else declared in the header must appear in a tests/test_*.py)
+ABI_TEST_EXEMPT = {
+    "adamml_last_error_string": "query: hip.call reads it on every failing launch",
+    "adamml_conv_bwd_weight_workspace": "query: workspace size, reached through hip.wgrad_workspace in every weight-gradient row",
+    "adamml_conv_stem_bwd_weight_workspace": "query: workspace size, reached through hip.wgrad_workspace(stem=True)",
+    "adamml_dwconv_bwd_weight_workspace": "query: workspace size, reached through hip.wgrad_workspace(depthwise=True)",
+    "adamml_plan_run": "plan plumbing: driven through adamml_amd/plan.py (tests/test_launch_plan_gpu.py)",
+    "adamml_plan_events_create": "plan plumbing: driven through adamml_amd/plan.py",
+    "adamml_plan_events_destroy": "plan plumbing: driven through adamml_amd/plan.py",
+}
+
+
+def test_every_declared_entry_point_is_named_by_a_test_module():
+    """A kernel entry point the suite never calls by name is a gap: every function of include/adamml_hip.h is called in some tests/test_*.py,
+    or is in ABI_TEST_EXEMPT with its reason (size queries, the error string, plan plumbing); the exemption list holds nothing stale.
+    Dispatch probes are not exempt: a row asserts them (test_dispatch_probes_answer_as_documented for those no GPU row reads)."""
+    import glob
+    hdr = open(os.path.join(ROOT, "include", "adamml_hip.h")).read()
+    declared = set(re.findall(r"\b(adamml_[a-z0-9_]+)\s*\(", hdr))
+    text = "".join(open(f).read() for f in glob.glob(os.path.join(ROOT, "tests", "test_*.py")))
+    text = re.sub(r"ABI_TEST_EXEMPT = \{.*?\n\}\n", "", text, flags=re.S)         # (the exemption list itself names nothing)
+    # named = called: the name as a string literal (hip.call("name", ..)) or as an attribute of the loaded library (lib.name(..)); a mention
+    # in a comment or a docstring does not count
+    named = {s for s in declared if re.search(r"[\"']%s[\"']|\.%s\b" % (s, s), text)}
+    assert set(ABI_TEST_EXEMPT) <= declared, sorted(set(ABI_TEST_EXEMPT) - declared)
+    assert not (set(ABI_TEST_EXEMPT) & named), "exempt although a test names it: %s" % sorted(set(ABI_TEST_EXEMPT) & named)
+    missing = declared - named - set(ABI_TEST_EXEMPT)
+    assert not missing, "entry points no test module names: %s" % sorted(missing)
+    assert all(len(r) > 10 for r in ABI_TEST_EXEMPT.values())
+
+
+def test_dispatch_probes_answer_as_documented(built):
+    """The probes the runtime reads to label launches, on the shapes include/adamml_hip.h documents for them (host functions: no GPU)."""
+    from ctypes import byref
+    from adamml_amd import hip
+    from adamml_amd.hip import ConvDesc
+    lib = hip.load()
+
+    def desc(H, cin, cout, k=1, stride=1, pad=0):
+        return ConvDesc(8, H, H, cin, H // stride, H // stride, cout, k, k, stride, pad, 1, 1, 0, 1, 0)
+    assert [lib.adamml_gram_colsum_supported(c) for c in (64, 128, 96, 8)] == [1, 1, 0, 0]
+    l1, l2, l3 = desc(56, 64, 256), desc(28, 128, 512), desc(14, 256, 1024)
+    assert lib.adamml_conv_fwd_bn_add_supported(byref(l1)) == 1 and lib.adamml_conv_fwd_bn_add_supported(byref(l2)) == 1
+    assert lib.adamml_conv_fwd_bn_add_supported(byref(desc(56, 64, 64, 3, 1, 1))) == 0           # not 1x1
+    assert lib.adamml_conv_fwd_bn_add_supported(byref(desc(56, 64, 256, 1, 2, 0))) == 0          # not stride 1
+    for frames in (2, 4, 8):            # 0 = tile kernel, 1 = the 64 -> 256 streaming kernel, 2 = the 128 -> 512 wave-slice kernel
+        assert [lib.adamml_conv_fwd_bn_add_tpool_streams(byref(d), frames) for d in (l1, l2, l3)] == [1, 2, 0]
+    # the layer-1 shape of the product-fused residual data gradient: d->Cin == 256, d->Cout == 64, a_channels == 64
+    assert lib.adamml_conv_bwd_data_res_prod_streams(byref(desc(56, 256, 64)), 64) == 1
+    assert lib.adamml_conv_bwd_data_res_prod_streams(byref(desc(28, 512, 128)), 64) == 0
+    assert lib.adamml_conv_bwd_data_res_prod_streams(byref(desc(56, 256, 64)), 32) == 0
+    # the two probes the conformance rows assert on their operands, on the host side of their predicates
+    assert lib.adamml_gemm_f32_uses_mfma(4096, 64, 1, 8192, 64, 1, 64) == 1 and lib.adamml_gemm_f32_uses_mfma(4096, 64, 1, 8192, 64, 1, 62) == 0
+    assert lib.adamml_gemm_f32_uses_mfma(4100, 64, 1, 8192, 64, 1, 64) == 0 and lib.adamml_gemm_f32_uses_mfma(4096, 1, 64, 8192, 64, 1, 64) == 0
+    assert lib.adamml_clip_to_nhwc_four_pixel(4096, 8192, 6, 8, 6, 8, 4) == 1 and lib.adamml_clip_to_nhwc_four_pixel(4096, 8192, 6, 10, 6, 10, 4) == 0
+    assert lib.adamml_clip_to_nhwc_four_pixel(4096, 8192, 6, 8, 6, 8, 8) == 0 and lib.adamml_clip_to_nhwc_four_pixel(4096, 8192, 6, 8, 3, 4, 4) == 0
+
+
 def test_environment_switch_registry_matches_the_code():
     """DESIGN.md appendix B is the complete registry of the ADAMML_* variables the product reads: the names adamml_amd/**/*.py takes from
     os.environ plus the names adamml_amd/csrc/* passes to getenv are exactly its operational and test-hook groups (the infrastructure
