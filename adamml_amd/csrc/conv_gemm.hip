@@ -871,7 +871,7 @@ __global__ __launch_bounds__(NTHREADS, conv_gemm_wg_per_cu(BC, MODE, PD, RES, DU
                 } else {
                     const f32x8 ov = bf8_to_f32(orr[EID ? 0 : j]);
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) f[i] *= mask_act(ov[i], rlo, rhi);
+                    for (int i = 0; i < 8; ++i) f[i] = (ov[i] > rlo && ov[i] < rhi) ? f[i] : 0.f;   // (selects, as the bit form above: a masked NaN / inf is 0, not NaN * 0)
                 }
                 const bf16x8 v = f32_to_bf8(f);
                 if (ok[j]) *reinterpret_cast<bf16x8*>(p.y + pr[j]) = v;

@@ -131,7 +131,8 @@ ADAMML_API int adamml_gram_stats(const void* w_packed, const float* G, const flo
 /* G [groups][C][C] = a^T a and s [groups][C] = sum_p a over the P pixels of each group, a = act(scale x + shift) rounded to bf16
  * as the conv loaders stage it (scale == NULL: a = x), in one streaming pass over x (csrc/gram.hip) -- the inputs of
  * adamml_gram_stats and of the algebraic BatchNorm backward (models/resnet.py:103-111: bn3 statistics without storing conv3's
- * output).  C in {64, 128}; workspace of adamml_gram_colsum_workspace() bytes (per-workgroup partials, summed in a fixed order). */
+ * output).  C in {64, 128, 256} (256: each unordered pair of 16-channel blocks is computed once and mirrored, G == G^T bitwise);
+ * workspace of adamml_gram_colsum_workspace() bytes (per-workgroup partials, summed in a fixed order). */
 ADAMML_API int adamml_gram_colsum_supported(int C);
 ADAMML_API size_t adamml_gram_colsum_workspace(size_t P, int C, int groups);
 ADAMML_API int adamml_gram_colsum(const void* x, const float* scale, const float* shift, int gstride, int act, float* G, float* s, size_t P, int C,
@@ -196,6 +197,10 @@ ADAMML_API int adamml_conv_bwd_data_alg(const adamml_conv_desc_t* d, const void*
  * other operand is BatchNorm'd too (downsample branch) z_b / vec_b / sums_b receive the same for it (else all NULL).
  * res_mask (optional): the 1-bit-per-element act'(res_out) != 0 mask written by adamml_bn_act_add_mask; when given it is read
  * instead of res_out (1/16 of the bytes).
+ * act' SELECTS in both forms and in every kernel that serves this entry point: where act'(res_out) == 0, g' is +0 whatever the gradient
+ * holds (a NaN or inf under a closed mask does not propagate, as in autograd's threshold backward).  The unfused
+ * adamml_residual_bwd and the BatchNorm-fused data-gradient epilogues multiply by act' instead: equal in value for finite gradients
+ * (the zero carries the gradient's sign there), NaN where a non-finite gradient meets a closed mask.
  * Replaces adamml_conv_bwd_data(accumulate) + adamml_residual_bwd: the block-output gradient is written once. */
 ADAMML_API int adamml_conv_bwd_data_res_supported(const adamml_conv_desc_t* d);
 /* 1 when an adamml_conv_bwd_data_res launch in the algebraic backward's form (accumulate, res_mask, z_a == z_b == NULL) is served by
@@ -215,8 +220,10 @@ ADAMML_API int adamml_conv_bwd_data_res(const adamml_conv_desc_t* d, const void*
 ADAMML_API int adamml_conv_bwd_data_res_prod_supported(const adamml_conv_desc_t* d, int a_channels);
 ADAMML_API size_t adamml_conv_bwd_data_res_prod_workspace(const adamml_conv_desc_t* d);
 /* 1 when the launch is served by the barrier-free streaming kernel of csrc/res_prod_stream.hip (the layer-1 shape: d->Cin == 256,
- * d->Cout == 64, a_channels == 64; same results: dx bit-identical) rather than the tile kernel -- a label for profilers, as
- * adamml_conv1x1_narrow_supported. */
+ * d->Cout == 64, a_channels == 64, >= 4096 pixels per group -- the same pixel-count term as adamml_conv_bwd_data_res_streams; same
+ * results: dx bit-identical) rather than the tile kernel -- a label for profilers, as adamml_conv1x1_narrow_supported.  Below 4096
+ * pixels per group the layer-1 shape is served by the tile kernel, whose own term (at least 4096 workgroups: ceil(pixels / 128) *
+ * (d->Cin / 128) * groups) then decides adamml_conv_bwd_data_res_prod_supported.  ADAMML_RES_PROD_STREAM=0 disables it (read at every call). */
 ADAMML_API int adamml_conv_bwd_data_res_prod_streams(const adamml_conv_desc_t* d, int a_channels);
 ADAMML_API int adamml_conv_bwd_data_res_prod(const adamml_conv_desc_t* d, const void* dz, const void* w_dgrad_packed, void* dx, const uint8_t* res_mask,
                                   int res_act, double* sums_a, const void* a, const float* a_scale, const float* a_shift, int a_act,

@@ -75,6 +75,46 @@ def test_every_declared_entry_point_is_named_by_a_test_module():
     assert all(len(r) > 10 for r in ABI_TEST_EXEMPT.values())
 
 
+# the modules that compare kernels with a float64 (or byte-exact integer) reference under a counted error model
+CONFORMANCE_MODULES = ("test_conv_conformance_gpu.py", "test_elementwise_conformance_gpu.py", "test_abi_conformance_gpu.py",
+                       "test_fused_conformance_gpu.py", "test_spectrogram_gpu.py", "test_jpeg_gpu.py", "test_video_gpu.py")
+# size queries and dispatch probes compute nothing a float64 reference could check
+CONFORMANCE_QUERY_SUFFIXES = ("_workspace", "_supported", "_streams")
+# entry points that launch no kernel of their own, with the reason no conformance row names them (keys without the adamml_ prefix: the full
+# name as a string literal would count as a call in test_every_declared_entry_point_is_named_by_a_test_module)
+CONFORMANCE_EXEMPT = {
+    "version": "plumbing: a constant (test_library_exports_every_declared_symbol reads it)",
+    "last_error_string": "plumbing: hip.call reads it on every failing launch",
+    "set_deterministic": "plumbing: accepted and ignored, there is one reduction mode (test_library_exports_every_declared_symbol)",
+    "get_deterministic": "plumbing: always 1 (test_library_exports_every_declared_symbol)",
+    "plan_run": "plan plumbing: replays recorded launches of entry points that have their own rows (tests/test_launch_plan_gpu.py)",
+    "plan_events_create": "plan plumbing: driven through adamml_amd/plan.py",
+    "plan_events_destroy": "plan plumbing: driven through adamml_amd/plan.py",
+    "plan_num_entry_points": "plan plumbing: the length of the thunk table (test_launch_plan_thunks_are_in_sync_with_the_c_abi)",
+}
+
+
+def test_every_computing_entry_point_is_named_by_a_float64_conformance_module():
+    """Being called by some test is not being checked: every function of include/adamml_hip.h that computes something -- everything but
+    the size queries and dispatch probes (CONFORMANCE_QUERY_SUFFIXES) -- is called in one of the CONFORMANCE_MODULES, or is in
+    CONFORMANCE_EXEMPT with its reason; the exemption list holds nothing stale (undeclared, a query, or named by a conformance module)."""
+    hdr = open(os.path.join(ROOT, "include", "adamml_hip.h")).read()
+    declared = set(re.findall(r"\b(adamml_[a-z0-9_]+)\s*\(", hdr))
+    text = ""
+    for m in CONFORMANCE_MODULES:
+        path = os.path.join(ROOT, "tests", m)
+        assert os.path.exists(path), "conformance module missing: " + m
+        text += open(path).read()
+    named = {s for s in declared if re.search(r"[\"']%s[\"']|\.%s\b" % (s, s), text)}
+    queries = {s for s in declared if s.endswith(CONFORMANCE_QUERY_SUFFIXES)}
+    exempt = {"adamml_" + k for k in CONFORMANCE_EXEMPT}
+    assert exempt <= declared - queries, sorted(exempt - (declared - queries))
+    assert not (exempt & named), "exempt although a conformance module names it: %s" % sorted(exempt & named)
+    missing = declared - queries - named - exempt
+    assert not missing, "entry points no float64 conformance module names: %s" % sorted(missing)
+    assert all(len(r) > 10 for r in CONFORMANCE_EXEMPT.values())
+
+
 def test_dispatch_probes_answer_as_documented(built):
     """The probes the runtime reads to label launches, on the shapes include/adamml_hip.h documents for them (host functions: no GPU)."""
     from ctypes import byref
@@ -84,7 +124,7 @@ def test_dispatch_probes_answer_as_documented(built):
 
     def desc(H, cin, cout, k=1, stride=1, pad=0):
         return ConvDesc(8, H, H, cin, H // stride, H // stride, cout, k, k, stride, pad, 1, 1, 0, 1, 0)
-    assert [lib.adamml_gram_colsum_supported(c) for c in (64, 128, 96, 8)] == [1, 1, 0, 0]
+    assert [lib.adamml_gram_colsum_supported(c) for c in (64, 128, 256, 96, 8, 512)] == [1, 1, 1, 0, 0, 0]
     l1, l2, l3 = desc(56, 64, 256), desc(28, 128, 512), desc(14, 256, 1024)
     assert lib.adamml_conv_fwd_bn_add_supported(byref(l1)) == 1 and lib.adamml_conv_fwd_bn_add_supported(byref(l2)) == 1
     assert lib.adamml_conv_fwd_bn_add_supported(byref(desc(56, 64, 64, 3, 1, 1))) == 0           # not 1x1
@@ -95,6 +135,9 @@ def test_dispatch_probes_answer_as_documented(built):
     assert lib.adamml_conv_bwd_data_res_prod_streams(byref(desc(56, 256, 64)), 64) == 1
     assert lib.adamml_conv_bwd_data_res_prod_streams(byref(desc(28, 512, 128)), 64) == 0
     assert lib.adamml_conv_bwd_data_res_prod_streams(byref(desc(56, 256, 64)), 32) == 0
+    # ... from 4096 pixels per group on (8 x 22 x 22 = 3872, 8 x 23 x 23 = 4232), as adamml_conv_bwd_data_res_streams at the layer-2 shape
+    assert [lib.adamml_conv_bwd_data_res_prod_streams(byref(desc(h, 256, 64)), 64) for h in (22, 23)] == [0, 1]
+    assert [lib.adamml_conv_bwd_data_res_streams(byref(desc(h, 512, 128))) for h in (22, 23)] == [0, 1]
     # the two probes the conformance rows assert on their operands, on the host side of their predicates
     assert lib.adamml_gemm_f32_uses_mfma(4096, 64, 1, 8192, 64, 1, 64) == 1 and lib.adamml_gemm_f32_uses_mfma(4096, 64, 1, 8192, 64, 1, 62) == 0
     assert lib.adamml_gemm_f32_uses_mfma(4100, 64, 1, 8192, 64, 1, 64) == 0 and lib.adamml_gemm_f32_uses_mfma(4096, 1, 64, 8192, 64, 1, 64) == 0
