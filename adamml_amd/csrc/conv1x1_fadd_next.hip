@@ -16,6 +16,7 @@
 // One 8-wave workgroup per CU (W3 36 KB + W1 33 KB + 8 x 8.25 KB tiles + vectors = 144 KB of LDS), no barrier in the tile loop.
 #include <type_traits>
 #include "common.h"
+#include "conv_internal.h"
 #include "../../include/adamml_hip.h"
 
 namespace {

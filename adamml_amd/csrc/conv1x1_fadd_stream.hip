@@ -11,6 +11,7 @@
 // store per lane.  The loads of the workgroup's next tile are requested after the stores.  Same K order, rounding points and epilogue
 // expression as the tile kernel: out and mask_out are bit-identical.
 #include "common.h"
+#include "conv_internal.h"
 #include "../../include/adamml_hip.h"
 #include <type_traits>
 
@@ -375,7 +376,7 @@ bool fs_on() { const char* e = getenv("ADAMML_FADD_STREAM"); return !(e && atoi(
 
 }  // namespace
 
-// (declared in conv_gemm.hip, which owns the C entry point and falls back to its tile kernel)
+// (declared in conv_internal.h; conv_gemm.hip owns the C entry point and falls back to its tile kernel)
 int adamml_conv1x1_fadd_stream_supported(const adamml_conv_desc_t* d) {
     if (!fs_on() || !d) return 0;
     return d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && d->up <= 1 && d->Cin == 128 && d->Cout == 512 &&

@@ -15,6 +15,7 @@
 // Same K order and rounding points as conv_gemm_kernel: bit-identical outputs; the statistics differ in summation order only.
 #include <type_traits>
 #include "common.h"
+#include "conv_internal.h"
 #include "../../include/adamml_hip.h"
 
 namespace {

@@ -7,6 +7,7 @@
 // then streams its own 32-pixel tiles with a 5-deep register ring and NO workgroup barrier in the loop.  The loader -> LDS ->
 // barrier -> MFMA pipeline of conv_gemm_kernel's CAT instance ran this layer at 3.6 TB/s.
 #include "common.h"
+#include "conv_internal.h"
 #include "../../include/adamml_hip.h"
 
 

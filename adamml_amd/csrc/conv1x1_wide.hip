@@ -32,6 +32,7 @@
 #include <type_traits>
 #include <stdlib.h>
 #include "common.h"
+#include "conv_internal.h"
 #include "../../include/adamml_hip.h"
 
 namespace {

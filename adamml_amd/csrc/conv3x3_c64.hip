@@ -13,6 +13,7 @@
 // applies the activation mask and accumulates the BatchNorm-backward sums (conv_gemm.hip epilogue semantics).
 #include <type_traits>
 #include "common.h"
+#include "conv_internal.h"
 #include "../../include/adamml_hip.h"
 
 

@@ -4,13 +4,16 @@
 //     input patch is staged into LDS, and per-channel sum / sum-of-squares of the (bf16-rounded) output
 //     accumulated in the epilogue (train-mode BN statistics, SURVEY.md section 7 hard part 1);
 //   * data-gradient (same kernel on the flipped/transposed weight pack, `up` = forward stride).
-// A second kernel computes the weight gradient with LDS transpose reads (ds_read_b64_tr_b16).
+// This file: the tile kernel, conv_launch (which instance, or which streaming kernel of another file, serves a launch) and the
+// forward / data-gradient entry points.  Weight gradients: conv_wgrad.hip.  Small kernels of the algebraic BatchNorm backward:
+// conv_alg.hip.  Tile primitives: tile.h.  Launchers of the other files: conv_internal.h.
 //
 // Replaces the torch operators called at models/resnet.py:83-113,138,199-210,
 // models/sound_mobilenet_v2.py:33-69 and models/policy_net.py:38-95 (nn.Conv2d + nn.BatchNorm2d + ReLU/ReLU6).
 #include "common.h"
+#include "tile.h"
+#include "conv_internal.h"
 #include "../../include/adamml_hip.h"
-#include <type_traits>
 #include <stdlib.h>
 #include <stdio.h>
 
@@ -19,7 +22,6 @@ namespace {
 
 constexpr int BP = 128;      // pixels per block tile
 constexpr int BK = 32;       // K step (one MFMA K)
-constexpr int NTHREADS = 256;
 
 struct ConvP {
     const bf16_t* x;
@@ -102,30 +104,6 @@ __device__ __forceinline__ int lds_off(int row, int chunk) {
 // MODE 2: generic path with zero-upsampled input (data gradient of strided convs other than the stride-2 fast path);
 // MODE 3: one parity class of a stride-2 data gradient: MODE 1 addressing over the class's tap subset (input and weight
 //         tap tables), output rows scattered with stride 2 -- no MFMA or load is spent on the zeros of the up-sampling.
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (N > 0) {
-        static_for<N - 1>(f);
-        f(std::integral_constant<int, N - 1>{});
-    }
-}
-
-// LDS image of one K step: [32 pixels][CH channels] bf16, row-major, 8-byte units XOR-swizzled so that the
-// ds_read_b64_tr_b16 of a 32-lane service group (rows {r..r+3} U {r+8..r+11}) touches 64 distinct banks.
-template <int CH>
-__device__ __forceinline__ int tr_swz(int row) {
-    if (CH >= 128) return ((row & 3) | (((row >> 3) & 1) << 2)) << 2;       // 256-byte rows: all rows start at bank 0
-    return (((row >> 1) & 1) | (((row >> 3) & 1) << 1)) << 2;               // 128-byte rows: parity picks the bank half
-}
-
-__device__ const uint4 g_zero_page[4] = {};          // 64 zero bytes: source of the out-of-range chunks of an LDS-DMA tile
-
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst_uniform) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst_uniform) : "memory");
-}
-
 // PD = register prefetch depth (K steps of global loads in flight).  PD 1 keeps 3-4 workgroups per CU (latency hidden by
 // occupancy: best for the big, short-K layers); PD 3 is for small grids with long K loops (layer3/4), where a CU holds a
 // single workgroup and only explicit look-ahead hides the HBM round trip.
@@ -1123,692 +1101,7 @@ __global__ __launch_bounds__(NTHREADS, conv_gemm_wg_per_cu(BC, MODE, PD, RES, DU
     }
 }
 
-// ------------------------------------------------------------------------------------------------
-// Weight gradient:  dW[co][ci][kh][kw] += sum_p dz[p][co] * a[p@(kh,kw)][ci]   (fp32 atomics, split over pixels)
-// Both operands are pixel-major in HBM (NHWC), i.e. K-major for this GEMM, so MFMA fragments are fetched
-// from LDS with the hardware transpose read ds_read_b64_tr_b16.
-struct WgradP {
-    const bf16_t* dz;      // [N,OH,OW,Cout]
-    const bf16_t* x;       // [N,H,W,Cin]
-    const float* in_scale;
-    const float* in_shift;
-    float* dw;             // OIHW fp32, Cin_true input channels
-    float* ws;             // optional [nsplit][numel(dw)] partial buffer (plain stores) instead of atomics
-    size_t dw_numel;
-    int nsplit;
-    int N, H, W, Cin, OH, OW, Cout, KH, KW, stride, pad, act, cin_true;
-    int P, pix_per_block, n_cotiles, n_tiles, cin_shift, NK;   // NK = KH*KW*Cin: flattened (tap, ci) GEMM-N extent
-    size_t gdz, gx;        // element strides between BatchNorm groups (blockIdx.y = group)
-    int in_gstride;
-    // LZ kernels: lazy transform of the dz operand as well (Gram matrix a^T a of a lazily normalised activation)
-    const float* dz_scale;
-    const float* dz_shift;
-    int dz_act, dz_gstride;
-};
-
-
-template <int BM, int BN, int WPD = 1, bool LZ = false>
-__global__ __launch_bounds__(NTHREADS) void conv_wgrad_kernel(WgradP p) {
-    constexpr int AROW = BM * 2;            // bytes per LDS row (one pixel)
-    constexpr int BROW = BN * 2;
-    constexpr int TILE_BYTES = 32 * (AROW + BROW);
-    constexpr int MT = BM / 32, NT = BN / 32;
-    __shared__ __attribute__((aligned(16))) char smem[2 * TILE_BYTES];
-
-    // block -> (group, pixel split, tile), tile fastest, through the XCD-contiguous bijection: each XCD works through a
-    // contiguous run of this list, so the tiles of one pixel range (which all re-read the same dz / activation rows)
-    // meet in one L2, and every XCD gets an equal share however few splits there are
-    const int lb = (int)xcd_contiguous(blockIdx.x, gridDim.x);
-    const int tile = lb % p.n_tiles;
-    const int unit = lb / p.n_tiles;
-    const int split = unit % p.nsplit, grp = unit / p.nsplit;
-    p.dz += (size_t)grp * p.gdz;
-    p.x += (size_t)grp * p.gx;
-    if (p.in_scale) { p.in_scale += (size_t)grp * p.in_gstride; p.in_shift += (size_t)grp * p.in_gstride; }
-    if (LZ && p.dz_scale) { p.dz_scale += (size_t)grp * p.dz_gstride; p.dz_shift += (size_t)grp * p.dz_gstride; }
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave & 1, wn = wave >> 1;
-    const int co0 = (tile % p.n_cotiles) * BM;
-    const int n0 = (tile / p.n_cotiles) * BN;           // offset in the flattened (tap, ci) axis
-    const int ps = split * p.pix_per_block;
-    const int pe = min(p.P, ps + p.pix_per_block);
-
-    constexpr int ACH = BM / 8, BCH = BN / 8;                 // 16-byte chunks per row
-    constexpr int AL = (32 * ACH) / NTHREADS, BL = (32 * BCH) / NTHREADS;
-    // register prefetch ring: global loads run WPD K steps (of 32 pixels) ahead of the MFMAs.  One K step is ~0.1 us of
-    // matrix work but an HBM round trip is 1-2 us: with a one-step look-ahead the layer2-4 problems (3-4 workgroups per CU)
-    // sat at 250-450 TFLOP/s and ~2.4 TB/s -- neither roof.  WPD = 4 costs 40 VGPRs (5 -> 3 waves per SIMD), which loses
-    // on the HBM-bound layer-1 shapes and on grids with > 4 workgroups per CU, so the launcher picks per problem.
-    bf16x8 ra[WPD][AL], rb[WPD][BL];
-    bool rbv[WPD][BL];
-    bool rav_a[LZ ? WPD : 1][AL];
-    int b_kh[BL], b_kw[BL], b_ci[BL], b_n[BL], b_oh[BL], b_ow[BL];
-    bool b_ok[BL];
-#pragma unroll
-    for (int l = 0; l < BL; ++l) {
-        int e = tid + l * NTHREADS;
-        int row = e / BCH, ch = e - row * BCH;
-        int n = n0 + ch * 8;
-        b_ok[l] = n < p.NK;
-        int tap = n >> p.cin_shift;
-        b_ci[l] = n - (tap << p.cin_shift);
-        b_kh[l] = tap / p.KW - p.pad;
-        b_kw[l] = tap - (tap / p.KW) * p.KW - p.pad;
-        int pp = ps + row;                                   // pixel of this chunk at K step 0; advanced by 32 per step
-        b_n[l] = pp / (p.OH * p.OW);
-        int rem = pp - b_n[l] * (p.OH * p.OW);
-        b_oh[l] = rem / p.OW;
-        b_ow[l] = rem - b_oh[l] * p.OW;
-    }
-
-    auto issue_loads = [&](auto slot_c, int pbase) {
-        constexpr int SL = decltype(slot_c)::value;
-#pragma unroll
-        for (int l = 0; l < AL; ++l) {
-            int e = tid + l * NTHREADS;
-            int row = e / ACH, ch = e - row * ACH;
-            int pp = pbase + row, co = co0 + ch * 8;
-            bf16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-            if (pp < pe && co < p.Cout) v = *reinterpret_cast<const bf16x8*>(p.dz + (size_t)pp * p.Cout + co);
-            ra[SL][l] = v;
-            if (LZ) rav_a[LZ ? SL : 0][l] = pp < pe && co < p.Cout;
-        }
-#pragma unroll
-        for (int l = 0; l < BL; ++l) {
-            int e = tid + l * NTHREADS;
-            int row = e / BCH;
-            bf16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-            int ih = b_oh[l] * p.stride + b_kh[l], iw = b_ow[l] * p.stride + b_kw[l];
-            bool ok = (pbase + row < pe) && b_ok[l] && ih >= 0 && iw >= 0 && ih < p.H && iw < p.W;
-            if (ok) v = *reinterpret_cast<const bf16x8*>(p.x + ((size_t)(b_n[l] * p.H + ih) * p.W + iw) * p.Cin + b_ci[l]);
-            rbv[SL][l] = ok;
-            rb[SL][l] = v;
-            // advance this chunk's pixel by one K step (32 output pixels)
-            b_ow[l] += 32;
-            while (b_ow[l] >= p.OW) { b_ow[l] -= p.OW; ++b_oh[l]; }
-            while (b_oh[l] >= p.OH) { b_oh[l] -= p.OH; ++b_n[l]; }
-        }
-    };
-    auto store_tile = [&](auto slot_c, int buf) {
-        constexpr int SL = decltype(slot_c)::value;
-        char* base = smem + buf * TILE_BYTES;
-#pragma unroll
-        for (int l = 0; l < AL; ++l) {
-            int e = tid + l * NTHREADS;
-            int row = e / ACH, ch = e - row * ACH;
-            bf16x8 va = ra[SL][l];
-            if (LZ && p.dz_scale && rav_a[LZ ? SL : 0][l]) va = f32_to_bf8(transform8(va, p.dz_scale, p.dz_shift, co0 + ch * 8, p.dz_act));
-            *reinterpret_cast<bf16x8*>(base + row * AROW + ((ch ^ (tr_swz<BM>(row) >> 1)) << 4)) = va;
-        }
-#pragma unroll
-        for (int l = 0; l < BL; ++l) {
-            int e = tid + l * NTHREADS;
-            int row = e / BCH, ch = e - row * BCH;
-            bf16x8 v = rb[SL][l];
-            if (p.in_scale && rbv[SL][l]) v = f32_to_bf8(transform8(v, p.in_scale, p.in_shift, b_ci[l], p.act));
-            *reinterpret_cast<bf16x8*>(base + 32 * AROW + row * BROW + ((ch ^ (tr_swz<BN>(row) >> 1)) << 4)) = v;
-        }
-    };
-
-    f32x4 acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int jn = 0; jn < NT; ++jn) acc[i][jn] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    const int nk = pe > ps ? (pe - ps + 31) / 32 : 0;
-    const int li = lane & 15, lg = lane >> 4;
-    // transpose-read addressing: lane li of a 16-lane group supplies the 8-byte unit
-    // [pixel row 8*lg + (li>>2) (+4)][channels 4*(li&3) ..+3]; it receives channel li of rows 0..3.
-    const int trow = 8 * lg + (li >> 2), tq = li & 3;
-    const int a_lo = trow * AROW, a_hi = (trow + 4) * AROW, b_lo = trow * BROW, b_hi = (trow + 4) * BROW;
-    const int ax_lo = tr_swz<BM>(trow), ax_hi = tr_swz<BM>(trow + 4), bx_lo = tr_swz<BN>(trow), bx_hi = tr_swz<BN>(trow + 4);
-    auto compute = [&](int buf) {
-        const char* base = smem + buf * TILE_BYTES;
-        bf16x8 fa[MT], fb[NT];
-#pragma unroll
-        for (int t = 0; t < MT; ++t) {
-            const int u = (wm * (BM / 2) + t * 16) / 4 + tq;
-            s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + a_lo + ((u ^ ax_lo) << 3)));
-            s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + a_hi + ((u ^ ax_hi) << 3)));
-            union { struct { s16x4 a, b; } s; bf16x8 v; } cvt;
-            cvt.s.a = lo; cvt.s.b = hi;
-            fa[t] = cvt.v;
-        }
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            const int u = (wn * (BN / 2) + t * 16) / 4 + tq;
-            s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + 32 * AROW + b_lo + ((u ^ bx_lo) << 3)));
-            s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + 32 * AROW + b_hi + ((u ^ bx_hi) << 3)));
-            union { struct { s16x4 a, b; } s; bf16x8 v; } cvt;
-            cvt.s.a = lo; cvt.s.b = hi;
-            fb[t] = cvt.v;
-        }
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-                acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[mt], fb[nt], acc[mt][nt], 0, 0, 0);
-    };
-    static_for<WPD>([&](auto sc) {
-        if ((int)decltype(sc)::value < nk) issue_loads(sc, ps + (int)decltype(sc)::value * 32);
-    });
-    for (int kt0 = 0; kt0 < nk; kt0 += WPD) {
-        static_for<WPD>([&](auto sc) {
-            const int kt = kt0 + (int)decltype(sc)::value;
-            if (kt < nk) {                               // uniform
-                store_tile(sc, kt & 1);                  // waits (counted vmcnt) only for this slot's loads
-                if (kt + WPD < nk) issue_loads(sc, ps + (kt + WPD) * 32);
-                __syncthreads();                         // tile kt visible; everyone is past compute(kt-1)
-                compute(kt & 1);
-            }
-        });
-    }
-    const int taps = p.KH * p.KW;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const int nn = n0 + wn * (BN / 2) + nt * 16 + li;
-            const int tap = nn >> p.cin_shift;
-            const int ci = nn - (tap << p.cin_shift);
-            if (nn >= p.NK || ci >= p.cin_true) continue;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int co = co0 + wm * (BM / 2) + mt * 16 + lg * 4 + r;
-                if (co >= p.Cout) continue;
-                // workspace partials are tap-major [co][tap][ci] (lanes = consecutive ci -> 64 B runs instead of 4 B
-                // stores 36 B apart); the split reduction permutes to OIHW
-                if (p.ws) p.ws[((size_t)grp * p.nsplit + split) * p.dw_numel + ((size_t)co * taps + tap) * p.cin_true + ci] = acc[mt][nt][r];
-                else atomicAdd(p.dw + ((size_t)co * p.cin_true + ci) * taps + tap, acc[mt][nt][r]);
-            }
-        }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Weight gradient with LDS-DMA staging (global_load_lds_dwordx4) for operands that are PLAIN in memory (no lazy transform):
-// the same tiles, LDS image and MFMA schedule as conv_wgrad_kernel, but the operand tiles go global -> LDS directly --
-// no VGPR ring, no ds_write pass -- through a ring of ST LDS stages with counted vmcnt across raw barriers, so that ST-2
-// K steps of loads stay in flight while one is being multiplied.  (Ablation of the register-staged kernel, layer-2 3x3: 418
-// TFLOP/s as is, 481 without its LDS stores, 717 without its global loads, 956 without both, 447 without its MFMAs: it is
-// bound by its staging, not by the matrix cores.)  The LDS destination of an LDS-DMA is wave-uniform base + lane * 16, so the
-// image is lane-linear and the bank swizzle of the transposed reads is applied to the SOURCE chunk index instead (an
-// involution within a pixel row: the same cache lines are fetched).  Out-of-range chunks (padding taps, tails) read a zero page.
-// LZB (1x1 convs): a lazily normalised x operand is staged RAW and its BatchNorm + activation transform is applied to the B fragment
-// after the transpose read.  That fragment holds 8 pixels of ONE channel per lane, so the transform needs one scale / shift pair per
-// lane and fragment (registers, loaded once) and ~28 VALU instructions beside 4-8 MFMAs -- unlike the forward kernels' fragments
-// (8 channels of one pixel per lane).  Rows past the pixel range hold zeros in the dz operand, so whatever act(shift) the transform
-// makes of the x operand's zero rows is multiplied by 0; K x K convs keep the staging-side transform (their padding taps must BE zero).
-template <int BM, int BN, int ST, bool LZB = false>
-__global__ __launch_bounds__(NTHREADS) void conv_wgrad_glds_kernel(WgradP p) {
-    const bf16_t* zeros = reinterpret_cast<const bf16_t*>(g_zero_page);
-    constexpr int AROW = BM * 2, BROW = BN * 2;
-    constexpr int TILE_BYTES = 32 * (AROW + BROW);
-    constexpr int MT = BM / 32, NT = BN / 32;
-    __shared__ __attribute__((aligned(1024))) char smem[ST * TILE_BYTES];
-    const int lb = (int)xcd_contiguous(blockIdx.x, gridDim.x);
-    const int tile = lb % p.n_tiles;
-    const int unit = lb / p.n_tiles;
-    const int split = unit % p.nsplit, grp = unit / p.nsplit;
-    p.dz += (size_t)grp * p.gdz;
-    p.x += (size_t)grp * p.gx;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave & 1, wn = wave >> 1;
-    const int co0 = (tile % p.n_cotiles) * BM;
-    const int n0 = (tile / p.n_cotiles) * BN;
-    const int ps = split * p.pix_per_block;
-    const int pe = min(p.P, ps + p.pix_per_block);
-    constexpr int ACH = BM / 8, BCH = BN / 8;
-    constexpr int AL = (32 * ACH) / NTHREADS, BL = (32 * BCH) / NTHREADS;
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
-
-    // staging slots of this thread: LDS chunk e = l * 256 + tid of a tile region, i.e. row e / CH at position e % CH, which holds
-    // SOURCE chunk position ^ swizzle(row)
-    int a_row[AL], a_co[AL];
-    bool a_cok[AL];
-#pragma unroll
-    for (int l = 0; l < AL; ++l) {
-        const int e = tid + l * NTHREADS;
-        a_row[l] = e / ACH;
-        const int ch = (e - a_row[l] * ACH) ^ (tr_swz<BM>(a_row[l]) >> 1);
-        a_co[l] = co0 + ch * 8;
-        a_cok[l] = a_co[l] < p.Cout;
-    }
-    int b_row[BL], b_kh[BL], b_kw[BL], b_ci[BL], b_n[BL], b_oh[BL], b_ow[BL];
-    bool b_ok[BL];
-#pragma unroll
-    for (int l = 0; l < BL; ++l) {
-        const int e = tid + l * NTHREADS;
-        b_row[l] = e / BCH;
-        const int ch = (e - b_row[l] * BCH) ^ (tr_swz<BN>(b_row[l]) >> 1);
-        const int n = n0 + ch * 8;
-        b_ok[l] = n < p.NK;
-        const int tap = n >> p.cin_shift;
-        b_ci[l] = n - (tap << p.cin_shift);
-        b_kh[l] = tap / p.KW - p.pad;
-        b_kw[l] = tap - (tap / p.KW) * p.KW - p.pad;
-        const int pp = ps + b_row[l];
-        b_n[l] = pp / (p.OH * p.OW);
-        const int rem = pp - b_n[l] * (p.OH * p.OW);
-        b_oh[l] = rem / p.OW;
-        b_ow[l] = rem - b_oh[l] * p.OW;
-    }
-    auto stage = [&](int pbase, int st) {                       // 4 LDS-DMAs per thread (128 x 128 tile)
-        const unsigned sbase = lds0 + st * TILE_BYTES + wave * 1024;
-#pragma unroll
-        for (int l = 0; l < AL; ++l) {
-            const int pp = pbase + a_row[l];
-            const bf16_t* src = (pp < pe && a_cok[l]) ? p.dz + (size_t)pp * p.Cout + a_co[l] : zeros;
-            glds16(src, __builtin_amdgcn_readfirstlane(sbase + l * NTHREADS * 16));
-        }
-#pragma unroll
-        for (int l = 0; l < BL; ++l) {
-            const int ih = b_oh[l] * p.stride + b_kh[l], iw = b_ow[l] * p.stride + b_kw[l];
-            const bool ok = (pbase + b_row[l] < pe) && b_ok[l] && ih >= 0 && iw >= 0 && ih < p.H && iw < p.W;
-            const bf16_t* src = ok ? p.x + ((size_t)(b_n[l] * p.H + ih) * p.W + iw) * p.Cin + b_ci[l] : zeros;
-            glds16(src, __builtin_amdgcn_readfirstlane(sbase + 32 * AROW + l * NTHREADS * 16));
-            b_ow[l] += 32;
-            while (b_ow[l] >= p.OW) { b_ow[l] -= p.OW; ++b_oh[l]; }
-            while (b_oh[l] >= p.OH) { b_oh[l] -= p.OH; ++b_n[l]; }
-        }
-    };
-
-    f32x4 acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int jn = 0; jn < NT; ++jn) acc[i][jn] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int nk = pe > ps ? (pe - ps + 31) / 32 : 0;
-    const int li = lane & 15, lg = lane >> 4;
-    const int trow = 8 * lg + (li >> 2), tq = li & 3;
-    const int a_lo = trow * AROW, a_hi = (trow + 4) * AROW, b_lo = trow * BROW, b_hi = (trow + 4) * BROW;
-    const int ax_lo = tr_swz<BM>(trow), ax_hi = tr_swz<BM>(trow + 4), bx_lo = tr_swz<BN>(trow), bx_hi = tr_swz<BN>(trow + 4);
-    float bsc[LZB ? NT : 1], bsh[LZB ? NT : 1];
-    if constexpr (LZB) {
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            const int nn = min(n0 + wn * (BN / 2) + t * 16 + li, p.NK - 1);        // (1x1: the flattened index IS the input channel)
-            bsc[t] = p.in_scale[(size_t)grp * p.in_gstride + nn];
-            bsh[t] = p.in_shift[(size_t)grp * p.in_gstride + nn];
-        }
-    }
-    const float blo = act_lo(p.act), bhi = act_hi(p.act);
-    auto compute = [&](int st) {
-        const char* base = smem + st * TILE_BYTES;
-        bf16x8 fa[MT], fb[NT];
-#pragma unroll
-        for (int t = 0; t < MT; ++t) {
-            const int u = (wm * (BM / 2) + t * 16) / 4 + tq;
-            s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + a_lo + ((u ^ ax_lo) << 3)));
-            s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + a_hi + ((u ^ ax_hi) << 3)));
-            union { struct { s16x4 a, b; } s; bf16x8 v; } cvt;
-            cvt.s.a = lo; cvt.s.b = hi;
-            fa[t] = cvt.v;
-        }
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            const int u = (wn * (BN / 2) + t * 16) / 4 + tq;
-            s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + 32 * AROW + b_lo + ((u ^ bx_lo) << 3)));
-            s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + 32 * AROW + b_hi + ((u ^ bx_hi) << 3)));
-            union { struct { s16x4 a, b; } s; bf16x8 v; } cvt;
-            cvt.s.a = lo; cvt.s.b = hi;
-            fb[t] = cvt.v;
-            if constexpr (LZB) {
-                f32x8 f = bf8_to_f32(fb[t]);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) f[i] = clamp_act(fmaf(f[i], bsc[t], bsh[t]), blo, bhi);
-                fb[t] = f32_to_bf8(f);
-            }
-        }
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-                acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[mt], fb[nt], acc[mt][nt], 0, 0, 0);
-    };
-    // ring of ST stages: steps kt+1 .. kt+ST-2 stay in flight (vmcnt counts this thread's LDS-DMAs, AL + BL per step) while step kt
-    // is multiplied; ONE raw barrier per step orders "step kt landed for every wave" and "everyone is done reading stage (kt-1) % ST"
-    constexpr int PER = AL + BL;
-#pragma unroll
-    for (int s0 = 0; s0 < ST - 1; ++s0)
-        if (s0 < nk) stage(ps + s0 * 32, s0);
-    int st = 0;
-    for (int kt = 0; kt < nk; ++kt) {
-        if (kt + ST - 2 <= nk - 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((ST - 2) * PER) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        if (kt + ST - 1 < nk) stage(ps + (kt + ST - 1) * 32, st == 0 ? ST - 1 : st - 1);
-        compute(st);
-        st = st + 1 == ST ? 0 : st + 1;
-    }
-    const int taps = p.KH * p.KW;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const int nn = n0 + wn * (BN / 2) + nt * 16 + li;
-            const int tap = nn >> p.cin_shift;
-            const int ci = nn - (tap << p.cin_shift);
-            if (nn >= p.NK || ci >= p.cin_true) continue;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int co = co0 + wm * (BM / 2) + mt * 16 + lg * 4 + r;
-                if (co >= p.Cout) continue;
-                p.ws[((size_t)grp * p.nsplit + split) * p.dw_numel + ((size_t)co * taps + tap) * p.cin_true + ci] = acc[mt][nt][r];
-            }
-        }
-}
-
-// ------------------------------------------------------------------------------------------------
-// 3x3 weight gradient, all nine taps per workgroup.  One K step = up to 32 output pixels of one image (a row
-// segment, or floor(32/OW) whole rows); the matching input patch (with its 1-pixel halo) is staged ONCE in LDS and
-// the nine shifted B operands are fetched from it with per-lane transpose reads, so dz and the activations are
-// read once per (co-tile, ci-tile) instead of once per tap.  Tile: 64 co x (9 taps x 64 ci); wave w owns the 16-ci
-// slice w for all taps and all 64 co (36 accumulator tiles = 144 VGPRs).
-struct W3P {
-    const bf16_t* dz;
-    const bf16_t* x;
-    const float* in_scale;
-    const float* in_shift;
-    float* dw;
-    float* ws;
-    size_t dw_numel;
-    int nsplit;
-    int N, H, W, Cin, OH, OW, Cout, pad, act, cin_true;
-    int cw, rows, PR, PC, units_per_img, units_per_row, total_units, units_per_block, n_cotiles, n_tiles;
-    size_t gdz, gx;
-    int in_gstride;
-};
-
-template <int S, int MAXSLOT>
-__global__ __launch_bounds__(NTHREADS, 2) void conv3x3_wgrad_kernel(W3P p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lb = (int)xcd_contiguous(blockIdx.x, gridDim.x);   // (group, split, tile) list, tile fastest (see conv_wgrad_kernel)
-    const int tile = lb % p.n_tiles;
-    const int split = (lb / p.n_tiles) % p.nsplit, grp = (lb / p.n_tiles) / p.nsplit;
-    p.dz += (size_t)grp * p.gdz;
-    p.x += (size_t)grp * p.gx;
-    if (p.in_scale) { p.in_scale += (size_t)grp * p.in_gstride; p.in_shift += (size_t)grp * p.in_gstride; }
-    const int patch_bytes = p.PR * p.PC * 128;
-    const int buf_bytes = 32 * 128 + patch_bytes;               // dz tile [32][64] + patch [PR*PC][64]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int li = lane & 15, lg = lane >> 4;
-    const int co0 = (tile % p.n_cotiles) * 64;
-    const int ci0 = (tile / p.n_cotiles) * 64;
-    const int u0 = split * p.units_per_block;
-    const int u1 = min(p.total_units, u0 + p.units_per_block);
-
-    // ---- fixed per-thread staging slots ---------------------------------------------------------------------
-    // dz tile: 32 rows x 8 chunks = 256 chunks -> one per thread
-    const int a_j = tid >> 3, a_ch = tid & 7;
-    const int a_r = a_j / p.cw, a_c = a_j - a_r * p.cw;
-    // patch: PR*PC pixels x 8 chunks, up to MAXSLOT slots per thread
-    const int n_chunks = p.PR * p.PC * 8;
-    int s_pr[MAXSLOT], s_pc[MAXSLOT];
-#pragma unroll
-    for (int l = 0; l < MAXSLOT; ++l) {
-        const int e = tid + l * NTHREADS;
-        const int pix = e >> 3;
-        s_pr[l] = pix / p.PC;
-        s_pc[l] = pix - s_pr[l] * p.PC;
-    }
-    const int b_ch = tid & 7;                                   // chunk within the 64-ci row (same for all slots)
-    bf16x8 ra, rb[MAXSLOT];
-    bool rbv[MAXSLOT];
-
-    auto decode = [&](int u, int& n, int& oh0, int& ow0) {
-        n = u / p.units_per_img;
-        int rem = u - n * p.units_per_img;
-        int ug = rem / p.units_per_row;                         // row group
-        int seg = rem - ug * p.units_per_row;
-        oh0 = ug * p.rows;
-        ow0 = seg * p.cw;
-    };
-    auto issue_loads = [&](int u) {
-        int n, oh0, ow0;
-        decode(u, n, oh0, ow0);
-        {
-            const int oh = oh0 + a_r, ow = ow0 + a_c;
-            bf16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-            if (a_r < p.rows && oh < p.OH && ow < p.OW)
-                v = *reinterpret_cast<const bf16x8*>(p.dz + ((size_t)(n * p.OH + oh) * p.OW + ow) * p.Cout + co0 + a_ch * 8);
-            ra = v;
-        }
-        const int ih0 = oh0 * S - p.pad, iw0 = ow0 * S - p.pad;
-#pragma unroll
-        for (int l = 0; l < MAXSLOT; ++l) {
-            bf16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-            const int ih = ih0 + s_pr[l], iw = iw0 + s_pc[l];
-            const bool ok = (tid + l * NTHREADS) < n_chunks && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
-            if (ok) v = *reinterpret_cast<const bf16x8*>(p.x + ((size_t)(n * p.H + ih) * p.W + iw) * p.Cin + ci0 + b_ch * 8);
-            rbv[l] = ok;
-            rb[l] = v;
-        }
-    };
-    auto store_tile = [&](int buf) {
-        char* base = smem + buf * buf_bytes;
-        *reinterpret_cast<bf16x8*>(base + a_j * 128 + ((a_ch ^ (tr_swz<64>(a_j) >> 1)) << 4)) = ra;
-        char* pb = base + 32 * 128;
-#pragma unroll
-        for (int l = 0; l < MAXSLOT; ++l) {
-            if (tid + l * NTHREADS < n_chunks) {
-                bf16x8 v = rb[l];
-                if (p.in_scale && rbv[l]) v = f32_to_bf8(transform8(v, p.in_scale, p.in_shift, ci0 + b_ch * 8, p.act));
-                const int pix = s_pr[l] * p.PC + s_pc[l];
-                // 16-byte chunk swizzle by patch column: neighbouring columns that share a bank half get distinct slots
-                *reinterpret_cast<bf16x8*>(pb + pix * 128 + ((b_ch ^ (((s_pc[l] >> 1) & 3) << 1)) << 4)) = v;
-            }
-        }
-    };
-
-    f32x4 acc[4][9];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int t = 0; t < 9; ++t) acc[i][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    // ---- fixed per-lane fragment addressing -----------------------------------------------------------------
-    const int trow = 8 * lg + (li >> 2), tq = li & 3;
-    const int a_lo = trow * 128, a_hi = (trow + 4) * 128;
-    const int ax_lo = tr_swz<64>(trow), ax_hi = tr_swz<64>(trow + 4);
-    int b_base[2], b_col[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int j = trow + 4 * h;
-        int r = j / p.cw, c = j - r * p.cw;
-        if (r >= p.rows) { r = 0; c = 0; }                       // padding k-rows (dz row is zero): read any FINITE patch pixel
-        b_col[h] = c * S;                                        // patch column of tap (.,0) for k-row j
-        b_base[h] = r * S * p.PC + c * S;                        // patch pixel index of tap (0,0)
-    }
-    const int b_unit = wave * 4 + tq;                            // 8-byte unit of this lane's 4 ci inside the 64-ci row
-
-    if (u0 < u1) {
-        issue_loads(u0);
-        store_tile(0);
-    }
-    __syncthreads();
-    for (int u = u0; u < u1; ++u) {
-        const int buf = (u - u0) & 1;
-        if (u + 1 < u1) issue_loads(u + 1);
-        const char* base = smem + buf * buf_bytes;
-        const char* pb = base + 32 * 128;
-        bf16x8 fa[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int un = t * 4 + tq;
-            s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + a_lo + ((un ^ ax_lo) << 3)));
-            s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + a_hi + ((un ^ ax_hi) << 3)));
-            union { struct { s16x4 a, b; } s; bf16x8 v; } cvt;
-            cvt.s.a = lo; cvt.s.b = hi;
-            fa[t] = cvt.v;
-        }
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-                s16x4 half[2];
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const int pix = b_base[h] + kh * p.PC + kw;
-                    const int un = b_unit ^ ((((b_col[h] + kw) >> 1) & 3) << 2);
-                    half[h] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(pb + pix * 128 + (un << 3)));
-                }
-                union { struct { s16x4 a, b; } s; bf16x8 v; } cvt;
-                cvt.s.a = half[0]; cvt.s.b = half[1];
-                const bf16x8 fb = cvt.v;
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt)
-                    acc[mt][kh * 3 + kw] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[mt], fb, acc[mt][kh * 3 + kw], 0, 0, 0);
-            }
-        if (u + 1 < u1) store_tile(buf ^ 1);
-        __syncthreads();
-    }
-    const int ci = ci0 + wave * 16 + li;
-    if (ci < p.cin_true) {
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int t = 0; t < 9; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int co = co0 + mt * 16 + lg * 4 + r;
-                    if (p.ws) p.ws[((size_t)grp * p.nsplit + split) * p.dw_numel + ((size_t)co * 9 + t) * p.cin_true + ci] = acc[mt][t][r];
-                    else atomicAdd(p.dw + ((size_t)co * p.cin_true + ci) * 9 + t, acc[mt][t][r]);
-                }
-    }
-}
-
-// dw[perm(i)] += sum_s ws[s][i]: 16 indices x 16 split lanes per workgroup (the split loop is the long axis).
-// taps > 1: ws is tap-major [co][tap][cin], dw is OIHW [co][cin][tap].
-// blockIdx.y = output group (per-group products of the algebraic BatchNorm backward: ws [group][split][n] -> dw [group][n], stored)
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* ws, float* dw, size_t n, int nsplit, int taps, int cin, int store) {
-    ws += (size_t)blockIdx.y * nsplit * n;
-    dw += (size_t)blockIdx.y * n;
-    __shared__ float red[16][17];
-    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    const size_t i = (size_t)blockIdx.x * 16 + tx;
-    float a = 0.f;
-    if (i < n) {
-        // four independent partial sums (fixed order): with one accumulator every load waits for the previous add -- hundreds of
-        // dependent round trips when a small problem was split over ~2000 workgroups
-        float a1 = 0.f, a2 = 0.f, a3 = 0.f;
-        int s = ty;
-        for (; s + 48 < nsplit; s += 64) {
-            a += ws[(size_t)s * n + i];
-            a1 += ws[(size_t)(s + 16) * n + i];
-            a2 += ws[(size_t)(s + 32) * n + i];
-            a3 += ws[(size_t)(s + 48) * n + i];
-        }
-        for (; s < nsplit; s += 16) a += ws[(size_t)s * n + i];
-        a = (a + a1) + (a2 + a3);
-    }
-    red[ty][tx] = a;
-    __syncthreads();
-    if (ty == 0 && i < n) {
-        float t = 0.f;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) t += red[k][tx];
-        size_t o = i;
-        if (taps > 1) {
-            const size_t per_co = (size_t)taps * cin;
-            const size_t co = i / per_co;
-            const int rem = (int)(i - co * per_co), tap = rem / cin, ci = rem - tap * cin;
-            o = (co * cin + ci) * taps + tap;
-        }
-        if (store) dw[o] = t; else dw[o] += t;
-    }
-}
-
-// The same reduction, four consecutive indices per thread (n % 4 == 0): 16-byte loads, 256 contiguous bytes per split row of a workgroup
-// instead of 64 -- the one-index form moved 1 TB/s and was, at 104 launches x 17 us, the largest of the step's small kernels
-// (1.8 ms per step; 2.2 of 34 ms of kernel time at the per-GPU share of the reference recipe).  Same fixed summation order per index.
-__global__ __launch_bounds__(256) void wgrad_reduce4_kernel(const float* ws, float* dw, size_t n, int nsplit, int taps, int cin, int store) {
-    ws += (size_t)blockIdx.y * nsplit * n;
-    dw += (size_t)blockIdx.y * n;
-    __shared__ f32x4 red[16][17];
-    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    const size_t i = ((size_t)blockIdx.x * 16 + tx) * 4;
-    f32x4 a = {0.f, 0.f, 0.f, 0.f};
-    if (i < n) {
-        f32x4 a1 = a, a2 = a, a3 = a;
-        int s = ty;
-        for (; s + 48 < nsplit; s += 64) {
-            a += *reinterpret_cast<const f32x4*>(ws + (size_t)s * n + i);
-            a1 += *reinterpret_cast<const f32x4*>(ws + (size_t)(s + 16) * n + i);
-            a2 += *reinterpret_cast<const f32x4*>(ws + (size_t)(s + 32) * n + i);
-            a3 += *reinterpret_cast<const f32x4*>(ws + (size_t)(s + 48) * n + i);
-        }
-        for (; s < nsplit; s += 16) a += *reinterpret_cast<const f32x4*>(ws + (size_t)s * n + i);
-        a = (a + a1) + (a2 + a3);
-    }
-    red[ty][tx] = a;
-    __syncthreads();
-    if (ty == 0 && i < n) {
-        f32x4 t = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < 16; ++k) t += red[k][tx];
-        if (taps > 1) {
-            const size_t per_co = (size_t)taps * cin;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const size_t ii = i + q;
-                const size_t co = ii / per_co;
-                const int rem = (int)(ii - co * per_co), tap = rem / cin, ci = rem - tap * cin;
-                const size_t o = (co * cin + ci) * taps + tap;
-                if (store) dw[o] = t[q]; else dw[o] += t[q];
-            }
-        } else if ((reinterpret_cast<uintptr_t>(dw + i) & 15) == 0) {
-            f32x4* o = reinterpret_cast<f32x4*>(dw + i);
-            if (store) *o = t; else *o += t;
-        } else {                                  // (gradient views of the flat buffer are only 4-byte aligned behind an odd-sized parameter)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { if (store) dw[i + q] = t[q]; else dw[i + q] += t[q]; }
-        }
-    }
-}
-
-// picks the 16-byte form whenever the index count allows it
-void launch_wgrad_reduce(const float* ws, float* dw, size_t n, int nsplit, int taps, int cin, int store, int groups, hipStream_t stream) {
-    if (n % 4 == 0 && (reinterpret_cast<uintptr_t>(ws) & 15) == 0)
-        hipLaunchKernelGGL(wgrad_reduce4_kernel, dim3((unsigned)((n / 4 + 15) / 16), groups), dim3(256), 0, stream, ws, dw, n, nsplit, taps, cin, store);
-    else
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n + 15) / 16), groups), dim3(256), 0, stream, ws, dw, n, nsplit, taps, cin, store);
-}
-
-int ilog2_exact(int v) {
-    int s = 0;
-    while ((1 << s) < v) ++s;
-    return (1 << s) == v ? s : -1;
-}
-
 }  // namespace
-
-bool adamml_conv3x3_c64_supported(const adamml_conv_desc_t* d);
-bool adamml_conv1x1_narrow_fwd_supported(const adamml_conv_desc_t* d);
-bool adamml_conv1x1_narrow_wgrad_supported(const adamml_conv_desc_t* d, int cin_true);
-bool adamml_conv1x1_narrow_dual_supported(const adamml_conv_desc_t* d);
-bool adamml_conv1x1_narrow_dgrad_epi_supported(const adamml_conv_desc_t* d);
-int adamml_conv1x1_narrow_dgrad_epi_launch(const adamml_conv_desc_t* d, const void* dz, const void* w_packed, void* dx, const void* z_in,
-                                           const float* bn_vec, int act, double* sums, hipStream_t stream);
-int adamml_conv1x1_narrow_dual_launch(const adamml_conv_desc_t* d, const void* g, const void* z, const float* aff, void* dz_side,
-                                      const void* w_dgrad_packed, void* dx, int accumulate, const void* z_in, const float* bn_vec, int act,
-                                      double* sums, hipStream_t stream);
-int adamml_conv1x1_narrow_wgrad_launch(const adamml_conv_desc_t* d, const void* dz, const void* x, const float* in_scale, const float* in_shift,
-                                       float* ws, int max_blocks_per_group, int* nblk_out, hipStream_t stream);
-int adamml_conv1x1_narrow_fwd_launch(const adamml_conv_desc_t* d, const void* x, const void* w_packed, const float* in_scale, const float* in_shift,
-                                     void* y, double* stats, hipStream_t stream);
-int adamml_conv3x3_c64_launch(const adamml_conv_desc_t* d, const void* x, const void* w_packed, const float* in_scale,
-                              const float* in_shift, void* y, double* stats, const void* bn_z, const float* bn_vec, int bn_act,
-                              hipStream_t stream);
-// wide 1x1 convs of ResNet layers 3-4 (conv1x1_wide.hip)
-bool adamml_conv1x1_wide_expand_supported(const adamml_conv_desc_t* d);
-int adamml_conv1x1_wide_expand_launch(const adamml_conv_desc_t* d, const void* x, const void* w_packed, const float* in_scale, const float* in_shift,
-                                      void* y, double* stats, hipStream_t stream);
-
-bool adamml_conv3x3_c64_wgrad_supported(const adamml_conv_desc_t* d, int cin_true);
-int adamml_conv3x3_c64_wgrad_blocks(const adamml_conv_desc_t* d, int* tpb_out);
-int adamml_conv3x3_c64_wgrad_launch(const adamml_conv_desc_t* d, const void* dz, const void* x, const float* in_scale,
-                                    const float* in_shift, float* ws, hipStream_t stream);
 
 // one parity class (ph, pw) of the data gradient of a stride-2 conv (see conv_dgrad_stride2)
 struct DgradClass { int nt; unsigned code; int ph, pw, OHc, OWc; };
@@ -1818,11 +1111,69 @@ struct ResEpi { const void* res_out; const uint8_t* res_mask; int res_act; const
 struct DualIn { const void* z; const float* aff; void* side; };
 // K-concatenated second input, per-group weights, epilogue constant (ConvP::xb ..)
 struct CatIn { const void* xb; int C2; size_t gw; const float* epi_add; };
-// forward BatchNorm + residual-add epilogue (ConvP::id_scale ..)
 // product with a second tensor accumulated from the gradient tile (ConvP::pf_a ..); ws: partial workspace, nsplit: out
 struct PfIn { const void* a; const float* scale; const float* shift; int act, gs, C; float* out; void* ws; size_t ws_bytes; };
+// forward BatchNorm + residual-add epilogue (ConvP::id_scale ..)
 struct FaddEpi { const float* vec; const void* idn; const float* id_scale; const float* id_shift; int id_gstride; int act; uint8_t* mask_out;
                  int tp_frames; void* tp_y; uint16_t* tp_code; };      // tp_frames > 0: temporal max-pool in the epilogue (ConvP::tp_y ..)
+
+// ---- the instances of conv_gemm_kernel, one launcher per family.  The kernel's positional template list
+//   <BC, MODE, PD, RES, DUAL, CAT, FADD, GLDS, EID, LZF, EPI, PF, TP>
+// is written out HERE and nowhere else; a launcher's own parameters are the ones that vary inside its family, under the kernel's names.
+struct ConvGrid { dim3 grid; hipStream_t stream; };
+
+template <int BC, int MODE, bool GLDS, int EPI>         // plain conv, one K step of look-ahead, the epilogue compiled in
+static void launch_plain(const ConvGrid& g, const ConvP& p) {
+    hipLaunchKernelGGL((conv_gemm_kernel<BC, MODE, 1, false, false, false, false, GLDS, 0, false, EPI>), g.grid, dim3(NTHREADS), 0, g.stream, p);
+}
+template <int BC, int MODE, int PD>                     // plain conv, epilogue selected at run time: deep prefetch (PD 3) and the MODE 2 loaders
+static void launch_rt_epi(const ConvGrid& g, const ConvP& p) {
+    hipLaunchKernelGGL((conv_gemm_kernel<BC, MODE, PD>), g.grid, dim3(NTHREADS), 0, g.stream, p);
+}
+template <int BC, bool GLDS, int EID, bool LZF>         // FADD: conv + BatchNorm + residual add + activation
+static void launch_fadd(const ConvGrid& g, const ConvP& p) {
+    hipLaunchKernelGGL((conv_gemm_kernel<BC, 0, 1, false, false, false, true, GLDS, EID, LZF>), g.grid, dim3(NTHREADS), 0, g.stream, p);
+}
+template <bool LZF, int TP>                             // FADD with the temporal max-pool of TP frames in the epilogue
+static void launch_fadd_tp(const ConvGrid& g, const ConvP& p) {
+    hipLaunchKernelGGL((conv_gemm_kernel<128, 0, 1, false, false, false, true, true, 1, LZF, -1, false, TP>), g.grid, dim3(NTHREADS), 0, g.stream, p);
+}
+template <int BC, int EID>                              // RES: residual form of the BatchNorm-fused data-gradient epilogue
+static void launch_res(const ConvGrid& g, const ConvP& p) {
+    hipLaunchKernelGGL((conv_gemm_kernel<BC, 0, 1, true, false, false, false, true, EID>), g.grid, dim3(NTHREADS), 0, g.stream, p);
+}
+static void launch_res_prod(const ConvGrid& g, const ConvP& p) {      // RES + EID with the product of the gradient tile (PF)
+    hipLaunchKernelGGL((conv_gemm_kernel<128, 0, 1, true, false, false, false, true, 1, false, -1, true>), g.grid, dim3(NTHREADS), 0, g.stream, p);
+}
+template <int BC>                                       // CAT: K-concatenated second input (algebraic BatchNorm backward)
+static void launch_cat(const ConvGrid& g, const ConvP& p) {
+    hipLaunchKernelGGL((conv_gemm_kernel<BC, 0, 3, false, false, true>), g.grid, dim3(NTHREADS), 0, g.stream, p);
+}
+template <int BC>                                       // DUAL: BatchNorm-backward affine of two tensors in the loader
+static void launch_dual(const ConvGrid& g, const ConvP& p) {
+    constexpr int PD = BC == 64 ? 3 : 2;                // (a third ring slot of g, z and weights does not fit 256 registers at 128-wide tiles)
+    hipLaunchKernelGGL((conv_gemm_kernel<BC, 0, PD, false, true>), g.grid, dim3(NTHREADS), 0, g.stream, p);
+}
+
+// ---- run-time value -> template argument, each choice written once: f receives the value as a std::integral_constant
+template <int V> using int_c = std::integral_constant<int, V>;
+template <class F> static void with_bc(int BC, F f) { if (BC == 64) f(int_c<64>{}); else f(int_c<128>{}); }
+template <class F> static void with_epi(int epi, F f) { if (epi == 0) f(int_c<0>{}); else if (epi == 1) f(int_c<1>{}); else f(int_c<2>{}); }
+template <class F> static void with_tp(int tp, F f) { if (tp == 8) f(int_c<8>{}); else if (tp == 4) f(int_c<4>{}); else f(int_c<2>{}); }
+template <class F> static void with_flag(bool b, F f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+
+// the plain instances of one (BC, MODE): LDS-DMA staging or the register-staged loader with the epilogue compiled in, deep prefetch (MODE
+// 0 / 1) or the strided loader (MODE 2) with the run-time epilogue
+template <int BC, int MODE>
+static void launch_conv(bool glds, bool deep, int epi, const ConvGrid& g, const ConvP& p) {
+    if constexpr (MODE == 2) {
+        if (deep) launch_rt_epi<BC, 2, 3>(g, p); else launch_rt_epi<BC, 2, 1>(g, p);
+    } else {
+        if constexpr (MODE != 3)
+            if (!glds && deep) return launch_rt_epi<BC, MODE, 3>(g, p);
+        with_flag(glds, [&](auto gl) { with_epi(epi, [&](auto e) { launch_plain<BC, MODE, gl(), e()>(g, p); }); });
+    }
+}
 
 static int conv_launch(const adamml_conv_desc_t* d, const void* x, const void* w_packed, const float* in_scale,
                        const float* in_shift, void* y, double* stats, const void* bn_z, const float* bn_vec, int bn_act,
@@ -1916,7 +1267,8 @@ static int conv_launch(const adamml_conv_desc_t* d, const void* x, const void* w
         p.tpb = (int)ceil_div(p.n_ptiles, (int)nsp);
         if (p.tpb < 1) p.tpb = 1;
     }
-    dim3 grid(ceil_div(p.n_ptiles, p.tpb) * p.n_ctiles, groups), block(NTHREADS);
+    const dim3 grid(ceil_div(p.n_ptiles, p.tpb) * p.n_ctiles, groups);
+    const ConvGrid cg{grid, stream};
     const int taps = d->KH * d->KW;
     // MODE 0 needs the whole row base in 32-bit element offsets (true for every layer of the hot path)
     if ((long)d->N * d->H * d->W * d->Cin >= (1L << 31)) return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_fwd: input tensor exceeds 2^31 elements");
@@ -1934,32 +1286,17 @@ static int conv_launch(const adamml_conv_desc_t* d, const void* x, const void* w
             // requested at the start of each tile (EID)
             const bool eid = p.res_out != nullptr;
             if (tp) {
-#define LAUNCH_TP(TV)                                                                                                                                        \
-                do {                                                                                                                                         \
-                    if (in_scale) hipLaunchKernelGGL((conv_gemm_kernel<128, 0, 1, false, false, false, true, true, 1, true, -1, false, TV>), grid, block, 0, stream, p);  \
-                    else hipLaunchKernelGGL((conv_gemm_kernel<128, 0, 1, false, false, false, true, true, 1, false, -1, false, TV>), grid, block, 0, stream, p);         \
-                } while (0)
-                if (tp == 8) LAUNCH_TP(8); else if (tp == 4) LAUNCH_TP(4); else LAUNCH_TP(2);
-#undef LAUNCH_TP
+                with_flag(in_scale != nullptr, [&](auto lzf) { with_tp(tp, [&](auto tv) { launch_fadd_tp<lzf(), tv()>(cg, p); }); });
                 return adamml_check_launch("conv_fwd_bn_add_tpool");
             }
-#define LAUNCH_FADD(BCV)                                                                                                                   \
-            do {                                                                                                                           \
-                if (in_scale) {                                                                                                            \
-                    if (eid) hipLaunchKernelGGL((conv_gemm_kernel<BCV, 0, 1, false, false, false, true, true, 1, true>), grid, block, 0, stream, p);  \
-                    else hipLaunchKernelGGL((conv_gemm_kernel<BCV, 0, 1, false, false, false, true, true, 0, true>), grid, block, 0, stream, p);      \
-                } else {                                                                                                                   \
-                    if (eid) hipLaunchKernelGGL((conv_gemm_kernel<BCV, 0, 1, false, false, false, true, true, 1, false>), grid, block, 0, stream, p); \
-                    else hipLaunchKernelGGL((conv_gemm_kernel<BCV, 0, 1, false, false, false, true, true, 0, false>), grid, block, 0, stream, p);     \
-                }                                                                                                                          \
-            } while (0)
-            if (BC == 64) LAUNCH_FADD(64); else LAUNCH_FADD(128);
-#undef LAUNCH_FADD
+            with_bc(BC, [&](auto bc) {
+                with_flag(in_scale != nullptr, [&](auto lzf) {
+                    if (eid) launch_fadd<bc(), true, 1, lzf()>(cg, p); else launch_fadd<bc(), true, 0, lzf()>(cg, p);
+                });
+            });
         } else
         if (tp) return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_fwd_bn_add_tpool: needs the LDS-DMA kernel (K <= 512 for a lazy input)");
-        else
-        if (BC == 64) hipLaunchKernelGGL((conv_gemm_kernel<64, 0, 1, false, false, false, true>), grid, block, 0, stream, p);
-        else hipLaunchKernelGGL((conv_gemm_kernel<128, 0, 1, false, false, false, true>), grid, block, 0, stream, p);
+        else with_bc(BC, [&](auto bc) { launch_fadd<bc(), false, 0, false>(cg, p); });
         return adamml_check_launch("conv_fwd_bn_add");
     }
     if (res) {
@@ -1973,7 +1310,7 @@ static int conv_launch(const adamml_conv_desc_t* d, const void* x, const void* w
             if (!pf->ws || pf->ws_bytes < need) return adamml_set_error(ADAMML_EINVAL, "conv_bwd_data_res_prod: workspace too small (need %zu bytes)", need);
             p.pf_a = (const bf16_t*)pf->a; p.pf_scale = pf->scale; p.pf_shift = pf->scale ? pf->shift : nullptr; p.pf_act = pf->act; p.pf_gs = pf->gs;
             p.pf_ws = (float*)pf->ws;
-            hipLaunchKernelGGL((conv_gemm_kernel<128, 0, 1, true, false, false, false, true, 1, false, -1, true>), grid, block, 0, stream, p);
+            launch_res_prod(cg, p);
             int rc = adamml_check_launch("conv_bwd_data_res_prod");
             if (rc) return rc;
             // P[g][ctile * 128 + r][c] = sum over the workgroups of (g, ctile), in workgroup order
@@ -1981,26 +1318,19 @@ static int conv_launch(const adamml_conv_desc_t* d, const void* x, const void* w
             return adamml_check_launch("conv_bwd_data_res_prod (reduce)");
         }
         if (in_scale) return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_data_res: the gradient operand is never lazy");
-        if (p.res_mask && p.accumulate && !p.bn_z && !p.bn_z2) {
-            // the algebraic backward's form (identity gradient + 1-bit mask, sum(g') only): identity-side loads at the start of each tile
-            if (BC == 64) hipLaunchKernelGGL((conv_gemm_kernel<64, 0, 1, true, false, false, false, true, 1>), grid, block, 0, stream, p);
-            else hipLaunchKernelGGL((conv_gemm_kernel<128, 0, 1, true, false, false, false, true, 1>), grid, block, 0, stream, p);
-        } else {
-            if (BC == 64) hipLaunchKernelGGL((conv_gemm_kernel<64, 0, 1, true, false, false, false, true>), grid, block, 0, stream, p);
-            else hipLaunchKernelGGL((conv_gemm_kernel<128, 0, 1, true, false, false, false, true>), grid, block, 0, stream, p);
-        }
+        // the algebraic backward's form (identity gradient + 1-bit mask, sum(g') only): identity-side loads at the start of each tile (EID)
+        const bool eid = p.res_mask && p.accumulate && !p.bn_z && !p.bn_z2;
+        with_bc(BC, [&](auto bc) { if (eid) launch_res<bc(), 1>(cg, p); else launch_res<bc(), 0>(cg, p); });
         return adamml_check_launch("conv_bwd_data_res");
     }
     if (cat) {
         if (mode != 0) return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_data_alg: only 1x1 / stride-1 convs");
-        if (BC == 64) hipLaunchKernelGGL((conv_gemm_kernel<64, 0, 3, false, false, true>), grid, block, 0, stream, p);
-        else hipLaunchKernelGGL((conv_gemm_kernel<128, 0, 3, false, false, true>), grid, block, 0, stream, p);
+        with_bc(BC, [&](auto bc) { launch_cat<bc()>(cg, p); });
         return adamml_check_launch("conv_bwd_data_alg");
     }
     if (dual) {
         if (mode != 0 || res) return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_data_dual: only 1x1 / stride-1 convs");
-        if (BC == 64) hipLaunchKernelGGL((conv_gemm_kernel<64, 0, 3, false, true>), grid, block, 0, stream, p);
-        else hipLaunchKernelGGL((conv_gemm_kernel<128, 0, 2, false, true>), grid, block, 0, stream, p);       // (a third ring slot of g, z and weights does not fit 256 registers at 128-wide tiles)
+        with_bc(BC, [&](auto bc) { launch_dual<bc()>(cg, p); });
         return adamml_check_launch("conv_bwd_data_dual");
     }
     // (the fragment-side lazy transform, LZF, is NOT used for the plain forward convs: measured 5-10 % slower than the register-staged
@@ -2009,32 +1339,26 @@ static int conv_launch(const adamml_conv_desc_t* d, const void* x, const void* w
     const bool glds = !in_scale && mode != 2;
     // the epilogue is a template parameter (EPI) of the LDS-DMA and one-step instances; deep-prefetch and MODE 2 keep the run-time form
     const int epi = bn_z ? 1 : (p.accumulate ? 2 : 0);
-#define LAUNCH_EPI(BCV, MODEV, GL)                                                                                                          \
-    do {                                                                                                                                    \
-        if (epi == 0) hipLaunchKernelGGL((conv_gemm_kernel<BCV, MODEV, 1, false, false, false, false, GL, 0, false, 0>), grid, block, 0, stream, p);       \
-        else if (epi == 1) hipLaunchKernelGGL((conv_gemm_kernel<BCV, MODEV, 1, false, false, false, false, GL, 0, false, 1>), grid, block, 0, stream, p);  \
-        else hipLaunchKernelGGL((conv_gemm_kernel<BCV, MODEV, 1, false, false, false, false, GL, 0, false, 2>), grid, block, 0, stream, p);               \
-    } while (0)
-#define LAUNCH_CONV(BCV, MODEV)                                                                             \
-    do {                                                                                                    \
-        if (glds) LAUNCH_EPI(BCV, MODEV, true);                                                             \
-        else if (deep) hipLaunchKernelGGL((conv_gemm_kernel<BCV, MODEV, 3>), grid, block, 0, stream, p);     \
-        else LAUNCH_EPI(BCV, MODEV, false);                                                                 \
-    } while (0)
-    if (BC == 64) {
-        if (mode == 0) LAUNCH_CONV(64, 0); else if (mode == 1) LAUNCH_CONV(64, 1);
-        else if (mode == 2) { if (deep) hipLaunchKernelGGL((conv_gemm_kernel<64, 2, 3>), grid, block, 0, stream, p); else hipLaunchKernelGGL((conv_gemm_kernel<64, 2, 1>), grid, block, 0, stream, p); }
-        else if (glds) LAUNCH_EPI(64, 3, true);
-        else LAUNCH_EPI(64, 3, false);
-    } else {
-        if (mode == 0) LAUNCH_CONV(128, 0); else if (mode == 1) LAUNCH_CONV(128, 1);
-        else if (mode == 2) { if (deep) hipLaunchKernelGGL((conv_gemm_kernel<128, 2, 3>), grid, block, 0, stream, p); else hipLaunchKernelGGL((conv_gemm_kernel<128, 2, 1>), grid, block, 0, stream, p); }
-        else if (glds) LAUNCH_EPI(128, 3, true);
-        else LAUNCH_EPI(128, 3, false);
-    }
-#undef LAUNCH_CONV
-#undef LAUNCH_EPI
+    with_bc(BC, [&](auto bc) {
+        if (mode == 0) launch_conv<bc(), 0>(glds, deep, epi, cg, p);
+        else if (mode == 1) launch_conv<bc(), 1>(glds, deep, epi, cg, p);
+        else if (mode == 2) launch_conv<bc(), 2>(glds, deep, epi, cg, p);
+        else launch_conv<bc(), 3>(glds, deep, epi, cg, p);
+    });
     return adamml_check_launch("conv_fwd");
+}
+
+// The descriptor conv_launch dispatches on for the data gradient of the forward conv d: a stride-1 conv of dz (pixels and channels of d's
+// output) into dx (those of d's input) with the flipped / transposed weight pack.  `upsampled`: dz is read zero-upsampled by d's stride and
+// padded for the flipped taps (the generic form of any conv); otherwise dense -- 1x1 / stride-1 convs and the parity classes of
+// conv_dgrad_stride2.  The gradient operand is never lazily normalised (act / in_gstride are cleared).
+static adamml_conv_desc_t dgrad_desc(const adamml_conv_desc_t* d, int accumulate, bool upsampled = false) {
+    adamml_conv_desc_t g = *d;
+    g.H = d->OH; g.W = d->OW; g.Cin = d->Cout;
+    g.OH = d->H; g.OW = d->W; g.Cout = d->Cin;
+    g.stride = 1; g.up = upsampled ? d->stride : 1; g.pad = upsampled ? d->KH - 1 - d->pad : 0;
+    g.act = ACT_NONE; g.accumulate = accumulate != 0; g.in_gstride = 0;
+    return g;
 }
 
 extern "C" int adamml_conv1x1_narrow_supported(const adamml_conv_desc_t* d, int kind) {
@@ -2042,8 +1366,8 @@ extern "C" int adamml_conv1x1_narrow_supported(const adamml_conv_desc_t* d, int 
     if (kind == 0) return adamml_conv1x1_narrow_fwd_supported(d) ? 1 : 0;
     if (kind == 1) return adamml_conv1x1_narrow_wgrad_supported(d, d->Cin) ? 1 : 0;
     if (kind == 2) return adamml_conv1x1_narrow_dual_supported(d) ? 1 : 0;
-    adamml_conv_desc_t g = *d;                                   // the data-gradient-shaped descriptor conv_launch dispatches on
-    g.H = d->OH; g.W = d->OW; g.Cin = d->Cout; g.OH = d->H; g.OW = d->W; g.Cout = d->Cin; g.accumulate = 0;
+    if (d->stride != 1 || d->pad != 0 || d->up > 1) return 0;    // (the streaming kernels take dense 1x1 launches only)
+    const adamml_conv_desc_t g = dgrad_desc(d, 0);
     if (kind == 3) return adamml_conv1x1_narrow_fwd_supported(&g) ? 1 : 0;
     if (kind == 4) return adamml_conv1x1_narrow_dgrad_epi_supported(&g) ? 1 : 0;
     return 0;
@@ -2054,8 +1378,7 @@ extern "C" int adamml_conv1x1_wide_supported(const adamml_conv_desc_t* d, int ki
     if (kind == 0) { adamml_conv_desc_t f = *d; f.accumulate = 0; return adamml_conv1x1_wide_expand_supported(&f) ? 1 : 0; }
     if (kind != 3 && kind != 4) return 0;
     if (d->stride != 1) return 0;                                // (strided data gradients run by parity class: conv_dgrad_stride2)
-    adamml_conv_desc_t g = *d;                                   // the data-gradient-shaped descriptor conv_launch dispatches on
-    g.H = d->OH; g.W = d->OW; g.Cin = d->Cout; g.OH = d->H; g.OW = d->W; g.Cout = d->Cin; g.accumulate = kind == 4; g.up = 1; g.pad = 0;
+    const adamml_conv_desc_t g = dgrad_desc(d, kind == 4);
     return adamml_conv1x1_wide_expand_supported(&g) ? 1 : 0;
 }
 
@@ -2072,11 +1395,6 @@ extern "C" int adamml_conv_fwd_bn_add_supported(const adamml_conv_desc_t* d) {
     return d && d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && (d->up <= 1) && d->Cin % 8 == 0 && d->Cout % 8 == 0 ? 1 : 0;
 }
 
-// (csrc/conv1x1_fadd_stream.hip: the barrier-free streaming form of the layer-2 shape)
-int adamml_conv1x1_fadd_stream_supported(const adamml_conv_desc_t* d);
-int adamml_conv1x1_fadd_stream_launch(const adamml_conv_desc_t* d, const void* x, const void* w_packed, const float* in_scale, const float* in_shift,
-                                      const float* bn_vec, const void* idn, const float* id_scale, const float* id_shift, int id_gstride, int act,
-                                      void* out, uint8_t* mask_out, hipStream_t stream);
 extern "C" int adamml_conv_fwd_bn_add_streams(const adamml_conv_desc_t* d) {
     return d && adamml_conv_fwd_bn_add_supported(d) && adamml_conv1x1_fadd_stream_supported(d) ? 1 : 0;
 }
@@ -2091,11 +1409,6 @@ extern "C" int adamml_conv_fwd_bn_add(const adamml_conv_desc_t* d, const void* x
     FaddEpi f{bn_vec, idn, id_scale, id_shift, id_gstride, act, mask_out, 0, nullptr, nullptr};
     return conv_launch(d, x, w_packed, in_scale, in_shift, out, nullptr, nullptr, nullptr, 0, stream, nullptr, nullptr, nullptr, nullptr, &f);
 }
-
-bool adamml_conv1x1_fadd_next_supported(const adamml_conv_desc_t* d, int next_cout);
-int adamml_conv1x1_fadd_next_launch(const adamml_conv_desc_t* d, const void* x, const void* w_packed, const float* in_scale, const float* in_shift,
-                                    const float* bn_vec, const void* idn, const float* id_scale, const float* id_shift, int id_gstride, int act,
-                                    void* out, uint8_t* mask_out, const void* w1_packed, void* y1, double* stats1, hipStream_t stream);
 
 extern "C" int adamml_conv_fwd_bn_add_next_supported(const adamml_conv_desc_t* d, int next_cout) {
     return d && next_cout > 0 && adamml_conv_fwd_bn_add_supported(d) && adamml_conv1x1_fadd_next_supported(d, next_cout) ? 1 : 0;
@@ -2112,16 +1425,6 @@ extern "C" int adamml_conv_fwd_bn_add_next(const adamml_conv_desc_t* d, const vo
                                            w_next, y_next, stats_next, stream);
 }
 
-// csrc/conv1x1_fadd_next.hip: the streaming form for layer 1 (64 -> 256)
-bool adamml_conv1x1_fadd_tpool_supported(const adamml_conv_desc_t* d, int frames);
-int adamml_conv1x1_fadd_tpool_launch(const adamml_conv_desc_t* d, const void* x, const void* w_packed, const float* in_scale, const float* in_shift,
-                                     const float* bn_vec, const void* idn, const float* id_scale, const float* id_shift, int id_gstride, int act,
-                                     int frames, void* pooled, uint16_t* code, hipStream_t stream);
-
-int adamml_conv1x1_fadd_tpool_stream_supported(const adamml_conv_desc_t* d, int frames);
-int adamml_conv1x1_fadd_tpool_stream_launch(const adamml_conv_desc_t* d, const void* x, const void* w_packed, const float* in_scale, const float* in_shift,
-                                            const float* bn_vec, const void* idn, const float* id_scale, const float* id_shift, int id_gstride, int act,
-                                            int frames, void* pooled, uint16_t* code, hipStream_t stream);
 extern "C" int adamml_conv_fwd_bn_add_tpool_supported(const adamml_conv_desc_t* d, int frames, int act, int lazy_input) {
     if (!adamml_conv_fwd_bn_add_supported(d)) return 0;
     if (!(frames == 2 || frames == 4 || frames == 8) || d->N % frames || d->Cout % 128 || act != ADAMML_ACT_RELU) return 0;
@@ -2155,47 +1458,6 @@ extern "C" int adamml_conv_fwd_bn_add_tpool(const adamml_conv_desc_t* d, const v
     return conv_launch(d, x, w_packed, in_scale, in_shift, pooled, nullptr, nullptr, nullptr, 0, stream, nullptr, nullptr, nullptr, nullptr, &f);
 }
 
-// Per-channel sum / sum of squares of z = W a over the pixels of each group WITHOUT z: sum z[co] = W[co,:] . s and
-// sum z[co]^2 = W[co,:] G W[co,:]^T with the Gram matrix G = a^T a [Cin, Cin] and the column sums s [Cin] of the conv input
-// (both over the pixels, fp32 from adamml_conv_bwd_weight_grouped / adamml_lazy_colsum).  W = the bf16 forward pack the conv
-// multiplies with.  sums: [groups][2*Cout] plain doubles (nslots = 1 for adamml_bn_finalize).  One wave per (group, cout).
-__global__ void gram_stats_kernel(const bf16_t* w, const float* G, const float* s, double* sums, int Cout, int Cin) {
-    const int co = blockIdx.x, g = blockIdx.y, lane = threadIdx.x;
-    const bf16_t* wr = w + (size_t)co * Cin;
-    const float* Gg = G + (size_t)g * Cin * Cin;
-    const float* sg = s + (size_t)g * Cin;
-    double a1 = 0.0, a2 = 0.0;
-    for (int ci = lane; ci < Cin; ci += 64) {
-        const double wi = (double)__builtin_bit_cast(float, (unsigned)wr[ci] << 16);
-        // t = (G w)[ci] read down COLUMN ci of the symmetric G: the 64 lanes of a load touch two contiguous lines (row-wise every lane walked
-        // its own 256-byte row: 64 lines per load instruction, 67 us per launch on the forward critical path of every fused conv3), four
-        // independent partial sums so that the loads of four steps are in flight together
-        const float* col = Gg + ci;
-        double t0 = 0.0, t1 = 0.0, t2 = 0.0, t3 = 0.0;
-        for (int cj = 0; cj < Cin; cj += 4) {                        // (Cin % 4 == 0: 64 / 128 / 256)
-            t0 += (double)col[(size_t)cj * Cin] * (double)__builtin_bit_cast(float, (unsigned)wr[cj] << 16);
-            t1 += (double)col[(size_t)(cj + 1) * Cin] * (double)__builtin_bit_cast(float, (unsigned)wr[cj + 1] << 16);
-            t2 += (double)col[(size_t)(cj + 2) * Cin] * (double)__builtin_bit_cast(float, (unsigned)wr[cj + 2] << 16);
-            t3 += (double)col[(size_t)(cj + 3) * Cin] * (double)__builtin_bit_cast(float, (unsigned)wr[cj + 3] << 16);
-        }
-        a1 += wi * (double)sg[ci];
-        a2 += wi * ((t0 + t1) + (t2 + t3));
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) { a1 += __shfl_xor(a1, off, 64); a2 += __shfl_xor(a2, off, 64); }
-    if (lane == 0) {
-        sums[(size_t)g * 2 * Cout + co] = a1;
-        sums[(size_t)g * 2 * Cout + Cout + co] = a2;
-    }
-}
-
-extern "C" int adamml_gram_stats(const void* w_packed, const float* G, const float* s, double* sums, int Cout, int Cin, int groups,
-                                 hipStream_t stream) {
-    if (!w_packed || !G || !s || !sums || Cout < 1 || Cin < 4 || (Cin & 3) || groups < 1) return adamml_set_error(ADAMML_EINVAL, "gram_stats: bad arguments (Cin must be a multiple of 4)");
-    hipLaunchKernelGGL(gram_stats_kernel, dim3(Cout, groups), dim3(64), 0, stream, (const bf16_t*)w_packed, G, s, sums, Cout, Cin);
-    return adamml_check_launch("gram_stats");
-}
-
 // Data gradient of a stride-2 conv (3x3 pad 1 / 1x1 pad 0: every strided conv of the hot path) WITHOUT the 4x wasted work
 // of a zero-upsampled stride-1 conv: the dx pixels split into 4 parity classes (ih % 2, iw % 2); class (ph, pw) only
 // receives the taps with kh == ph + pad (mod 2), kw likewise -- 1, 2, 2 and 4 of the 9 taps of a 3x3, 1/0/0/0 of a 1x1 --
@@ -2203,11 +1465,7 @@ extern "C" int adamml_gram_stats(const void* w_packed, const float* G, const flo
 // without taps is zero-filled (or skipped when accumulating).
 static int conv_dgrad_stride2(const adamml_conv_desc_t* d, const void* dz, const void* w, void* dx, int accumulate, double* sums,
                               const void* z_in, const float* bn_vec, int act, hipStream_t stream) {
-    adamml_conv_desc_t g = *d;
-    g.N = d->N; g.H = d->OH; g.W = d->OW; g.Cin = d->Cout;
-    g.OH = d->H; g.OW = d->W; g.Cout = d->Cin;
-    g.stride = 1; g.up = 1; g.pad = 0;
-    g.act = ACT_NONE; g.accumulate = accumulate; g.in_gstride = 0;
+    const adamml_conv_desc_t g = dgrad_desc(d, accumulate);
     const int taps = d->KH * d->KW;
     for (int ph = 0; ph < 2; ++ph)
         for (int pw = 0; pw < 2; ++pw) {
@@ -2243,11 +1501,7 @@ extern "C" int adamml_conv_bwd_data_bn(const adamml_conv_desc_t* d, const void* 
                                        const void* z_in, const float* bn_vec, int act, double* sums, hipStream_t stream) {
     if (!d || !z_in || !bn_vec || !sums) return adamml_set_error(ADAMML_EINVAL, "conv_bwd_data_bn: null argument");
     if (dgrad_stride2_ok(d)) return conv_dgrad_stride2(d, dz, w_dgrad_packed, dx, 0, sums, z_in, bn_vec, act, stream);
-    adamml_conv_desc_t g = *d;
-    g.N = d->N; g.H = d->OH; g.W = d->OW; g.Cin = d->Cout;
-    g.OH = d->H; g.OW = d->W; g.Cout = d->Cin;
-    g.stride = 1; g.up = d->stride; g.pad = d->KH - 1 - d->pad;
-    g.act = ACT_NONE; g.accumulate = 0; g.in_gstride = 0;
+    const adamml_conv_desc_t g = dgrad_desc(d, 0, true);
     return conv_launch(&g, dz, w_dgrad_packed, nullptr, nullptr, dx, sums, z_in, bn_vec, act, stream);
 }
 
@@ -2269,131 +1523,9 @@ extern "C" int adamml_conv_bwd_data_dual(const adamml_conv_desc_t* d, const void
     if (z_in && accumulate) return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_data_dual: the BatchNorm epilogue does not accumulate");
     if (adamml_conv1x1_narrow_dual_supported(d))             // projection convs of the MobileNetV2s: barrier-free streaming kernel (conv1x1_narrow.hip)
         return adamml_conv1x1_narrow_dual_launch(d, g, z, aff, dz_side, w_dgrad_packed, dx, accumulate, z_in, bn_vec, act, sums, stream);
-    adamml_conv_desc_t gd = *d;
-    gd.N = d->N; gd.H = d->OH; gd.W = d->OW; gd.Cin = d->Cout;
-    gd.OH = d->H; gd.OW = d->W; gd.Cout = d->Cin;
-    gd.stride = 1; gd.up = 1; gd.pad = 0;
-    gd.act = ACT_NONE; gd.accumulate = accumulate ? 1 : 0; gd.in_gstride = 0;
+    const adamml_conv_desc_t gd = dgrad_desc(d, accumulate);
     DualIn di{z, aff, dz_side};
     return conv_launch(&gd, g, w_dgrad_packed, nullptr, nullptr, dx, sums, z_in, bn_vec, act, stream, nullptr, nullptr, &di);
-}
-
-bool adamml_alg_stream_supported(int Cout, int Cin);
-int adamml_alg_stream_launch(const adamml_conv_desc_t* d, const void* g, const void* a, const float* a_scale, const float* a_shift,
-                             const void* w_alg, const float* epi_add, void* dx, int accumulate, const void* z_in, const float* bn_vec,
-                             int act, double* sums, hipStream_t stream);
-
-// ---- algebraic BatchNorm backward through a 1x1 conv z = W a followed by a linear BatchNorm (dz = A g' + B z + C per channel):
-//   dx = (W^T diag(A)) g' + (W^T diag(B) W) a + W^T C,   dW = A (.) (g'^T a) + B (.) (W G) + C (x) s,  G = a^T a, s = sum_p a
-// -- neither z nor dz is read or written.  Per BatchNorm group g the data gradient is ONE GEMM over the concatenated input
-// [g' | a] with the weight pack [Cin][Cout + Cin] built here, plus a constant per output channel.
-__global__ void alg_pack_kernel(const float* w, const float* aff, const float* m_pre, bf16_t* wp, float* cadd, int Cout, int Cin, int groups) {
-    // one thread per (group, ci, k): k < Cout -> W[k][ci] * A[k]; else M[ci][k - Cout] = sum_co W[co][ci] B[co] W[co][k - Cout]
-    const int K = Cout + Cin;
-    const size_t total = (size_t)groups * Cin * K;
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-        const int k = (int)(e % K);
-        const int ci = (int)((e / K) % Cin);
-        const int g = (int)(e / ((size_t)K * Cin));
-        const float* A = aff + (size_t)g * 3 * Cout;
-        const float* B = A + Cout;
-        float v;
-        if (k < Cout) v = w[(size_t)k * Cin + ci] * A[k];
-        else {
-            const int cj = k - Cout;
-            if (m_pre) v = m_pre[((size_t)g * Cin + ci) * Cin + cj];      // M_g computed by a GEMM (large Cin)
-            else {
-                float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;                // (Cout % 32 == 0; split accumulators: see alg_wgrad_combine)
-#pragma unroll 4
-                for (int co = 0; co < Cout; co += 4) {
-                    a0 = fmaf(w[(size_t)co * Cin + ci] * B[co], w[(size_t)co * Cin + cj], a0);
-                    a1 = fmaf(w[(size_t)(co + 1) * Cin + ci] * B[co + 1], w[(size_t)(co + 1) * Cin + cj], a1);
-                    a2 = fmaf(w[(size_t)(co + 2) * Cin + ci] * B[co + 2], w[(size_t)(co + 2) * Cin + cj], a2);
-                    a3 = fmaf(w[(size_t)(co + 3) * Cin + ci] * B[co + 3], w[(size_t)(co + 3) * Cin + cj], a3);
-                }
-                v = (a0 + a1) + (a2 + a3);
-            }
-        }
-        wp[e] = __builtin_bit_cast(bf16_t, (__bf16)v);
-        if (k == 0) {
-            const float* Cc = A + 2 * Cout;
-            float acc = 0.f;
-            for (int co = 0; co < Cout; ++co) acc = fmaf(w[(size_t)co * Cin + ci], Cc[co], acc);
-            cadd[(size_t)g * Cin + ci] = acc;
-        }
-    }
-}
-
-// dW[co][ci] += sum_g  A_g[co] P_g[co][ci] + B_g[co] sum_cj W[co][cj] G_g[cj][ci] + C_g[co] s_g[ci]
-__global__ void alg_wgrad_combine_kernel(const float* w, const float* aff, const float* P, const float* G, const float* wg_pre, const float* s,
-                                         float* dw, int Cout, int Cin, int groups) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= Cout * Cin) return;
-    const int co = e / Cin, ci = e - co * Cin;
-    float acc = 0.f;
-    for (int g = 0; g < groups; ++g) {
-        const float* A = aff + (size_t)g * 3 * Cout;
-        const float* Gg = G + (size_t)g * Cin * Cin;
-        float wg = 0.f;
-        if (wg_pre) wg = wg_pre[(size_t)co * groups * Cin + (size_t)g * Cin + ci];        // (W G_g) computed by a GEMM (large Cin)
-        else {
-            // (unrolled with split accumulators: one dependent L2 round trip per cj made this 0.2 ms per layer-2 block)
-            float w0 = 0.f, w1 = 0.f, w2 = 0.f, w3 = 0.f;
-            const float* wr = w + (size_t)co * Cin;
-#pragma unroll 4
-            for (int cj = 0; cj < Cin; cj += 4) {
-                w0 = fmaf(wr[cj], Gg[(size_t)cj * Cin + ci], w0);
-                w1 = fmaf(wr[cj + 1], Gg[(size_t)(cj + 1) * Cin + ci], w1);
-                w2 = fmaf(wr[cj + 2], Gg[(size_t)(cj + 2) * Cin + ci], w2);
-                w3 = fmaf(wr[cj + 3], Gg[(size_t)(cj + 3) * Cin + ci], w3);
-            }
-            wg = (w0 + w1) + (w2 + w3);
-        }
-        acc += A[co] * P[((size_t)g * Cout + co) * Cin + ci] + A[Cout + co] * wg + A[2 * Cout + co] * s[(size_t)g * Cin + ci];
-    }
-    dw[e] += acc;
-}
-
-// Second BatchNorm-backward moment from the algebraic identity  sum_p g'[p,co] z[p,co] = sum_cj W[co,cj] (g'^T a)[co,cj]  (z = W a):
-// sums [groups][SLOTS][2C] holds sum(g') in its first halves (epilogues run with z == NULL leave the second halves zero);
-// writes sum(g' zhat) = invstd (sum_j W (.) P - mean * sum g') into slot 0 of the second half.
-__global__ void alg_sumfix_kernel(const float* w, const float* P, const float* vec, double* sums, int Cout, int Cin, int groups) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= Cout * groups) return;
-    const int g = e / Cout, co = e - g * Cout;
-    double* sg = sums + (size_t)g * ADAMML_STAT_SLOTS * 2 * Cout;
-    double s1 = 0.0;
-    s1 = det_decode(sg + co, 2 * (size_t)Cout);
-    const float* Pg = P + ((size_t)g * Cout + co) * Cin;
-    double dot = 0.0;
-    for (int cj = 0; cj < Cin; ++cj) dot += (double)w[(size_t)co * Cin + cj] * (double)Pg[cj];
-    const float* v = vec + (size_t)g * 4 * Cout;
-    const double r = (double)v[3 * Cout + co] * (dot - (double)v[2 * Cout + co] * s1);
-    det_encode(sg + Cout + co, 2 * (size_t)Cout, r);
-}
-
-extern "C" int adamml_alg_sumfix(const float* w, const float* P, const float* vec, double* sums, int Cout, int Cin, int groups,
-                                 hipStream_t stream) {
-    if (!w || !P || !vec || !sums) return adamml_set_error(ADAMML_EINVAL, "alg_sumfix: null argument");
-    hipLaunchKernelGGL(alg_sumfix_kernel, dim3(ceil_div(Cout * groups, 128)), dim3(128), 0, stream, w, P, vec, sums, Cout, Cin, groups);
-    return adamml_check_launch("alg_sumfix");
-}
-
-extern "C" int adamml_alg_pack(const float* w, const float* aff, const float* m_pre, void* w_alg, float* epi_add, int Cout, int Cin,
-                               int groups, hipStream_t stream) {
-    if (!w || !aff || !w_alg || !epi_add || Cout < 1 || Cin < 1 || groups < 1) return adamml_set_error(ADAMML_EINVAL, "alg_pack: bad arguments");
-    if (Cout % 4) return adamml_set_error(ADAMML_EUNSUPPORTED, "alg_pack: Cout must be a multiple of 4");
-    const size_t total = (size_t)groups * Cin * (Cout + Cin);
-    hipLaunchKernelGGL(alg_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, w, aff, m_pre, (bf16_t*)w_alg, epi_add, Cout, Cin, groups);
-    return adamml_check_launch("alg_pack");
-}
-
-extern "C" int adamml_alg_wgrad_combine(const float* w, const float* aff, const float* P, const float* G, const float* wg_pre, const float* s,
-                                        float* dw, int Cout, int Cin, int groups, hipStream_t stream) {
-    if (!w || !aff || !P || (!G && !wg_pre) || !s || !dw) return adamml_set_error(ADAMML_EINVAL, "alg_wgrad_combine: null argument");
-    if (Cin % 4 || Cout % 4) return adamml_set_error(ADAMML_EUNSUPPORTED, "alg_wgrad_combine: Cin and Cout must be multiples of 4");
-    hipLaunchKernelGGL(alg_wgrad_combine_kernel, dim3(ceil_div(Cout * Cin, 256)), dim3(256), 0, stream, w, aff, P, G, wg_pre, s, dw, Cout, Cin, groups);
-    return adamml_check_launch("alg_wgrad_combine");
 }
 
 extern "C" int adamml_conv_bwd_data_alg_streams(const adamml_conv_desc_t* d) {
@@ -2409,13 +1541,10 @@ extern "C" int adamml_conv_bwd_data_alg(const adamml_conv_desc_t* d, const void*
     if ((z_in != nullptr) != (bn_vec != nullptr) || (z_in != nullptr) != (sums != nullptr))
         return adamml_set_error(ADAMML_EINVAL, "conv_bwd_data_alg: incomplete BatchNorm epilogue operands");
     if (z_in && accumulate) return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_data_alg: the BatchNorm epilogue does not accumulate");
-    adamml_conv_desc_t gd = *d;
-    gd.N = d->N; gd.H = d->OH; gd.W = d->OW; gd.Cin = d->Cout;
-    gd.OH = d->H; gd.OW = d->W; gd.Cout = d->Cin;
-    gd.stride = 1; gd.up = 1; gd.pad = 0;
-    gd.act = d->act; gd.accumulate = accumulate ? 1 : 0; gd.in_gstride = d->in_gstride;
     if (adamml_alg_stream_supported(d->Cout, d->Cin))
         return adamml_alg_stream_launch(d, g, a, a_scale, a_shift, w_alg, epi_add, dx, accumulate, z_in, bn_vec, act, sums, stream);
+    adamml_conv_desc_t gd = dgrad_desc(d, accumulate);
+    gd.act = d->act; gd.in_gstride = d->in_gstride;          // the lazy transform of the concatenated operand a (the loader applies it to a only)
     CatIn c{a, d->Cin, (size_t)d->Cin * (d->Cout + d->Cin), epi_add};
     return conv_launch(&gd, g, w_alg, a_scale, a_shift, dx, sums, z_in, bn_vec, act, stream, nullptr, nullptr, nullptr, &c);
 }
@@ -2424,10 +1553,6 @@ extern "C" int adamml_conv_bwd_data_res_supported(const adamml_conv_desc_t* d) {
     return d && d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && d->Cin % 8 == 0 && d->Cout % 8 == 0 ? 1 : 0;
 }
 
-// (csrc/res_prod_stream.hip: the barrier-free streaming forms)
-int adamml_res_stream_supported(const adamml_conv_desc_t* d);
-int adamml_res_stream_launch(const adamml_conv_desc_t* d, const void* dz, const void* w_dgrad_packed, void* dx, const uint8_t* res_mask, double* sums_a,
-                             const void* z_b, const float* vec_b, double* sums_b, hipStream_t stream);
 extern "C" int adamml_conv_bwd_data_res_streams(const adamml_conv_desc_t* d) {
     return d && adamml_conv_bwd_data_res_supported(d) && adamml_res_stream_supported(d) ? 1 : 0;
 }
@@ -2442,21 +1567,10 @@ extern "C" int adamml_conv_bwd_data_res(const adamml_conv_desc_t* d, const void*
     if (!adamml_conv_bwd_data_res_supported(d)) return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_data_res: only 1x1 / stride-1 convs");
     if (accumulate && res_mask && !z_a && adamml_res_stream_supported(d))       // (the algebraic backward's form at the layer-2 shape)
         return adamml_res_stream_launch(d, dz, w_dgrad_packed, dx, res_mask, sums_a, z_b, vec_b, sums_b, stream);
-    adamml_conv_desc_t g = *d;
-    g.N = d->N; g.H = d->OH; g.W = d->OW; g.Cin = d->Cout;
-    g.OH = d->H; g.OW = d->W; g.Cout = d->Cin;
-    g.stride = 1; g.up = 1; g.pad = 0;
-    g.act = ACT_NONE; g.accumulate = accumulate ? 1 : 0; g.in_gstride = 0;
+    const adamml_conv_desc_t g = dgrad_desc(d, accumulate);
     ResEpi r{res_out, res_mask, res_act, z_b, vec_b, sums_b};
     return conv_launch(&g, dz, w_dgrad_packed, nullptr, nullptr, dx, sums_a, z_a, vec_a, ACT_NONE, stream, nullptr, &r);
 }
-
-// (csrc/res_prod_stream.hip: the barrier-free streaming form of the layer-1 shape)
-int adamml_res_prod_stream_supported(const adamml_conv_desc_t* d, int a_channels);
-size_t adamml_res_prod_stream_workspace(const adamml_conv_desc_t* d);
-int adamml_res_prod_stream_launch(const adamml_conv_desc_t* d, const void* dz, const void* w_dgrad_packed, void* dx, const uint8_t* res_mask,
-                                  double* sums_a, const void* a, const float* a_scale, const float* a_shift, int a_act, int a_gstride,
-                                  float* prod, void* workspace, size_t workspace_bytes, hipStream_t stream);
 
 extern "C" size_t adamml_conv_bwd_data_res_prod_workspace(const adamml_conv_desc_t* d) {
     if (!d) return 0;
@@ -2488,9 +1602,7 @@ extern "C" int adamml_conv_bwd_data_res_prod(const adamml_conv_desc_t* d, const 
     if (adamml_res_prod_stream_supported(d, a_channels))
         return adamml_res_prod_stream_launch(d, dz, w_dgrad_packed, dx, res_mask, sums_a, a, a_scale, a_shift, a_act, a_gstride, prod, workspace,
                                              workspace_bytes, stream);
-    adamml_conv_desc_t dd = *d;                          // data gradient of d: swap the channel roles, as adamml_conv_bwd_data_res does
-    dd.H = d->OH; dd.W = d->OW; dd.Cin = d->Cout; dd.OH = d->H; dd.OW = d->W; dd.Cout = d->Cin;
-    dd.stride = 1; dd.up = 1; dd.pad = 0; dd.act = ACT_NONE; dd.accumulate = 1; dd.in_gstride = 0;
+    const adamml_conv_desc_t dd = dgrad_desc(d, 1);
     ResEpi r{dx, res_mask, res_act, nullptr, nullptr, nullptr};       // (res_out is never read in the mask form)
     PfIn pf{a, a_scale, a_shift, a_act, a_gstride, a_channels, prod, workspace, workspace_bytes};
     return conv_launch(&dd, dz, w_dgrad_packed, nullptr, nullptr, dx, sums_a, nullptr, nullptr, 0, stream, nullptr, &r, nullptr, nullptr, nullptr, &pf);
@@ -2502,207 +1614,6 @@ extern "C" int adamml_conv_bwd_data(const adamml_conv_desc_t* d, const void* dz,
     // flipped / transposed weight pack (adamml_pack_conv_weight, mode 1).
     if (!d) return adamml_set_error(ADAMML_EINVAL, "conv_bwd_data: null desc");
     if (dgrad_stride2_ok(d)) return conv_dgrad_stride2(d, dz, w_dgrad_packed, dx, accumulate, nullptr, nullptr, nullptr, 0, stream);
-    adamml_conv_desc_t g = *d;
-    g.N = d->N; g.H = d->OH; g.W = d->OW; g.Cin = d->Cout;
-    g.OH = d->H; g.OW = d->W; g.Cout = d->Cin;
-    g.stride = 1; g.up = d->stride; g.pad = d->KH - 1 - d->pad;
-    g.act = ACT_NONE; g.accumulate = accumulate; g.in_gstride = 0;
+    const adamml_conv_desc_t g = dgrad_desc(d, accumulate, true);
     return adamml_conv_fwd(&g, dz, w_dgrad_packed, nullptr, nullptr, dx, nullptr, stream);
-}
-
-constexpr int W3_SLOTS = 4;      // 16-byte patch chunks a thread of conv3x3_wgrad_kernel stages per unit (3 x 34 pixels x 8 chunks = 816 <= 4 x 256)
-
-// split plan shared by the workspace query and the launcher
-struct WgradPlan { bool use3x3; int nsplit, per_block, n_cotiles, n_tiles, BM, BN, NK, cin_shift; int cw, rows, PR, PC, upi, upr, total_units, buf_bytes; };
-
-static int wgrad_plan(const adamml_conv_desc_t* d, int cin_true, WgradPlan* pl) {
-    const int taps = d->KH * d->KW;
-    pl->use3x3 = false;
-    // the LDS-patch kernel only pays on wide feature maps (measured on MI355X: 56x56 1.87 ms vs 1.97 ms generic; at
-    // 28x28 and below the generic implicit-GEMM gather is 5-40 % faster)
-    // (stride 1 only: a 32-column strip of a stride-2 conv needs a 3 x 65 patch, more than the staging slots of a workgroup hold)
-    if (d->OW > 32 && d->KH == 3 && d->KW == 3 && d->pad == 1 && d->stride == 1 && d->Cin % 64 == 0 && d->Cout % 64 == 0 &&
-        cin_true == d->Cin) {
-        if (d->OW > 32) { pl->cw = 32; pl->rows = 1; pl->upr = ceil_div(d->OW, 32); }
-        else { pl->cw = d->OW; pl->rows = 32 / d->OW; pl->upr = 1; }
-        pl->PR = (pl->rows - 1) * d->stride + 3;
-        pl->PC = (pl->cw - 1) * d->stride + 3;
-        pl->upi = ceil_div(d->OH, pl->rows) * pl->upr;
-        pl->total_units = d->N * pl->upi;
-        pl->buf_bytes = 32 * 128 + pl->PR * pl->PC * 128;
-        if (pl->PR * pl->PC * 8 <= W3_SLOTS * NTHREADS && 2 * pl->buf_bytes <= 64 * 1024 && pl->total_units > 0) {
-            pl->use3x3 = true;
-            pl->n_cotiles = d->Cout / 64;
-            pl->n_tiles = pl->n_cotiles * (d->Cin / 64);
-            int nsplit = ceil_div(512, pl->n_tiles * (d->groups < 1 ? 1 : d->groups));
-            int upb = ceil_div(pl->total_units, nsplit);
-            if (upb < 4) upb = 4;
-            pl->nsplit = ceil_div(pl->total_units, upb);
-            pl->per_block = upb;
-            return 0;
-        }
-    }
-    pl->NK = taps * d->Cin;
-    pl->cin_shift = 30;                     // 1x1: tap = n >> 30 = 0
-    if (taps > 1) {
-        pl->cin_shift = ilog2_exact(d->Cin);
-        if (pl->cin_shift < 0) return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_weight: KxK conv needs power-of-two Cin (got %d)", d->Cin);
-    }
-    pl->BM = d->Cout <= 64 ? 64 : 128;
-    pl->BN = pl->NK <= 64 ? 64 : 128;
-    pl->n_cotiles = ceil_div(d->Cout, pl->BM);
-    pl->n_tiles = pl->n_cotiles * ceil_div(pl->NK, pl->BN);
-    const int P = d->N * d->OH * d->OW;
-    int nsplit = ceil_div(768, pl->n_tiles * (d->groups < 1 ? 1 : d->groups));
-    int ppb = ceil_div(ceil_div(P, nsplit), 32) * 32;
-    if (ppb < 256) ppb = 256;
-    pl->nsplit = ceil_div(P, ppb);
-    pl->per_block = ppb;
-    return 0;
-}
-
-int adamml_launch_split_reduce(const float* ws, float* dw, size_t n, int nsplit, hipStream_t stream, int taps, int cin) {
-    launch_wgrad_reduce(ws, dw, n, nsplit, taps, cin, 0, 1, stream);
-    return adamml_check_launch("split_reduce");
-}
-
-// per-group form: ws [groups][nsplit][n] -> out [groups][n], OVERWRITTEN (the products of the algebraic BatchNorm backward)
-int adamml_launch_split_reduce_grouped(const float* ws, float* out, size_t n, int nsplit, int groups, int cin, hipStream_t stream) {
-    launch_wgrad_reduce(ws, out, n, nsplit, 1, cin, 1, groups, stream);
-    return adamml_check_launch("split_reduce");
-}
-
-extern "C" size_t adamml_conv_bwd_weight_workspace(const adamml_conv_desc_t* d, int cin_true) {
-    WgradPlan pl;
-    if (!d || wgrad_plan(d, cin_true, &pl)) return 0;
-    const int groups = d->groups < 1 ? 1 : d->groups;
-    size_t need = (size_t)groups * pl.nsplit * d->Cout * cin_true * d->KH * d->KW * sizeof(float);
-    if (adamml_conv3x3_c64_wgrad_supported(d, cin_true)) {
-        const size_t n3 = (size_t)adamml_conv3x3_c64_wgrad_blocks(d, nullptr) * d->Cout * cin_true * 9 * sizeof(float);
-        if (n3 > need) need = n3;
-    }
-    return need;
-}
-
-struct WgradExtra { const float* dz_scale; const float* dz_shift; int dz_act, dz_gstride; bool per_group; };
-
-static int wgrad_launch(const adamml_conv_desc_t* d, const void* dz, const void* x, const float* in_scale, const float* in_shift, float* dw,
-                        int cin_true, void* workspace, size_t workspace_bytes, hipStream_t stream, const WgradExtra* ex);
-
-extern "C" int adamml_conv_bwd_weight(const adamml_conv_desc_t* d, const void* dz, const void* x, const float* in_scale,
-                                      const float* in_shift, float* dw, int cin_true, void* workspace, size_t workspace_bytes,
-                                      hipStream_t stream) {
-    return wgrad_launch(d, dz, x, in_scale, in_shift, dw, cin_true, workspace, workspace_bytes, stream, nullptr);
-}
-
-// Per-group products for the algebraic BatchNorm backward: out[g] = dz_g^T x_g ([groups][Cout][cin_true], OVERWRITTEN), with an
-// optional lazy transform of the dz operand too (Gram matrix a^T a: dz = x = the raw tensor, both transformed).  1x1 convs.
-extern "C" int adamml_conv_bwd_weight_grouped(const adamml_conv_desc_t* d, const void* dz, const float* dz_scale, const float* dz_shift,
-                                              int dz_act, int dz_gstride, const void* x, const float* in_scale, const float* in_shift,
-                                              float* out, int cin_true, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-    if (!d || d->KH * d->KW != 1) return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_weight_grouped: 1x1 convs only");
-    if (!workspace) return adamml_set_error(ADAMML_EINVAL, "conv_bwd_weight_grouped: needs the split workspace");
-    WgradExtra ex{dz_scale, dz_shift, dz_act, dz_gstride, true};
-    return wgrad_launch(d, dz, x, in_scale, in_shift, out, cin_true, workspace, workspace_bytes, stream, &ex);
-}
-
-static int wgrad_launch(const adamml_conv_desc_t* d, const void* dz, const void* x, const float* in_scale, const float* in_shift, float* dw,
-                        int cin_true, void* workspace, size_t workspace_bytes, hipStream_t stream, const WgradExtra* ex) {
-    if (!d || !dz || !x || !dw) return adamml_set_error(ADAMML_EINVAL, "conv_bwd_weight: null argument");
-    if (d->Cin % 8 || d->Cout % 8) return adamml_set_error(ADAMML_EINVAL, "conv_bwd_weight: channels must be multiples of 8");
-    if ((long)d->N * d->OH * d->OW <= 0) return ADAMML_OK;
-    WgradPlan pl;
-    int rc = wgrad_plan(d, cin_true, &pl);
-    if (rc) return rc;
-    const size_t dw_numel = (size_t)d->Cout * cin_true * d->KH * d->KW;
-    const int groups = d->groups < 1 ? 1 : d->groups;
-    if (ex && ex->per_group && !(workspace && workspace_bytes >= (size_t)groups * pl.nsplit * dw_numel * sizeof(float)))
-        return adamml_set_error(ADAMML_EINVAL, "conv_bwd_weight_grouped: workspace too small");
-    if (!ex && workspace && adamml_conv3x3_c64_wgrad_supported(d, cin_true)) {
-        // 3x3 / 64 -> 64: LDS-patch kernel with one partial per workgroup (conv3x3_c64.hip)
-        const int nblk = adamml_conv3x3_c64_wgrad_blocks(d, nullptr);
-        if (workspace_bytes >= (size_t)nblk * dw_numel * sizeof(float)) {
-            rc = adamml_conv3x3_c64_wgrad_launch(d, dz, x, in_scale, in_shift, (float*)workspace, stream);
-            if (rc) return rc;
-            return adamml_launch_split_reduce((const float*)workspace, dw, dw_numel, nblk, stream, 9, cin_true);
-        }
-    }
-    if (!ex && workspace && adamml_conv1x1_narrow_wgrad_supported(d, cin_true) && workspace_bytes >= (size_t)groups * pl.nsplit * dw_numel * sizeof(float)) {
-        // narrow 1x1 convs of the MobileNetV2s: barrier-free streaming kernel, one partial per workgroup (conv1x1_narrow.hip)
-        int nblk = 0;
-        rc = adamml_conv1x1_narrow_wgrad_launch(d, dz, x, in_scale, in_shift, (float*)workspace, pl.nsplit, &nblk, stream);
-        if (rc) return rc;
-        return adamml_launch_split_reduce((const float*)workspace, dw, dw_numel, groups * nblk, stream, 1, cin_true);
-    }
-    float* ws = nullptr;
-    if (workspace && workspace_bytes >= (size_t)groups * pl.nsplit * dw_numel * sizeof(float)) ws = (float*)workspace;
-    dim3 grid(pl.nsplit * pl.n_tiles * groups), block(NTHREADS);
-    const size_t gdz = (size_t)d->N * d->OH * d->OW * d->Cout, gx = (size_t)d->N * d->H * d->W * d->Cin;
-    if (pl.use3x3) {
-        W3P q;
-        q.dz = (const bf16_t*)dz; q.x = (const bf16_t*)x; q.in_scale = in_scale; q.in_shift = in_shift; q.dw = dw;
-        q.ws = ws; q.dw_numel = dw_numel; q.nsplit = pl.nsplit;
-        q.gdz = gdz; q.gx = gx; q.in_gstride = d->in_gstride;
-        q.N = d->N; q.H = d->H; q.W = d->W; q.Cin = d->Cin; q.OH = d->OH; q.OW = d->OW; q.Cout = d->Cout; q.pad = d->pad;
-        q.act = d->act; q.cin_true = cin_true;
-        q.cw = pl.cw; q.rows = pl.rows; q.PR = pl.PR; q.PC = pl.PC; q.units_per_img = pl.upi; q.units_per_row = pl.upr;
-        q.total_units = pl.total_units; q.units_per_block = pl.per_block; q.n_cotiles = pl.n_cotiles; q.n_tiles = pl.n_tiles;
-        hipLaunchKernelGGL((conv3x3_wgrad_kernel<1, W3_SLOTS>), grid, block, 2 * pl.buf_bytes, stream, q);
-    } else {
-        WgradP p;
-        p.dz = (const bf16_t*)dz; p.x = (const bf16_t*)x; p.in_scale = in_scale; p.in_shift = in_shift; p.dw = dw;
-        p.ws = ws; p.dw_numel = dw_numel; p.nsplit = pl.nsplit;
-        p.gdz = gdz; p.gx = gx; p.in_gstride = d->in_gstride;
-        p.N = d->N; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.OH = d->OH; p.OW = d->OW; p.Cout = d->Cout;
-        p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.act = d->act; p.cin_true = cin_true;
-        p.P = d->N * d->OH * d->OW; p.NK = pl.NK; p.cin_shift = pl.cin_shift; p.n_cotiles = pl.n_cotiles; p.n_tiles = pl.n_tiles;
-        p.pix_per_block = pl.per_block;
-        p.dz_scale = ex ? ex->dz_scale : nullptr; p.dz_shift = ex ? ex->dz_shift : nullptr;
-        p.dz_act = ex ? ex->dz_act : 0; p.dz_gstride = ex ? ex->dz_gstride : 0;
-        if (ws && in_scale && !(ex && ex->dz_scale) && pl.BM == 128 && pl.BN == 128 && d->KH * d->KW == 1 && d->pad == 0) {
-            // 1x1 conv with a lazily normalised input: LDS-DMA staging of the raw tensor, transform at the B fragment (LZB); same tile choice
-            if (d->Cout % 256 == 0 && pl.n_tiles <= 64) {
-                p.n_cotiles = d->Cout / 256; p.n_tiles = p.n_cotiles * ceil_div(pl.NK, 128);
-                hipLaunchKernelGGL((conv_wgrad_glds_kernel<256, 128, 2, true>), dim3(pl.nsplit * p.n_tiles * groups), block, 0, stream, p);
-            } else if (d->Cout == 128 && pl.NK % 256 == 0) {
-                p.n_tiles = p.n_cotiles * (pl.NK / 256);
-                hipLaunchKernelGGL((conv_wgrad_glds_kernel<128, 256, 2, true>), dim3(pl.nsplit * p.n_tiles * groups), block, 0, stream, p);
-            } else
-            hipLaunchKernelGGL((conv_wgrad_glds_kernel<128, 128, 3, true>), grid, block, 0, stream, p);
-        } else
-        if (ws && !in_scale && !(ex && ex->dz_scale) && pl.BM == 128 && pl.BN == 128) {
-            // both operands plain in memory: LDS-DMA staging
-            // 256-wide tiles halve the operand bytes fetched per MAC (this kernel is bound by the L1 load path: 16 KB per 128 x 128 x 32
-            // step = 256 cycles of 64 B/clk against 256 cycles of MFMA).  Measured (tools/bench_conv.py, B = 72, TFLOP/s 128^2 -> wide):
-            // 256 x 128 for Cout % 256 == 0: layer 3 conv1 366 -> 476, conv2 458 -> 616, downsample 329 -> 451, layer-2 downsample
-            // 407 -> 512; it loses where the pixel axis is short and the tile list long (layer 4 conv2 / downsample: 376 -> 367, 366 -> 339);
-            // 128 x 256 for a single cout tile: layer-2 conv1 374 -> 453.
-            if (d->Cout % 256 == 0 && pl.n_tiles <= 64) {
-                p.n_cotiles = d->Cout / 256; p.n_tiles = p.n_cotiles * ceil_div(pl.NK, 128);
-                hipLaunchKernelGGL((conv_wgrad_glds_kernel<256, 128, 2>), dim3(pl.nsplit * p.n_tiles * groups), block, 0, stream, p);
-            } else if (d->Cout == 128 && (pl.NK % 256 == 0 || pl.NK > 512)) {
-                // (NK % 256 != 0: the last tile is half empty -- 3x3 / 128 -> 128: 5 tiles of 256 instead of 9 of 128; measured +4 %)
-                p.n_tiles = p.n_cotiles * ceil_div(pl.NK, 256);
-                hipLaunchKernelGGL((conv_wgrad_glds_kernel<128, 256, 2>), dim3(pl.nsplit * p.n_tiles * groups), block, 0, stream, p);
-            } else
-            hipLaunchKernelGGL((conv_wgrad_glds_kernel<128, 128, 3>), grid, block, 0, stream, p);
-        } else
-        if (ex && ex->dz_scale) {
-            if (pl.BM == 64 && pl.BN == 64) hipLaunchKernelGGL((conv_wgrad_kernel<64, 64, 1, true>), grid, block, 0, stream, p);
-            else if (pl.BM == 128 && pl.BN == 128) hipLaunchKernelGGL((conv_wgrad_kernel<128, 128, 1, true>), grid, block, 0, stream, p);
-            else return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_weight_grouped: lazy dz needs Cout == Cin in {64, >= 128}");
-        } else
-        if (pl.BM == 64 && pl.BN == 64) hipLaunchKernelGGL((conv_wgrad_kernel<64, 64>), grid, block, 0, stream, p);
-        else if (pl.BM == 64) hipLaunchKernelGGL((conv_wgrad_kernel<64, 128>), grid, block, 0, stream, p);
-        else if (pl.BN == 64) hipLaunchKernelGGL((conv_wgrad_kernel<128, 64>), grid, block, 0, stream, p);
-        else if ((long)grid.x * grid.y <= 1100) hipLaunchKernelGGL((conv_wgrad_kernel<128, 128, 6>), grid, block, 0, stream, p);
-        else hipLaunchKernelGGL((conv_wgrad_kernel<128, 128>), grid, block, 0, stream, p);
-    }
-    rc = adamml_check_launch("conv_bwd_weight");
-    if (rc || !ws) return rc;
-    if (ex && ex->per_group) {
-        launch_wgrad_reduce(ws, dw, dw_numel, pl.nsplit, 1, cin_true, 1, groups, stream);
-        return adamml_check_launch("split_reduce");
-    }
-    return adamml_launch_split_reduce(ws, dw, dw_numel, groups * pl.nsplit, stream, d->KH * d->KW, cin_true);
 }

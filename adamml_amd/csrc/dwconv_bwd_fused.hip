@@ -12,6 +12,7 @@
 // g', z, x are read once and dx written once: four passes instead of eight.  Stride 2 (S = 2): the thread owns a 2 x 4 block of input
 // pixels per step and the 2 x 3 dz pixels that reach it.
 #include "common.h"
+#include "conv_internal.h"
 #include "../../include/adamml_hip.h"
 
 namespace {

@@ -2,6 +2,7 @@
 // forward / data-grad / weight-grad as VALU kernels (K = 9 per channel: bandwidth work, not MFMA work), and the
 // fp32 strided GEMM used by the Linear / LSTMCell layers of the policy head and the classifier heads.
 #include "common.h"
+#include "conv_internal.h"
 #include "../../include/adamml_hip.h"
 
 

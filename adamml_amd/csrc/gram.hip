@@ -15,12 +15,10 @@
 // a workspace with plain stores ([group][split][C*C + C]) and are summed in a fixed order by gram_reduce_kernel, so the
 // result does not depend on the arrival order (deterministic mode needs no special path).
 #include "common.h"
+#include "tile.h"      // NTHREADS, static_for, tr_swz: the transpose-read image of conv_wgrad_kernel
 #include "../../include/adamml_hip.h"
-#include <type_traits>
 
 namespace {
-
-constexpr int NTHREADS = 256;
 
 struct GramP {
     const bf16_t* x;
@@ -31,22 +29,6 @@ struct GramP {
     int gstride, act;
     int P, ppb, nsplit;
 };
-
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (N > 0) {
-        static_for<N - 1>(f);
-        f(std::integral_constant<int, N - 1>{});
-    }
-}
-
-// 8-byte-unit XOR swizzle of the [32 pixels][CH channels] transpose-read image (same as conv_gemm.hip: the two 32-lane
-// service groups of ds_read_b64_tr_b16 touch 64 distinct banks)
-template <int CH>
-__device__ __forceinline__ int tr_swz(int row) {
-    if (CH >= 128) return ((row & 3) | (((row >> 3) & 1) << 2)) << 2;
-    return (((row >> 1) & 1) | (((row >> 3) & 1) << 1)) << 2;
-}
 
 template <int C, int D>
 __global__ __launch_bounds__(NTHREADS) void gram_colsum_kernel(GramP p) {

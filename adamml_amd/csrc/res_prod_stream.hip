@@ -13,6 +13,7 @@
 // product over hardware transpose reads of both (pixels = the reduction dimension).  All loads of the workgroup's next tile are
 // requested, unconditionally and clamped, between the stores and the product.  g' is bit-identical to the tile kernel's.
 #include "common.h"
+#include "conv_internal.h"
 #include "../../include/adamml_hip.h"
 #include <type_traits>
 
@@ -272,7 +273,7 @@ bool rps_1x1(const adamml_conv_desc_t* d) {
 
 }  // namespace
 
-// (declared in conv_gemm.hip, which owns the C entry points and falls back to its tile kernel)
+// (declared in conv_internal.h; conv_gemm.hip owns the C entry points and falls back to its tile kernel)
 int adamml_res_prod_stream_supported(const adamml_conv_desc_t* d, int a_channels) {
     return rps_on() && rps_1x1(d) && d->Cin == 256 && d->Cout == 64 && a_channels == CIN ? 1 : 0;
 }

@@ -11,6 +11,7 @@
 // (pixels = the reduction dimension).  g2 and sum(g2) as adamml_temporal_pool_bwd_code (g2 bit-identical); one partial P per workgroup.
 #include <type_traits>
 #include "common.h"
+#include "conv_internal.h"
 #include "../../include/adamml_hip.h"
 
 namespace {

@@ -1,5 +1,5 @@
 """float64 references and error models of the C-ABI entry points outside the conv / elementwise conformance suites: the algebraic
-BatchNorm backward (csrc/conv_gemm.hip alg_*_kernel, csrc/conv1x1_stream.hip), adamml_gemm_f32 (csrc/dwconv_gemm32.hip), the classifier
+BatchNorm backward (csrc/conv_alg.hip alg_*_kernel, csrc/conv1x1_stream.hip), adamml_gemm_f32 (csrc/dwconv_gemm32.hip), the classifier
 head, adamml_colsum_f32 / adamml_lazy_colsum, the input re-layout kernels and the optimizer steps (csrc/elementwise.hip), the policy
 head, the Gumbel gate and the late fusion (csrc/policy_head.hip).
 
@@ -23,14 +23,14 @@ k is counted from the source line (a contracted fma rounds less often than the s
                                epi_add: `acc = fmaf(w, Cc, acc)` over Cout -> k = acc(Cout), float32 (rho = 0).
   alg_wgrad_combine_kernel     `acc += A P + B wg + C s` per group, `dw[e] += acc`: every term passes its product, the two adds of the
                                line, the add into acc of its own and of every later group, and the final add -> k = G + 4 on
-                               abs = |dw0| + sum_g |A P| + |B| abs(wg) + |C s|; wg = the split fma inner product over Cin (conv_gemm.hip:2341-2350)
+                               abs = |dw0| + sum_g |A P| + |B| abs(wg) + |C s|; wg = the split fma inner product over Cin (conv_alg.hip, the w0..w3 loop)
                                adds |B| acc(Cin) u abs(wg) (nothing when wg_pre is given: it is read).
   alg_sumfix_kernel            fp64: `dot += (double)w * (double)P` (products of two float32 are exact in fp64) over Cin, then
                                `r = invstd * (dot - mean * s1)`: Cin - 1 adds, one product, one subtraction, one product ->
                                |r - ref| <= (Cin + 3) 2^-53 |invstd| (|W|.|P| + |mean| |s1|): an ABSOLUTE bound that carries the cancellation
                                of dot against mean * s1; det_encode stores r exactly (three float32 pieces hold 53 bits).
   conv_bwd_data_alg            one GEMM over [g' | a] (bf16 x bf16 exact, float32 accumulation, n = Cout + Cin: conv_ref's model), a = the lazy
-                               read rounded to bf16 as the loaders stage it.  CatIn tile path (conv_gemm.hip:926,959-968): the tile is staged in
+                               read rounded to bf16 as the loaders stage it.  CatIn tile path (conv_gemm_kernel's epi_add reads in its epilogue): the tile is staged in
                                LDS as bf16 BEFORE epi_add is added (extra 2^-8 |gemm|), `f += epi_add; v = f32_to_bf8(f)` (the output rounding,
                                1 u for the add), accumulate: `f += y; v = f32_to_bf8(f)` (extra 2^-8 |gemm + epi_add|, 1 u).  Streaming kernel
                                (conv1x1_stream.hip:154-177): `f += s_add` on the float32 accumulator (1 u), accumulate: the tile is rounded

@@ -40,7 +40,7 @@ C_ACC sqrt(n) 2^-24 abs of conv_ref.tolerance, or one of these, passed as `extra
    (dgrad_epi_ref) or BatchNorm-fused (mask exact, no extra) epilogue.
  Gram (gram.hip): float32 MFMA accumulation inside a split of the pixels, the splits summed in float64 and rounded once: n = P,
    rho = RHO_F32, per element; C = 256 mirrors each off-diagonal block pair: G == G^T bitwise.
- gram_stats (conv_gemm.hip gram_stats_kernel): float64 throughout (products of a float32 and a bf16 value are exact in float64): at most
+ gram_stats (conv_alg.hip gram_stats_kernel): float64 throughout (products of a float32 and a bf16 value are exact in float64): at most
    Cin + GRAM_STATS_OPS float64 roundings on |W| |G| |W|^T per output.
  temporal_pool_bwd_code_prod (tpool_bwd_prod.hip): g2 = bf16(sum of at most two routed bf16 gradients): exact in float64, rounded once --
    compared EXACTLY; prod as above over the stored g2.

@@ -145,6 +145,61 @@ def test_dispatch_probes_answer_as_documented(built):
     assert lib.adamml_clip_to_nhwc_four_pixel(4096, 8192, 6, 8, 6, 8, 8) == 0 and lib.adamml_clip_to_nhwc_four_pixel(4096, 8192, 6, 8, 3, 4, 4) == 0
 
 
+def _namespace_scope_prototypes(src):
+    """Names of the adamml_* functions DECLARED without a body at namespace scope of a C++ source (multi-line prototypes included):
+    statements that end in `;` outside every brace other than those of a namespace or a linkage specification."""
+    src = re.sub(r"//[^\n]*|/\*.*?\*/", " ", src, flags=re.S)
+    src = re.sub(r'"(?:\\.|[^"\\\n])*"', '""', src)
+    src = re.sub(r"^[ \t]*#[^\n]*", "", src, flags=re.M)
+    found, stmt, opened = [], "", []            # opened: per open brace, whether it is transparent (namespace / extern "C")
+    for ch in src:
+        if ch == "{":
+            opened.append(all(opened) and re.search(r'(\bnamespace\b[\w\s:]*|\bextern\s*"")\s*$', stmt) is not None)
+            stmt = ""
+        elif ch == "}":
+            opened.pop()
+            stmt = ""
+        elif ch == ";":
+            m = re.match(r'\s*(?:extern\s*""\s*)?[\w\s\*&:<>]*?\b(adamml_\w+)\s*\(.*\)\s*$', stmt, flags=re.S)
+            if all(opened) and m:
+                found.append(m.group(1))
+            stmt = ""
+        else:
+            stmt += ch
+    assert not opened
+    return found
+
+
+def test_internal_launchers_are_declared_once_in_the_internal_header():
+    """A launcher that one csrc/*.hip file defines and another calls is declared in csrc/conv_internal.h and nowhere else: no .hip file holds
+    a bodiless declaration of an adamml_* function (a prototype of its own drifts from the definition unnoticed: with C++ linkage the
+    mismatch compiles, links and fails when the library is loaded), and every .hip file that defines or calls a declared function includes
+    the header."""
+    import glob
+    csrc = os.path.join(ROOT, "adamml_amd", "csrc")
+    assert _namespace_scope_prototypes('namespace {\nint adamml_a(int x,\n  int y = 1);\n}\nextern "C" { int adamml_b(); }\n'
+                                       'int adamml_c(int v) { return adamml_a(v); }\n// int adamml_d();\n') == ["adamml_a", "adamml_b"]
+    declared = set(_namespace_scope_prototypes(open(os.path.join(csrc, "conv_internal.h")).read()))
+    assert len(declared) >= 30, sorted(declared)
+    sources = sorted(glob.glob(os.path.join(csrc, "*.hip")))
+    assert len(sources) >= 20
+    stray, missing, used = {}, [], set()
+    for path in sources:
+        src = open(path).read()
+        name = os.path.basename(path)
+        protos = _namespace_scope_prototypes(src)
+        if protos:
+            stray[name] = protos
+        code = re.sub(r"//[^\n]*|/\*.*?\*/", " ", src, flags=re.S)
+        names = set(re.findall(r"\b(adamml_\w+)\s*\(", code)) & declared
+        used |= names
+        if names and not re.search(r'^#include "conv_internal\.h"', src, flags=re.M):
+            missing.append(name)
+    assert not stray, "prototypes outside csrc/conv_internal.h: %s" % stray
+    assert not missing, "files that define or call a function of csrc/conv_internal.h without including it: %s" % missing
+    assert used == declared, "declared but neither defined nor called: %s" % sorted(declared - used)
+
+
 def test_environment_switch_registry_matches_the_code():
     """DESIGN.md appendix B is the complete registry of the ADAMML_* variables the product reads: the names adamml_amd/**/*.py takes from
     os.environ plus the names adamml_amd/csrc/* passes to getenv are exactly its operational and test-hook groups (the infrastructure
