@@ -154,7 +154,8 @@ class NetRT:
         self.tape = Tape(False)
         self.wgrad_stream = None     # optional side stream for the weight-gradient kernels (_on_wgrad_stream)
         self.wgrad_pending = collections.deque()      # (event, operand tensors) of weight-gradient launches still in flight
-        self.capture = None          # test aid: dict id(conv weight Parameter) -> list of raw conv outputs of this forward
+        self.capture = None          # test aid: dict id(conv weight Parameter) -> list of raw conv outputs of this forward; a test that
+        #                              seeds it with an "aux" dict also gets aux[id(returned Lazy)] = (code_t, mask_t, vec) of conv_bn_add, = idx of maxpool3x3s2
         self.pre_pending = 0         # next-conv results a fused kernel computed ahead (Lazy.next_pre) that no conv_bn has claimed yet
         self.pre_dropped = 0         # ... and were never claimed by the end of a forward (a silent fallback: tests assert 0)
         self.state_gen = 0           # bumped whenever BatchNorm tensors change behind torch's back (raw-pointer writes)
@@ -969,6 +970,8 @@ def conv_bn_add(rt, x, cs, bn, idn, act, idn_sole=False, tpool=0, next_cs=None):
                  ptr(idn.shift) if idn is not None else None, idn.gs if idn is not None else 0, act, ptr(out_t), ptr(mask_t))
         full_shape = tuple(out_t.shape)
     out = Lazy(out_t)
+    if rt.capture is not None and "aux" in rt.capture:           # (otherwise only reachable through the backward closures below)
+        rt.capture["aux"][id(out)] = (code_t if tpool else None, mask_t, vec)
     if not tpool:
         out.next_pre = nxt
         if nxt is not None:
@@ -1049,6 +1052,8 @@ def maxpool3x3s2(rt, x, sole_consumer=False):
     zsel = torch.empty_like(y) if fuse_bn else None
     call("adamml_maxpool2d_fwd", ptr(x.data), ptr(x.scale), ptr(x.shift), x.gs, x.act, ptr(y), ptr(idx), ptr(zsel), n // G, h, w, C, oh, ow, G)
     out = Lazy(y)
+    if rt.capture is not None and "aux" in rt.capture:
+        rt.capture["aux"][id(out)] = idx
     if rt.tape.need_grad:
         def bwd():
             g = out.grad

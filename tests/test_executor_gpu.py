@@ -1,0 +1,370 @@
+"""The host executor's fused training paths (adamml_amd/runtime.py) against a forced float64 replay of the forward that ran
+(tests/executor_ref.py; tests/test_executor_ref_cpu.py shows on the CPU that the bound used here catches seven kinds of executor defect).
+
+Every row drives one forward and one backward of a real model through its own `_run` with the executor entry points recorded, then
+  * checks the forward op by op, teacher-forced (each op's float64 result from the recorded inputs against the recorded output),
+  * checks every BatchNorm's vectors, running statistics and num_batches_tracked,
+  * checks every parameter gradient against  K e_emu + alg_term  (K = 4, shared with the CPU test),
+  * asserts a written expectation of the entry points that ran (hip.LaunchProfiler).
+Shapes are the smallest that reach the branch (the host-side *_supported / *_streams probes answer without a GPU)."""
+import collections
+import time
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from adamml_amd import hip  # noqa: E402
+from adamml_amd import runtime  # noqa: E402
+from adamml_amd.backbone import run_tape  # noqa: E402
+from tests import executor_ref as X  # noqa: E402
+from tests import elementwise_ref as E  # noqa: E402
+from tests import fused_ref as FR  # noqa: E402
+from tests.test_blocks_gpu import randomize  # noqa: E402
+
+DEV = "cuda"
+
+
+def gen(seed):
+    return torch.Generator().manual_seed(seed)
+
+
+def frames_input(n, hw, c, cpad, seed):
+    x = torch.zeros(n, hw, hw, cpad)
+    x[..., :c] = torch.randn(n, hw, hw, c, generator=gen(seed))
+    return x.to(torch.bfloat16)
+
+
+def randomize_convs(net, seed):
+    """He-scaled weights everywhere (the policy net's own initialisation is fan-out scaled and leaves tiny activations)"""
+    g = gen(seed)
+    for m in net.modules():
+        if isinstance(m, torch.nn.Conv2d):
+            fan = m.weight.shape[1] * m.weight.shape[2] * m.weight.shape[3]
+            m.weight.data = torch.randn(m.weight.shape, generator=g) * (2.0 / fan) ** 0.5
+        elif isinstance(m, torch.nn.Linear):
+            m.weight.data = torch.randn(m.weight.shape, generator=g) * (1.0 / m.weight.shape[1]) ** 0.5
+            m.bias.data = torch.randn(m.bias.shape, generator=g) * 0.1
+
+
+def cls_of(name, t):
+    return "fc" if name.startswith(("fc.", "classifier.")) else "conv" if t.dim() == 4 else "gamma" if name.endswith("weight") else "beta"
+
+
+def run_row(net, x, groups, out_cols, monkeypatch, frozen=(), label="", frozen_buffers=True):
+    """-> dict: names (Counter of entry points), log ([(entry point, args)]), rep (the float64 replay), res (id -> (err, bound)), ..."""
+    t0 = time.time()
+    net.to(DEV)
+    net.train()
+    if not frozen_buffers:                         # frozen BEFORE the gradient views are attached: their .grad is None, as in a real run
+        for m in frozen:
+            for p in m.parameters():
+                p.requires_grad_(False)
+    if getattr(net, "flat_owner", None) is not None:
+        net.flat_owner.ensure(torch.device(DEV, torch.cuda.current_device()))
+        net.flat_owner.ensure_grads()
+    else:                                          # (the policy trunk's flat buffers belong to the joint net around it)
+        for p in net.parameters():
+            p.grad = torch.zeros_like(p)
+    sentinel = {}
+    for m in (frozen if frozen_buffers else ()):
+        for p in m.parameters():
+            p.grad.fill_(0.25)
+            sentinel[id(p)] = p.grad               # the buffer itself: must stay bit for bit what it was
+            p.requires_grad_(False)
+    net.__dict__.pop("_plist", None)
+    named = list(net.named_parameters())
+    p64, names = X.leaves(named, torch.float64)
+    p32, _ = X.leaves(named, torch.float32)
+    run0 = X.running_of(net)
+    rec = X.Recorder()
+    rec.install(monkeypatch)
+    log = []
+    real_call = runtime.call
+    monkeypatch.setattr(runtime, "call", lambda name, *a: (log.append((name, a)), real_call(name, *a))[1])
+    x = x.to(DEV)
+    rt = net.rt
+    rt.capture = {"aux": {}}
+    hip.profiler = hip.LaunchProfiler()
+    try:
+        out, tape = net._run(x, groups, True)
+        assert tuple(out.shape) == tuple(out_cols(x)), (out.shape, out_cols(x))
+        g = X.bf(torch.randn(tuple(out.shape), generator=gen(77)))
+        run_tape(tape, g.to(DEV), net)
+        torch.cuda.synchronize()
+        counts = collections.Counter(r[0] for r in hip.profiler.records)
+    finally:
+        hip.profiler = None
+        rt.capture = None
+    t1 = time.time()
+    got = {id(p): p.grad.detach().cpu().clone() for _, p in named if p.requires_grad}
+    rep = X.Replay(rec.calls, groups, p64, run0)
+    ref = rep.backward(g)
+    pert = rep.backward_alg(g)
+    emu = X.Replay(rec.calls, groups, p32, X.running_of(net), dtype=torch.float32, round_grads=True)
+    bnd = X.bounds(ref, emu.backward(g), X.alg_terms(ref, pert))
+    res = X.compare(got, ref, bnd)
+    t2 = time.time()
+    # ---- report (profiles/executor_rows.md is written from these lines)
+    print("\nROW %s: hip %.2f s, replay + emulator %.2f s, %d ops" % (label, t1 - t0, t2 - t1, len(rec.calls)))
+    print("  entry points:", {k: v for k, v in sorted(counts.items())})
+    fw = collections.defaultdict(float)
+    for op, r in rep.fwd.values():
+        fw[op] = max(fw[op], r)
+    print("  forward max err/tol:", {k: round(v, 3) for k, v in fw.items()}, "vectors %.3f" % max(rep.vec_ratio.values()),
+          "undecided share %.5f" % rep.undecided_share())
+    cls = collections.defaultdict(lambda: [0.0, 0.0, 1.0])
+    for k, (e, b) in res.items():
+        n = names[k]
+        c = cls_of(n, got[k])
+        r = e / b if b > 0 else (0.0 if e == 0 else float("inf"))
+        cls[c][0] = max(cls[c][0], r)
+        cls[c][1] = max(cls[c][1], bnd[k][0])
+        cls[c][2] = min(cls[c][2], bnd[k][0])
+    print("  worst err/bound per class (e_emu min..max):", {c: "%.3f (%.2e..%.2e)" % (v[0], v[2], v[1]) for c, v in cls.items()})
+    # how much of the bound alg_term supplies
+    share = collections.defaultdict(float)
+    for k, (e, b) in res.items():
+        if b > 0:
+            share[cls_of(names[k], got[k])] = max(share[cls_of(names[k], got[k])], (b - X.K * bnd[k][0]) / b)
+    print("  largest alg_term / bound per class:", {c: round(v, 3) for c, v in share.items()})
+    # ---- forward, op by op
+    bad = {i: v for i, v in rep.fwd.items() if not v[1] <= 1.0}
+    assert not bad, "teacher-forced forward: %s" % bad
+    badv = {i: v for i, v in rep.vec_ratio.items() if not v <= 1.0}
+    assert not badv, "BatchNorm vectors: %s" % badv
+    assert rep.undecided_share() <= FR.UNDECIDED_CAP
+    # ---- running statistics
+    stat = 0.0
+    for m in net.modules():
+        if isinstance(m, torch.nn.BatchNorm2d) and id(m) in rep.stat_tol:
+            trm, trv = rep.stat_tol[id(m)]
+            stat = max(stat, E.vec_ratio(m.running_mean, rep.running[id(m)][0], trm), E.vec_ratio(m.running_var, rep.running[id(m)][1], trv))
+            assert int(m.num_batches_tracked) == rep.running[id(m)][2]
+    print("  running statistics max err/tol %.3f" % stat)
+    assert stat <= 1.0
+    # ---- gradients
+    k, wr = X.worst(res)
+    print("  worst gradient err/bound %.3f at %s" % (wr, names[k]))
+    over = {names[i]: (e, b) for i, (e, b) in res.items() if not e <= b}
+    assert not over, "gradients over the bound (err, bound): %s" % over
+    for i, buf in sentinel.items():
+        p = [q for _, q in named if id(q) == i][0]
+        assert p.grad is buf and bool((buf == 0.25).all()), "a frozen parameter's gradient buffer was touched: " + names[i]
+    if not frozen_buffers:                         # no algebraic, dual or weight-gradient path was handed (or made) a buffer for them
+        assert all(p.grad is None for m in frozen for p in m.parameters())
+    return dict(names=counts, log=log, rep=rep, res=res, pnames=names, net=net, ref=ref, got=got)
+
+
+def resnet(frames, **kw):
+    from adamml_amd.resnet import ResNet
+    torch.manual_seed(0)
+    net = ResNet(50, num_frames=frames, num_classes=11, dropout=0.0, **kw)
+    randomize(net, 1)
+    return net
+
+
+def resnet_row(net, hw, clips, groups, monkeypatch, label, prepare=None, frozen=(), rows=None, frozen_buffers=True):
+    T = net.orig_num_frames
+    if prepare is not None:
+        prepare(net)
+    x = frames_input(groups * clips * T, hw, 3, net.input_cpad(hw, hw), 5)
+    return run_row(net, x, groups, lambda xx: (rows or groups * clips, 11), monkeypatch, frozen=frozen(net) if callable(frozen) else frozen, label=label,
+                   frozen_buffers=frozen_buffers)
+
+
+def residual_bwd_channels(r):
+    """channel counts of the adamml_residual_bwd launches (its last three arguments are P, C, G)"""
+    return [a[-2] for n, a in r["log"] if n == "adamml_residual_bwd"]
+
+
+def test_resnet50_streaming_forms(monkeypatch):
+    """8 frames of 92 x 92, 8 clips in one group: layer 1 is 23 x 23 (33856 pixels per group), layer 2 12 x 12 with 4 frames (4608)."""
+    net = resnet(8)
+    r = resnet_row(net, 92, 8, 1, monkeypatch, "resnet50-streaming")
+    n = r["names"]
+    assert n["adamml_conv_fwd_bn_add_next"] == 2 and net.rt.pre_dropped == 0 and net.rt.pre_pending == 0
+    assert n["adamml_conv_fwd_bn_add_tpool"] >= 2
+    assert n["adamml_temporal_pool_bwd_code_prod"] == 1
+    assert n["adamml_conv_bwd_data_res_prod"] >= 1 and n["adamml_conv_bwd_data_res"] >= 1
+    assert n["adamml_alg_sumfix"] >= 1
+    assert n["adamml_maxpool2d_bwd_bn_apply"] == 1
+    assert n["adamml_temporal_pool_fwd"] == 1 and n["adamml_temporal_pool_bwd_res"] == 1      # layer 3 (2 frames): the unfused pool behind add_act
+    assert not [c for c in residual_bwd_channels(r) if c in (256, 512)]          # layers 1 and 2 never take the unfused residual backward
+
+
+def test_resnet50_tile_and_fallback_forms_grouped(monkeypatch):
+    """44 x 44, 2 clips of 4 frames per group, 3 groups: spatial sizes 11, 6, 3, 2 -- odd sizes, partial tiles, per-group statistics."""
+    net = resnet(4)
+    r = resnet_row(net, 44, 2, 3, monkeypatch, "resnet50-tile-g3")
+    n = r["names"]
+    assert n["adamml_conv_bwd_data_res_prod"] == 0           # refused by its workgroup term
+    assert n["adamml_conv_bwd_data_res"] >= 1 and n["adamml_conv_bwd_weight_grouped"] >= 1
+    assert n["adamml_conv_fwd_bn_add_tpool"] == 2 and n["adamml_conv_fwd_bn_add_next"] == 2 and net.rt.pre_dropped == 0
+
+
+def test_resnet50_without_t_stride(monkeypatch):
+    net = resnet(4, without_t_stride=True)
+    r = resnet_row(net, 44, 2, 1, monkeypatch, "resnet50-without-t-stride")
+    n = r["names"]
+    assert n["adamml_temporal_pool_fwd"] == 0 and n["adamml_conv_fwd_bn_add_tpool"] == 0
+    assert n["adamml_conv_fwd_bn_add"] + n["adamml_conv_fwd_bn_add_next"] == 7 and n["adamml_residual_bwd"] >= 1
+
+
+def test_resnet50_avg_pooling(monkeypatch):
+    """12 frames (avg pooling needs T >= 3 at every stage, as in the reference: 12, 6, 3), one clip"""
+    net = resnet(12, pooling_method="avg")
+    r = resnet_row(net, 44, 1, 1, monkeypatch, "resnet50-avg", rows=2)      # (3 frames pool to 2, and the head is told 3 // 2 = 1 per clip)
+    n = r["names"]
+    assert n["adamml_conv_fwd_bn_add_tpool"] == 0 and n["adamml_temporal_pool_fwd"] == 3
+    assert n["adamml_temporal_pool_bwd_res"] == 0 and n["adamml_temporal_pool_bwd"] == 3          # the fused form is refused for avg
+    assert n["adamml_residual_bwd"] >= 1
+
+
+def _zero_bn3(net):
+    net.layer1[1].bn3.weight.data.zero_()
+
+
+def _zero_row(net):
+    net.layer1[1].conv3.weight.data[5].zero_()
+
+
+def _cancelling_row(net):
+    """channel 9 of layer1.1.conv3 reads eight inputs that are nearly constant and positive (bn2: gamma 0.02, beta 2) with positive
+    weights: |mean| / std of its output is in the hundreds -- sum z^2 = diag(W G W^T) cancels against mean^2"""
+    b = net.layer1[1]
+    b.bn2.weight.data[:8], b.bn2.bias.data[:8] = 0.02, 2.0
+    w = b.conv3.weight.data
+    w[9] = 0
+    w[9, :8] = w[10, :8].abs() + 0.05
+
+
+@pytest.mark.parametrize("case", ["bn3-gamma-zero", "conv3-zero-row", "conv3-cancelling-row"])
+def test_resnet50_edge_parameters(monkeypatch, case):
+    net = resnet(4)
+    r = resnet_row(net, 44, 2, 3, monkeypatch, "resnet50-edge-" + case,
+                   prepare={"bn3-gamma-zero": _zero_bn3, "conv3-zero-row": _zero_row, "conv3-cancelling-row": _cancelling_row}[case])
+    # the reference's exact zeros are exact zeros in the result, element by element (a small non-zero value there would pass a rel-L2 bound)
+    nz, whole = 0, []
+    for k, v in r["ref"].items():
+        z = v == 0
+        nz += int(z.sum())
+        bad = int((r["got"][k][z] != 0).sum())
+        assert bad == 0, "%s: %d elements are exact zeros of the reference but not of the result" % (r["pnames"][k], bad)
+        if bool(z.all()):
+            whole.append(k)
+    print("  exact zeros of the reference: %d elements, %d whole tensors" % (nz, len(whole)))
+    assert nz > 0
+    zeros = whole
+    bn3 = net.layer1[1].bn3
+    vec = [c for c in r["rep"].calls if c.op == "conv_bn_add" and c.args["bn"] is bn3][0].aux[2].detach().cpu().double()
+    if case == "conv3-zero-row":
+        # channel 5 of conv3 sees no input: z = 0, variance 0, zhat = 0 -- dgamma[5] is an exact zero, invstd[5] = 1 / sqrt(eps) to the three
+        # float32 roundings of (eps, var + eps, rsqrt) and the mean exactly 0
+        names = {v: k for k, v in r["pnames"].items()}
+        assert float(r["ref"][names["layer1.1.bn3.weight"]][5]) == 0.0 and float(r["got"][names["layer1.1.bn3.weight"]][5]) == 0.0
+        assert bool((vec[:, 2, 5] == 0).all())
+        assert float((vec[:, 3, 5] - 1e-5 ** -0.5).abs().max()) <= 3 * 2.0 ** -23 * 1e-5 ** -0.5, vec[:, 3, 5]
+    if case == "bn3-gamma-zero":
+        assert {r["pnames"][k] for k in zeros} >= {"layer1.1.conv1.weight", "layer1.1.conv2.weight", "layer1.1.conv3.weight", "layer1.1.bn1.weight",
+                                                    "layer1.1.bn2.bias"}
+    if case == "conv3-cancelling-row":
+        assert float((vec[:, 2, 9].abs() * vec[:, 3, 9]).min()) > 30.0          # |mean| * invstd
+
+
+@pytest.mark.parametrize("buffers", ["grad-buffers-kept", "grad-none"])
+def test_resnet50_partly_frozen(monkeypatch, buffers):
+    """requires_grad = False on the stem and layer 1.  grad-buffers-kept: their gradient buffers stay bit for bit what they were;
+    grad-none: they have no buffer at all (frozen before the views are attached) and no path asks for one.  The rest meets the bound."""
+    net = resnet(4)
+    r = resnet_row(net, 44, 2, 3, monkeypatch, "resnet50-frozen-stem-layer1-" + buffers, frozen=lambda n: [n.conv1, n.bn1, n.layer1],
+                   frozen_buffers=buffers == "grad-buffers-kept")
+    assert not [k for k in r["res"] if r["pnames"][k].startswith(("conv1.", "bn1.", "layer1."))]
+    assert any(r["pnames"][k].startswith("layer2.0.") for k in r["res"])
+    n = r["names"]
+    assert n["adamml_conv_stem_bwd_weight"] == 0
+    # layer 1 cannot take conv_bn_add (its conv3 is frozen): conv_bn + add_act + the unfused temporal pool, whose backward finishes the add
+    assert n["adamml_temporal_pool_fwd"] == 2 and n["adamml_temporal_pool_bwd_res"] == 1
+    assert n["adamml_conv_bwd_data_alg"] == 4 and n["adamml_conv_bwd_data_dual"] == 4
+
+
+def _mobilenet_expectations(n):
+    assert n["adamml_dwconv_bwd_fused"] == 17                        # once per depthwise conv
+    assert n["adamml_dwconv_bwd_weight"] == 0 and n["adamml_dwconv_bwd_data"] == 0 and n["adamml_dwconv_bwd_data_bn"] == 0
+    assert n["adamml_conv_bwd_data_dual"] >= 17                      # every projection (and the expansions behind a fused depthwise backward)
+
+
+def test_sound_mobilenet_v2(monkeypatch):
+    from adamml_amd.sound_mobilenet_v2 import MobileNetV2
+    torch.manual_seed(0)
+    net = MobileNetV2(num_classes=11, input_channels=1, dropout=0.0)
+    randomize_convs(net, 2)
+    randomize(net, 3)
+    G, B = 2, 4
+    x = torch.randn(B, G, 64, 64, generator=gen(6))
+    r = run_row(net, x, G, lambda xx: (G * B, 11), monkeypatch, label="sound-mobilenetv2-g2")
+    assert r["names"]["adamml_conv_stem1_fwd"] == 1
+    _mobilenet_expectations(r["names"])
+
+
+def test_policy_mobilenet_v2(monkeypatch):
+    from adamml_amd.policy_net import MobileNetV2
+    torch.manual_seed(0)
+    net = MobileNetV2(num_frames=4, input_channels=3)
+    randomize_convs(net, 4)
+    randomize(net, 5)
+    G, clips = 2, 4
+    x = frames_input(G * clips * 4, 64, 3, 8, 7)
+    r = run_row(net, x, G, lambda xx: (G * clips * net.out_frames, 1280), monkeypatch, label="policy-mobilenetv2-g2")
+    assert r["names"]["adamml_temporal_pool_fwd"] == 2 and r["names"]["adamml_temporal_pool_bwd_res"] == 2
+    _mobilenet_expectations(r["names"])
+
+
+def test_eval_vector_cache_follows_raw_pointer_writes(monkeypatch):
+    """The eval-mode BatchNorm affines are cached on the modules, keyed on NetRT.state_gen: after a train step (adamml_bn_finalize rewrites
+    the running statistics through raw pointers) and after FlatSGD.step() (gamma / beta rewritten the same way) an eval forward must use
+    the NEW values -- its recorded affines and every op of its forward are checked against the float64 eval replay of the current state."""
+    from adamml_amd.optim import FlatSGD
+    net = resnet(4)
+    net.to(DEV)
+    net.flat_owner.ensure(torch.device(DEV, torch.cuda.current_device()))
+    rec = X.Recorder()
+    rec.install(monkeypatch)
+    x = frames_input(8, 44, 3, net.input_cpad(44, 44), 5).to(DEV)
+    net.rt.capture = {"aux": {}}
+
+    def eval_forward(what):
+        net.eval()
+        rec.calls = []
+        with torch.no_grad():
+            out, _ = net._run(x, 1, False)
+        torch.cuda.synchronize()
+        p64, _ = X.leaves(list(net.named_parameters()), torch.float64)
+        rep = X.Replay(rec.calls, 1, p64, X.running_of(net), training=False)
+        bad = {i: v for i, v in rep.fwd.items() if not v[1] <= 1.0}
+        print("eval %s: %d ops, forward max err/tol %.3f, affines %.3f" % (what, len(rec.calls), max(v[1] for v in rep.fwd.values()),
+                                                                            max(rep.vec_ratio.values())))
+        assert len(rep.vec_ratio) == 53 and max(rep.vec_ratio.values()) <= 1.0, (what, rep.vec_ratio)
+        assert not bad, (what, bad)
+        assert bool(torch.isfinite(out).all())
+        return out.detach().cpu().clone()
+
+    try:
+        a = eval_forward("fresh")
+        before = net.bn1.running_mean.detach().cpu().clone()
+        net.train()
+        net.flat_owner.ensure_grads()
+        rec.calls = []
+        out, tape = net._run(x, 1, True)
+        run_tape(tape, X.bf(torch.randn(2, 11, generator=gen(77))).to(DEV), net)
+        torch.cuda.synchronize()
+        assert not torch.equal(before, net.bn1.running_mean.detach().cpu())
+        b = eval_forward("after a train step")
+        assert not torch.equal(a, b)
+        FlatSGD(net.flat_owner, lr=1e-3).step()         # (a small step: eval mode does not renormalise, a large one overflows bf16 by layer 3)
+        assert all(bool(torch.isfinite(p).all()) for p in net.parameters())
+        c = eval_forward("after FlatSGD.step")
+        assert not torch.equal(b, c)
+    finally:
+        net.rt.capture = None
