@@ -307,17 +307,12 @@ def wgrad_workspace(desc, cin_true, device, depthwise=False, stem=False):
         need = load().adamml_dwconv_bwd_weight_workspace(ctypes.byref(desc))
     else:
         need = load().adamml_conv_bwd_weight_workspace(ctypes.byref(desc), cin_true)
-    key = (device, _stream())      # one scratch per stream: backbones run concurrently
-    buf = _wgrad_ws.get(key)
-    if buf is None or buf.numel() * 4 < need:
-        buf = torch.empty(max(need // 4 + 1, 1 << 20), dtype=torch.float32, device=device)
-        _wgrad_ws[key] = buf
-    return buf
+    return scratch(need, device)
 
 
 def scratch(nbytes, device):
     """The per-stream scratch buffer of wgrad_workspace(), grown to at least nbytes."""
-    key = (device, _stream())
+    key = (device, _stream())      # one scratch per stream: backbones run concurrently
     buf = _wgrad_ws.get(key)
     if buf is None or buf.numel() * 4 < nbytes:
         buf = torch.empty(max(nbytes // 4 + 1, 1 << 20), dtype=torch.float32, device=device)

@@ -290,6 +290,11 @@ def _bn_eval_vectors(rt, bn, C, device):
     return vec
 
 
+def _take_sums(rt, C):
+    """Zeroed accumulators [G][STAT_SLOTS][2C] for the BatchNorm-backward sums of a C-channel tensor."""
+    return rt.bwd_arena.take(rt.groups * 2 * C * STAT_SLOTS)
+
+
 def _bn_backward(rt, out, y, vec, bn, act, count, defer_apply=False):
     """Turns out.grad (w.r.t. the activated value) into dz (w.r.t. the raw conv output); accumulates dgamma/dbeta.
     defer_apply=True stops after the finalize step and returns (g, coef, aff): the caller's data-gradient kernel applies
@@ -299,40 +304,35 @@ def _bn_backward(rt, out, y, vec, bn, act, count, defer_apply=False):
     n, oh, ow, C = y.shape
     G = rt.groups
     P = n // G * oh * ow                    # pixels per group
-    if out.pool_grad is not None:
+    pool, out.pool_grad = out.pool_grad, None
+    if pool is not None:
         # the only consumer was a 3x3/2 max-pool: its routed gradient is recomputed from the pooled gradient and the
         # arg-max indices inside both BatchNorm-backward passes instead of being written and re-read twice
-        gy, idx, zsel, poh, pow_ = out.pool_grad
-        out.pool_grad = None
-        sums = rt.bwd_arena.take(G * 2 * C * STAT_SLOTS)
+        gy, idx, zsel, poh, pow_ = pool
+        sums = _take_sums(rt, C)
         # sums over the windows (g_y, z_sel): each pooled gradient lands on exactly one input pixel
         call("adamml_bn_bwd_reduce", ptr(gy), ptr(zsel), ptr(vec), act, ptr(sums), n // G * poh * pow_, C, G)
-        sums, nslots = rt.sync.reduce(sums, C, G)
-        coef = torch.empty(G, 3, C, dtype=torch.float32, device=y.device)
-        train_bn = bn.weight.requires_grad
-        call("adamml_bn_bwd_finalize", ptr(sums), nslots, G, float(count * rt.sync.world), ptr(bn.weight), ptr(vec),
-             ptr(bn.weight.grad) if train_bn else None, ptr(bn.bias.grad) if train_bn else None, ptr(coef), C, 1.0 / rt.sync.world)
-        dz = torch.empty_like(y)
-        call("adamml_maxpool2d_bwd_bn_apply", ptr(gy), ptr(idx), ptr(y), ptr(vec), act, ptr(coef), ptr(dz), n // G, oh, ow, C, poh, pow_, G)
-        return dz
-    if out.pre_sums is not None:            # reduction fused into the kernel that produced g (already activation-masked)
+    elif out.pre_sums is not None:          # reduction fused into the kernel that produced g (already activation-masked)
         sums, out.pre_sums = out.pre_sums, None
     else:
-        sums = rt.bwd_arena.take(G * 2 * C * STAT_SLOTS)
+        sums = _take_sums(rt, C)
         call("adamml_bn_bwd_reduce", ptr(g), ptr(y), ptr(vec), act, ptr(sums), P, C, G)
     sums, nslots = rt.sync.reduce(sums, C, G)
     coef = torch.empty(G, 3, C, dtype=torch.float32, device=y.device)
     train_bn = bn.weight.requires_grad
-    if defer_apply:
+    finalize = (ptr(sums), nslots, G, float(count * rt.sync.world), ptr(bn.weight), ptr(vec),
+                ptr(bn.weight.grad) if train_bn else None, ptr(bn.bias.grad) if train_bn else None, ptr(coef))
+    if defer_apply and pool is None:
         # the caller's data-gradient loader wants dz = A g + B z + C: finalize and the affine form in one launch
         aff = torch.empty(G, 3, C, dtype=torch.float32, device=y.device)
-        call("adamml_bn_bwd_finalize_affine", ptr(sums), nslots, G, float(count * rt.sync.world), ptr(bn.weight), ptr(vec),
-             ptr(bn.weight.grad) if train_bn else None, ptr(bn.bias.grad) if train_bn else None, ptr(coef), ptr(aff), C, 1.0 / rt.sync.world)
+        call("adamml_bn_bwd_finalize_affine", *finalize, ptr(aff), C, 1.0 / rt.sync.world)
         return g, coef, aff
-    call("adamml_bn_bwd_finalize", ptr(sums), nslots, G, float(count * rt.sync.world), ptr(bn.weight), ptr(vec),
-         ptr(bn.weight.grad) if train_bn else None, ptr(bn.bias.grad) if train_bn else None, ptr(coef), C, 1.0 / rt.sync.world)
+    call("adamml_bn_bwd_finalize", *finalize, C, 1.0 / rt.sync.world)
     dz = torch.empty_like(y)
-    call("adamml_bn_bwd_apply", ptr(g), ptr(y), ptr(vec), act, ptr(coef), ptr(dz), P, C, G)
+    if pool is not None:
+        call("adamml_maxpool2d_bwd_bn_apply", ptr(gy), ptr(idx), ptr(y), ptr(vec), act, ptr(coef), ptr(dz), n // G, oh, ow, C, poh, pow_, G)
+    else:
+        call("adamml_bn_bwd_apply", ptr(g), ptr(y), ptr(vec), act, ptr(coef), ptr(dz), P, C, G)
     return dz
 
 
@@ -352,6 +352,54 @@ def materialize(rt, x):
                 _accum_grad(x, g)          # d/d(activated value) is the same quantity on both sides
         rt.tape.record(bwd)
     return a
+
+
+def _conv_labels(cs, d):
+    """Profiler labels of one conv_bn layer -> (kern_f, role_f) of the forward launch and, for the backward (_ConvCall.lab),
+    (kern, kern_dual, kern_acc, kern_bn, role_b, role_bf, nar); nar, the narrow-kernel probes of a dense conv, also decides in _conv_backward."""
+    # device kernel behind adamml_conv_fwd / adamml_conv_bwd_data[_bn] for this layer (bench.py groups launches by it)
+    kern = kern_f = kern_dual = kern_acc = kern_bn = nar = None
+    if not cs.depthwise:
+        lib = hip.load()
+        kern = "conv3x3_c64_kernel" if lib.adamml_conv_fused_input_supported(byref(d)) else "conv_gemm_kernel"
+        # the narrow 1x1 layers of the MobileNetV2s run on the streaming kernels of csrc/conv1x1_narrow.hip
+        nar = [bool(lib.adamml_conv1x1_narrow_supported(byref(d), k)) for k in range(5)] if cs.kh * cs.kw == 1 else [False] * 5
+        kern_f = "conv1x1_narrow_fwd_kernel" if nar[0] else kern
+        kern_dual = "conv1x1_narrow_dgrad_kernel" if nar[2] else kern
+        kern_acc = ("conv1x1_narrow_dgrad_kernel" if nar[4] else kern, "conv1x1_narrow_fwd_kernel" if nar[3] else kern)      # [accumulating?]
+        kern_bn = "conv1x1_narrow_dgrad_kernel" if nar[4] else kern
+        if cs.kh * cs.kw == 1 and d.Cin >= 256:
+            # the wide 1x1 layers of ResNet layers 3-4 run on the activation-stationary streaming kernels of csrc/conv1x1_wide.hip
+            wide = [bool(lib.adamml_conv1x1_wide_supported(byref(d), k)) for k in (0, 3, 4)]
+            if wide[0]:
+                kern_f = "wide_all_kernel"
+            kern_acc = ("wide_all_kernel" if wide[2] else kern_acc[0], "wide_all_kernel" if wide[1] else kern_acc[1])
+    role_f = None if cs.depthwise else (R_KXK if cs.kh * cs.kw > 1 else R_1X1)
+    role_b = None if cs.depthwise else (R_KXK if (cs.kh * cs.kw > 1 or cs.stride > 1) else R_1X1)
+    role_bf = role_b if role_b != R_1X1 else R_FUSED          # data gradient with a fused BatchNorm-backward / residual epilogue
+    return kern_f, role_f, (kern, kern_dual, kern_acc, kern_bn, role_b, role_bf, nar)
+
+
+class _ConvCall:
+    """What the backward of one conv_bn / conv_bn_add call needs, complete when its forward creates it: x -> conv -> y (raw) -> out (lazy); the
+    decisions taken at forward time (sole_consumer, last_consumer, stem, lab[-1] = nar); the layer's algorithmic work and its labels
+    (_conv_labels) for the roofline report.  conv_bn_add: y is None (never stored), Gm / sv = the _gram_colsum of x its forward computed."""
+    __slots__ = ("rt", "x", "y", "out", "vec", "bn", "cs", "d", "count", "act", "sole_consumer", "last_consumer", "stem",
+                 "macs", "in_b", "out_b", "w_b", "lab", "Gm", "sv")
+
+    def __init__(self, rt, x, y, out, vec, bn, cs, d, count, act, sole_consumer, last_consumer, stem, macs, in_b, out_b, w_b, lab, Gm=None, sv=None):
+        self.rt, self.x, self.y, self.out, self.vec, self.bn, self.cs, self.d, self.count, self.act = rt, x, y, out, vec, bn, cs, d, count, act
+        self.sole_consumer, self.last_consumer, self.stem = sole_consumer, last_consumer, stem
+        self.macs, self.in_b, self.out_b, self.w_b, self.lab, self.Gm, self.sv = macs, in_b, out_b, w_b, lab, Gm, sv
+
+
+def _launch_conv_fwd(cs, d, x, y, stem, stats):
+    """The forward conv of lazy x into the raw tensor y; stats: the train-mode statistics accumulators its epilogue fills, or None."""
+    if stem:
+        call("adamml_conv_stem_fwd", byref(d), ptr(x.data), ptr(cs.w_stem), ptr(y), ptr(stats))
+    else:
+        call("adamml_dwconv_fwd" if cs.depthwise else "adamml_conv_fwd", byref(d), ptr(x.data), ptr(cs.w_fwd), ptr(x.scale), ptr(x.shift),
+             ptr(y), ptr(stats))
 
 
 def conv_bn(rt, x, cs, bn, act, sole_consumer=False, last_consumer=False):
@@ -384,7 +432,6 @@ def conv_bn(rt, x, cs, bn, act, sole_consumer=False, last_consumer=False):
     y = pre[1] if pre is not None else torch.empty(G * d.N, d.OH, d.OW, d.Cout, dtype=torch.bfloat16, device=dev)
     C = d.Cout
     count = d.N * d.OH * d.OW               # elements per channel per group
-    fwd = "adamml_dwconv_fwd" if cs.depthwise else "adamml_conv_fwd"
     stem = cs.stem and x.scale is None and hip.load().adamml_conv_stem_supported(byref(d))
     if x.shape[3] != cs.cin and not stem:
         raise RuntimeError("conv_bn: 4-channel pixels need the 7x7 stem kernel, which does not support this shape")
@@ -392,165 +439,185 @@ def conv_bn(rt, x, cs, bn, act, sole_consumer=False, last_consumer=False):
     macs = float(count) * G * C * cs.kh * cs.kw * (1 if cs.depthwise else cs.cin_true)
     in_b, out_b = 2.0 * G * d.N * d.H * d.W * cs.cin_true, 2.0 * G * count * C
     w_b = 2.0 * C * cs.kh * cs.kw * (1 if cs.depthwise else cs.cin_true)
-    # device kernel behind adamml_conv_fwd / adamml_conv_bwd_data[_bn] for this layer (bench.py groups launches by it)
-    kern = kern_f = kern_dual = kern_acc = kern_bn = None
-    if not cs.depthwise:
-        lib = hip.load()
-        kern = "conv3x3_c64_kernel" if lib.adamml_conv_fused_input_supported(byref(d)) else "conv_gemm_kernel"
-        # the narrow 1x1 layers of the MobileNetV2s run on the streaming kernels of csrc/conv1x1_narrow.hip
-        nar = [bool(lib.adamml_conv1x1_narrow_supported(byref(d), k)) for k in range(5)] if cs.kh * cs.kw == 1 else [False] * 5
-        kern_f = "conv1x1_narrow_fwd_kernel" if nar[0] else kern
-        kern_dual = "conv1x1_narrow_dgrad_kernel" if nar[2] else kern
-        kern_acc = ("conv1x1_narrow_dgrad_kernel" if nar[4] else kern, "conv1x1_narrow_fwd_kernel" if nar[3] else kern)      # [accumulating?]
-        kern_bn = "conv1x1_narrow_dgrad_kernel" if nar[4] else kern
-        if cs.kh * cs.kw == 1 and d.Cin >= 256:
-            # the wide 1x1 layers of ResNet layers 3-4 run on the activation-stationary streaming kernels of csrc/conv1x1_wide.hip
-            wide = [bool(lib.adamml_conv1x1_wide_supported(byref(d), k)) for k in (0, 3, 4)]
-            if wide[0]:
-                kern_f = "wide_all_kernel"
-            kern_acc = ("wide_all_kernel" if wide[2] else kern_acc[0], "wide_all_kernel" if wide[1] else kern_acc[1])
-    role_f = None if cs.depthwise else (R_KXK if cs.kh * cs.kw > 1 else R_1X1)
-    role_b = None if cs.depthwise else (R_KXK if (cs.kh * cs.kw > 1 or cs.stride > 1) else R_1X1)
-    role_bf = role_b if role_b != R_1X1 else R_FUSED          # data gradient with a fused BatchNorm-backward / residual epilogue
+    kern_f, role_f, lab = _conv_labels(cs, d)
     hip.next_meta = (2 * macs, in_b + out_b + w_b, "conv_stem_kernel" if stem else kern_f, role_f)
     if pre is not None:
         hip.next_meta = (0.0, 0.0)
-        vec = _bn_vectors(rt, bn, pre[2], count, C, dev)
-        rt.touched_bns.append(bn)
-    elif rt.training:
-        stats = rt.fwd_arena.take(G * 2 * C * STAT_SLOTS)
-        if stem:
-            call("adamml_conv_stem_fwd", byref(d), ptr(x.data), ptr(cs.w_stem), ptr(y), ptr(stats))
-        else:
-            call(fwd, byref(d), ptr(x.data), ptr(cs.w_fwd), ptr(x.scale), ptr(x.shift), ptr(y), ptr(stats))
-        vec = _bn_vectors(rt, bn, stats, count, C, dev)
-        rt.touched_bns.append(bn)
+        stats = pre[2]
     else:
-        if stem:
-            call("adamml_conv_stem_fwd", byref(d), ptr(x.data), ptr(cs.w_stem), ptr(y), None)
-        else:
-            call(fwd, byref(d), ptr(x.data), ptr(cs.w_fwd), ptr(x.scale), ptr(x.shift), ptr(y), None)
-        vec = _bn_eval_vectors(rt, bn, C, dev)
+        stats = rt.fwd_arena.take(G * 2 * C * STAT_SLOTS) if rt.training else None
+        _launch_conv_fwd(cs, d, x, y, stem, stats)
     if rt.capture is not None:
         rt.capture.setdefault(id(cs.weight), []).append(y)
     if rt.training:
+        vec = _bn_vectors(rt, bn, stats, count, C, dev)
+        rt.touched_bns.append(bn)
         out = Lazy(y, vec[0, 0], vec[0, 1], act, gs=4 * C)
         out.vec = vec
         out.alg = bool(rt.tape.need_grad and act == ACT_NONE and not cs.depthwise and not stem and x.requires_grad
                        and cs.weight.requires_grad and _alg_supported(cs, d))
     else:
+        vec = _bn_eval_vectors(rt, bn, C, dev)
         out = Lazy(y, vec[0], vec[1], act)
     if rt.tape.need_grad:
-        def bwd():
-            if out.grad is None and out.pool_grad is None:
-                return
-            if out.alg and out.pool_grad is None:
-                _conv1x1_backward_alg(rt, out, x, y, vec, bn, cs, d, count, sole_consumer, macs, in_b, out_b, w_b, kern)
-                return
-            if act == ACT_NONE and not cs.depthwise and not stem and out.pool_grad is None and x.requires_grad \
-                    and rt.training and hip.load().adamml_conv_bwd_data_dual_supported(byref(d)):
-                _conv1x1_backward_dual(rt, out, x, y, vec, bn, cs, d, count, sole_consumer, macs, in_b, out_b, w_b, kern_dual)
-                return
-            if act != ACT_NONE and out.pre_sums is not None and not cs.depthwise and not stem and out.pool_grad is None \
-                    and x.requires_grad and rt.training and cs.kh * cs.kw == 1 and nar[2]:
-                # expansion conv of an inverted residual (round 6): its gradient arrives ALREADY masked by its ReLU6 (the depthwise conv's fused
-                # backward applied the mask and accumulated the sums), so the BatchNorm-backward apply is the same affine A g' + B z + C as for
-                # a linear BatchNorm and folds into the narrow streaming data gradient's loader the same way
-                _conv1x1_backward_dual(rt, out, x, y, vec, bn, cs, d, count, sole_consumer, macs, in_b, out_b, w_b, kern_dual)
-                return
-            if cs.depthwise and out.pool_grad is None and out.pre_sums is not None and rt.training and sole_consumer \
-                    and cs.weight.requires_grad and x.requires_grad and x.grad is None and x.src is None and x.vec is not None \
-                    and x.pre_sums is None and x.scale is not None and x.scale.data_ptr() == x.vec.data_ptr() \
-                    and hip.load().adamml_dwconv_bwd_fused_supported(byref(d)):
-                # g is already masked by this conv's activation (out.pre_sums: the projection's data gradient did that), so
-                # dz = A g + B z + C in the loader; apply + weight gradient + data gradient (mask / sums of the expansion) in one pass
-                g, coef, aff = _bn_backward(rt, out, y, vec, bn, act, count, defer_apply=True)
-                x.grad = torch.empty_like(x.data)
-                sums = rt.bwd_arena.take(G * 2 * d.Cin * STAT_SLOTS)
-                ws = hip.scratch(hip.load().adamml_dwconv_bwd_fused_workspace(byref(d)), dev)
-                hip.next_meta = (4 * macs, 2 * in_b + 2 * out_b + 2 * w_b, "dwconv_bwd_fused_kernel", None)
-                call("adamml_dwconv_bwd_fused", byref(d), ptr(g), ptr(y), ptr(aff), ptr(cs.w_fwd), ptr(x.data), ptr(x.vec), x.act, ptr(x.grad),
-                     ptr(sums), ptr(cs.weight.grad), ptr(ws), ws.numel() * 4)
-                x.pre_sums = sums
-                return
-            dz = _bn_backward(rt, out, y, vec, bn, act, count)
-            if cs.weight.requires_grad:
-                with _on_wgrad_stream(rt, (dz, x.data, x.scale)):
-                    hip.next_meta = (2 * macs, in_b + out_b + 2 * w_b, None, None if cs.depthwise else R_WGRAD)
-                    if cs.depthwise:
-                        ws = hip.wgrad_workspace(d, 0, dz.device, depthwise=True)
-                        call("adamml_dwconv_bwd_weight", byref(d), ptr(dz), ptr(x.data), ptr(x.scale), ptr(x.shift), ptr(cs.weight.grad),
-                             ptr(ws), ws.numel() * 4)
-                    elif stem:
-                        ws = hip.wgrad_workspace(d, cs.cin_true, dz.device, stem=True)
-                        call("adamml_conv_stem_bwd_weight", byref(d), ptr(dz), ptr(x.data), ptr(cs.weight.grad), cs.cin_true, ptr(ws),
-                             ws.numel() * 4)
-                    else:
-                        ws = hip.wgrad_workspace(d, cs.cin_true, dz.device)
-                        call("adamml_conv_bwd_weight", byref(d), ptr(dz), ptr(x.data), ptr(x.scale), ptr(x.shift),
-                             ptr(cs.weight.grad), cs.cin_true, ptr(ws), ws.numel() * 4)
-            if x.requires_grad:
-                acc = 1
-                if x.grad is None:
-                    x.grad = torch.empty_like(x.data)
-                    acc = 0
-                hip.next_meta = (2 * macs, in_b * (1 + acc) + out_b + w_b, kern if cs.depthwise else kern_acc[0 if acc else 1], role_b)
-                tgt = x.src if x.src is not None else x
-                if cs.depthwise and sole_consumer and acc == 0 and tgt.vec is not None and tgt.pre_sums is None \
-                        and hip.load().adamml_dwconv_bwd_data_bn_supported(byref(d)):
-                    # the expansion's BatchNorm-backward sums come out of this data gradient (mask applied here): no reduction pass
-                    sums = rt.bwd_arena.take(G * 2 * d.Cin * STAT_SLOTS)
-                    call("adamml_dwconv_bwd_data_bn", byref(d), ptr(dz), ptr(cs.w_fwd), ptr(x.grad), ptr(tgt.data), ptr(tgt.vec), tgt.act, ptr(sums))
-                    tgt.pre_sums = sums
-                elif cs.depthwise:
-                    call("adamml_dwconv_bwd_data", byref(d), ptr(dz), ptr(cs.w_fwd), ptr(x.grad), acc)
-                elif last_consumer and _residual_fusable(x, d):
-                    z, idn, ract, idn_sole, rmask = x.res
-                    fb = idn is not None and idn_sole and idn.requires_grad and idn.vec is not None and idn.grad is None
-                    sa = rt.bwd_arena.take(G * 2 * d.Cin * STAT_SLOTS)
-                    sb = rt.bwd_arena.take(G * 2 * d.Cin * STAT_SLOTS) if fb else None
-                    fb_alg = fb and idn.alg               # the downsample BatchNorm shares sum(g'); its second moment comes from g'^T a too
-                    hip.next_meta = (2 * macs, in_b * ((1.0625 if rmask is not None else 2) + (0 if z.alg else 1) + acc
-                                                       + (1 if (fb and not (fb and idn.alg)) else 0)) + out_b + w_b, kern, R_FUSED)
-                    fbk = fb and not fb_alg
-                    ain = z.alg_in
-                    if (z.alg and ain is not None and (not fb or fb_alg) and acc == 1 and rmask is not None and ain[0].data is not None
-                            and hip.load().adamml_conv_bwd_data_res_prod_supported(byref(d), ain[1].Cin)):
-                        # the product g'^T a of the algebraic backward of the conv that produced z (its input a = ain[0]) is accumulated
-                        # from the gradient tile inside this kernel: no separate pass over g' and a
-                        xa = ain[0]
-                        z.prod = torch.empty(G, d.Cin, ain[1].Cin, dtype=torch.float32, device=dz.device)
-                        need = hip.load().adamml_conv_bwd_data_res_prod_workspace(byref(d))
-                        wsp = hip.scratch(need, dz.device)
-                        # (layer 1: the barrier-free streaming kernel of csrc/res_prod_stream.hip; its workspace is sized for it)
-                        kern_rp = "res_prod_stream_kernel" if hip.load().adamml_conv_bwd_data_res_prod_streams(byref(d), ain[1].Cin) else kern
-                        hip.next_meta = (2 * macs + 2.0 * G * d.N * d.H * d.W * d.Cin * ain[1].Cin, in_b * 2.0625 + out_b + w_b + 2.0 * G * d.N * d.H * d.W * ain[1].Cin, kern_rp, R_FUSED)
-                        call("adamml_conv_bwd_data_res_prod", byref(d), ptr(dz), ptr(cs.w_dgrad), ptr(x.grad), ptr(rmask), ract, ptr(sa), ptr(xa.data),
-                             ptr(xa.scale), ptr(xa.shift), xa.act, xa.gs, ain[1].Cin, ptr(z.prod), ptr(wsp), wsp.numel() * 4)
-                    else:
-                        if acc == 1 and rmask is not None and z.alg and hip.load().adamml_conv_bwd_data_res_streams(byref(d)):
-                            hip.next_meta = hip.next_meta[:2] + ("res_prod_stream_kernel", R_FUSED)       # (layer 2: csrc/res_prod_stream.hip)
-                        call("adamml_conv_bwd_data_res", byref(d), ptr(dz), ptr(cs.w_dgrad), ptr(x.grad), acc, ptr(x.data), ptr(rmask), ract,
-                             None if z.alg else ptr(z.data), ptr(z.vec), ptr(sa), ptr(idn.data) if fbk else None, ptr(idn.vec) if fbk else None,
-                             ptr(sb) if fbk else None)
-                    z.pre_sums = sa
-                    z.sums_partial = z.alg
-                    if fb:
-                        if fb_alg:
-                            call("adamml_copy2d", ptr(sb), 2 * d.Cin * 8, ptr(sa), 2 * d.Cin * 8, d.Cin * 8, G * STAT_SLOTS)       # the sum(g') columns
-                            idn.sums_partial = True
-                        idn.pre_sums = sb
-                    x.res_done = True
-                elif sole_consumer and acc == 0 and tgt.vec is not None and tgt.pre_sums is None:
-                    sums = rt.bwd_arena.take(G * 2 * d.Cin * STAT_SLOTS)
-                    hip.next_meta = (2 * macs, 2 * in_b + out_b + w_b, kern_bn, role_bf)
-                    call("adamml_conv_bwd_data_bn", byref(d), ptr(dz), ptr(cs.w_dgrad), ptr(x.grad), ptr(tgt.data), ptr(tgt.vec),
-                         tgt.act, ptr(sums))
-                    tgt.pre_sums = sums
-                else:
-                    call("adamml_conv_bwd_data", byref(d), ptr(dz), ptr(cs.w_dgrad), ptr(x.grad), acc)
-        rt.tape.record(bwd)
+        c = _ConvCall(rt, x, y, out, vec, bn, cs, d, count, act, sole_consumer, last_consumer, stem, macs, in_b, out_b, w_b, lab)
+        rt.tape.record(lambda: _conv_backward(c))
     return out
+
+
+def _conv_backward(c):
+    """Which backward form the conv of one conv_bn call takes: the first arm whose predicate holds."""
+    rt, x, out, cs, d = c.rt, c.x, c.out, c.cs, c.d
+    if out.grad is None and out.pool_grad is None:
+        return
+    if out.alg and out.pool_grad is None:
+        _conv1x1_backward_alg(c, c.y)
+    elif c.act == ACT_NONE and not cs.depthwise and not c.stem and out.pool_grad is None and x.requires_grad \
+            and rt.training and hip.load().adamml_conv_bwd_data_dual_supported(byref(d)):
+        _conv1x1_backward_dual(c)
+    elif c.act != ACT_NONE and out.pre_sums is not None and not cs.depthwise and not c.stem and out.pool_grad is None \
+            and x.requires_grad and rt.training and cs.kh * cs.kw == 1 and c.lab[-1][2]:
+        # expansion conv of an inverted residual (round 6): its gradient arrives ALREADY masked by its ReLU6 (the depthwise conv's fused
+        # backward applied the mask and accumulated the sums), so the BatchNorm-backward apply is the same affine A g' + B z + C as for
+        # a linear BatchNorm and folds into the narrow streaming data gradient's loader the same way
+        _conv1x1_backward_dual(c)
+    elif cs.depthwise and out.pool_grad is None and out.pre_sums is not None and rt.training and c.sole_consumer \
+            and cs.weight.requires_grad and x.requires_grad and x.grad is None and x.src is None and x.vec is not None \
+            and x.pre_sums is None and x.scale is not None and x.scale.data_ptr() == x.vec.data_ptr() \
+            and hip.load().adamml_dwconv_bwd_fused_supported(byref(d)):
+        _conv_backward_dw_fused(c)
+    else:
+        _conv_backward_plain(c)
+
+
+def _conv_backward_dw_fused(c):
+    rt, x, cs, d = c.rt, c.x, c.cs, c.d
+    # g is already masked by this conv's activation (out.pre_sums: the projection's data gradient did that), so
+    # dz = A g + B z + C in the loader; apply + weight gradient + data gradient (mask / sums of the expansion) in one pass
+    g, coef, aff = _bn_backward(rt, c.out, c.y, c.vec, c.bn, c.act, c.count, defer_apply=True)
+    x.grad = torch.empty_like(x.data)
+    sums = _take_sums(rt, d.Cin)
+    ws = hip.scratch(hip.load().adamml_dwconv_bwd_fused_workspace(byref(d)), x.data.device)
+    hip.next_meta = (4 * c.macs, 2 * c.in_b + 2 * c.out_b + 2 * c.w_b, "dwconv_bwd_fused_kernel", None)
+    call("adamml_dwconv_bwd_fused", byref(d), ptr(g), ptr(c.y), ptr(aff), ptr(cs.w_fwd), ptr(x.data), ptr(x.vec), x.act, ptr(x.grad),
+         ptr(sums), ptr(cs.weight.grad), ptr(ws), ws.numel() * 4)
+    x.pre_sums = sums
+
+
+def _conv_backward_plain(c):
+    """The unfused form: BatchNorm backward into dz, the weight gradient from dz, then the data gradient that fits the conv and x."""
+    x, cs, d = c.x, c.cs, c.d
+    kern, _, kern_acc, kern_bn, role_b, role_bf, _ = c.lab
+    dz = _bn_backward(c.rt, c.out, c.y, c.vec, c.bn, c.act, c.count)
+    if cs.weight.requires_grad:
+        _launch_wgrad(c, dz)
+    if not x.requires_grad:
+        return
+    if cs.depthwise:
+        # (the depthwise copy of _claim_grad_and_sums stays here: its kernel has a probe of its own and no accumulating form)
+        acc = _claim_grad(x)
+        hip.next_meta = (2 * c.macs, c.in_b * (1 + acc) + c.out_b + c.w_b, kern, role_b)
+        tgt = x.src if x.src is not None else x
+        if c.sole_consumer and acc == 0 and tgt.vec is not None and tgt.pre_sums is None \
+                and hip.load().adamml_dwconv_bwd_data_bn_supported(byref(d)):
+            # the expansion's BatchNorm-backward sums come out of this data gradient (mask applied here): no reduction pass
+            sums = _take_sums(c.rt, d.Cin)
+            call("adamml_dwconv_bwd_data_bn", byref(d), ptr(dz), ptr(cs.w_fwd), ptr(x.grad), ptr(tgt.data), ptr(tgt.vec), tgt.act, ptr(sums))
+            tgt.pre_sums = sums
+        else:
+            call("adamml_dwconv_bwd_data", byref(d), ptr(dz), ptr(cs.w_fwd), ptr(x.grad), acc)
+    elif c.last_consumer and _residual_fusable(x, d):
+        _dgrad_finish_residual(c, dz, _claim_grad(x))
+    else:
+        acc, sums, tail = _claim_grad_and_sums(c)
+        if sums is not None:
+            hip.next_meta = (2 * c.macs, 2 * c.in_b + c.out_b + c.w_b, kern_bn, role_bf)
+            call("adamml_conv_bwd_data_bn", byref(d), ptr(dz), ptr(cs.w_dgrad), ptr(x.grad), *tail)
+        else:
+            hip.next_meta = (2 * c.macs, c.in_b * (1 + acc) + c.out_b + c.w_b, kern_acc[0 if acc else 1], role_b)
+            call("adamml_conv_bwd_data", byref(d), ptr(dz), ptr(cs.w_dgrad), ptr(x.grad), acc)
+
+
+def _launch_wgrad(c, dz):
+    """The weight gradient of a conv (depthwise / 7x7 stem / dense) from dz and its lazy input, on the weight-gradient stream."""
+    x, cs, d = c.x, c.cs, c.d
+    with _on_wgrad_stream(c.rt, (dz, x.data, x.scale)):
+        hip.next_meta = (2 * c.macs, c.in_b + c.out_b + 2 * c.w_b, None, None if cs.depthwise else R_WGRAD)
+        if cs.depthwise:
+            ws = hip.wgrad_workspace(d, 0, dz.device, depthwise=True)
+            call("adamml_dwconv_bwd_weight", byref(d), ptr(dz), ptr(x.data), ptr(x.scale), ptr(x.shift), ptr(cs.weight.grad),
+                 ptr(ws), ws.numel() * 4)
+        elif c.stem:
+            ws = hip.wgrad_workspace(d, cs.cin_true, dz.device, stem=True)
+            call("adamml_conv_stem_bwd_weight", byref(d), ptr(dz), ptr(x.data), ptr(cs.weight.grad), cs.cin_true, ptr(ws),
+                 ws.numel() * 4)
+        else:
+            ws = hip.wgrad_workspace(d, cs.cin_true, dz.device)
+            call("adamml_conv_bwd_weight", byref(d), ptr(dz), ptr(x.data), ptr(x.scale), ptr(x.shift),
+                 ptr(cs.weight.grad), cs.cin_true, ptr(ws), ws.numel() * 4)
+
+
+def _claim_grad(x):
+    """-> acc.  0: x.grad was unclaimed, it is allocated here and the data gradient overwrites it; 1: the data gradient adds to it."""
+    if x.grad is None:
+        x.grad = torch.empty_like(x.data)
+        return 0
+    return 1
+
+
+def _claim_grad_and_sums(c):
+    """Claims x.grad for a dense data gradient -> (acc, sums, tail).  sums: the kernel also produces the BatchNorm-backward sums of x's
+    producer tgt (mask applied in its epilogue, no reduction pass over g and z), or None; tail: its trailing arguments (z, vec, act,
+    sums), null without sums."""
+    x = c.x
+    acc = _claim_grad(x)
+    tgt = x.src if x.src is not None else x
+    if not (c.sole_consumer and acc == 0 and tgt.vec is not None and tgt.pre_sums is None):
+        return acc, None, (None, None, 0, None)
+    sums = tgt.pre_sums = _take_sums(c.rt, c.d.Cin)
+    return acc, sums, (ptr(tgt.data), ptr(tgt.vec), tgt.act, ptr(sums))
+
+
+def _dgrad_finish_residual(c, dz, acc):
+    """Data gradient of the last consumer of a residual add's output x that also finishes the add's backward (conv_bn, last_consumer)."""
+    rt, x, cs, d = c.rt, c.x, c.cs, c.d
+    G, macs, in_b, out_b, w_b, kern = rt.groups, c.macs, c.in_b, c.out_b, c.w_b, c.lab[0]
+    z, idn, ract, idn_sole, rmask = x.res
+    fb = idn is not None and idn_sole and idn.requires_grad and idn.vec is not None and idn.grad is None
+    sa = _take_sums(rt, d.Cin)
+    sb = _take_sums(rt, d.Cin) if fb else None
+    fb_alg = fb and idn.alg               # the downsample BatchNorm shares sum(g'); its second moment comes from g'^T a too
+    hip.next_meta = (2 * macs, in_b * ((1.0625 if rmask is not None else 2) + (0 if z.alg else 1) + acc
+                                       + (1 if (fb and not (fb and idn.alg)) else 0)) + out_b + w_b, kern, R_FUSED)
+    fbk = fb and not fb_alg
+    ain = z.alg_in
+    if (z.alg and ain is not None and (not fb or fb_alg) and acc == 1 and rmask is not None and ain[0].data is not None
+            and hip.load().adamml_conv_bwd_data_res_prod_supported(byref(d), ain[1].Cin)):
+        # the product g'^T a of the algebraic backward of the conv that produced z (its input a = ain[0]) is accumulated
+        # from the gradient tile inside this kernel: no separate pass over g' and a
+        xa = ain[0]
+        z.prod = torch.empty(G, d.Cin, ain[1].Cin, dtype=torch.float32, device=dz.device)
+        need = hip.load().adamml_conv_bwd_data_res_prod_workspace(byref(d))
+        wsp = hip.scratch(need, dz.device)
+        # (layer 1: the barrier-free streaming kernel of csrc/res_prod_stream.hip; its workspace is sized for it)
+        kern_rp = "res_prod_stream_kernel" if hip.load().adamml_conv_bwd_data_res_prod_streams(byref(d), ain[1].Cin) else kern
+        hip.next_meta = (2 * macs + 2.0 * G * d.N * d.H * d.W * d.Cin * ain[1].Cin, in_b * 2.0625 + out_b + w_b + 2.0 * G * d.N * d.H * d.W * ain[1].Cin, kern_rp, R_FUSED)
+        call("adamml_conv_bwd_data_res_prod", byref(d), ptr(dz), ptr(cs.w_dgrad), ptr(x.grad), ptr(rmask), ract, ptr(sa), ptr(xa.data),
+             ptr(xa.scale), ptr(xa.shift), xa.act, xa.gs, ain[1].Cin, ptr(z.prod), ptr(wsp), wsp.numel() * 4)
+    else:
+        if acc == 1 and rmask is not None and z.alg and hip.load().adamml_conv_bwd_data_res_streams(byref(d)):
+            hip.next_meta = hip.next_meta[:2] + ("res_prod_stream_kernel", R_FUSED)       # (layer 2: csrc/res_prod_stream.hip)
+        call("adamml_conv_bwd_data_res", byref(d), ptr(dz), ptr(cs.w_dgrad), ptr(x.grad), acc, ptr(x.data), ptr(rmask), ract,
+             None if z.alg else ptr(z.data), ptr(z.vec), ptr(sa), ptr(idn.data) if fbk else None, ptr(idn.vec) if fbk else None,
+             ptr(sb) if fbk else None)
+    z.pre_sums = sa
+    z.sums_partial = z.alg
+    if fb:
+        if fb_alg:
+            call("adamml_copy2d", ptr(sb), 2 * d.Cin * 8, ptr(sa), 2 * d.Cin * 8, d.Cin * 8, G * STAT_SLOTS)       # the sum(g') columns
+            idn.sums_partial = True
+        idn.pre_sums = sb
+    x.res_done = True
 
 
 def stem1_supported(cs, x):
@@ -682,12 +749,14 @@ def _alg_supported(cs, d):
             and d.Cout % 32 == 0 and 2 * d.Cin <= d.Cout <= ALG_MAX_COUT)
 
 
-def _conv1x1_backward_alg(rt, out, x, y, vec, bn, cs, d, count, sole_consumer, macs, in_b, out_b, w_b, kern, Gm=None, sv=None):
+def _conv1x1_backward_alg(c, y):
     """Backward of z = W a (1x1) followed by a linear train-mode BatchNorm WITHOUT touching z or dz (include/adamml_hip.h,
     "algebraic BatchNorm backward"): with dz = A g' + B z + C per channel,
         dx = (W^T diag(A)) g' + (W^T diag(B) W) a + W^T C,      dW = A (.) (g'^T a) + B (.) (W G) + C (x) s,  G = a^T a, s = sum a.
     The products over pixels (g'^T a, a^T a, sum a) run on the weight-gradient stream; the data gradient is one GEMM over the
-    concatenated input [g' | a] with per-group weights."""
+    concatenated input [g' | a] with per-group weights.  c.Gm / c.sv: G and s where the forward already computed them (conv_bn_add)."""
+    rt, out, x, vec, cs, d, kern = c.rt, c.out, c.x, c.vec, c.cs, c.d, c.lab[0]
+    macs, in_b, out_b, w_b = c.macs, c.in_b, c.out_b, c.w_b
     G = rt.groups
     Cout, Cin = d.Cout, d.Cin
     dev = y.device
@@ -707,12 +776,10 @@ def _conv1x1_backward_alg(rt, out, x, y, vec, bn, cs, d, count, sole_consumer, m
         if out.prod is None:
             products()
         call("adamml_alg_sumfix", ptr(w2), ptr(P), ptr(vec), ptr(out.pre_sums), Cout, Cin, G)
-    elif out.prod is not None:
-        pass
-    else:
+    elif out.prod is None:
         with _on_wgrad_stream(rt, (g0, x.data, x.scale)):
             products()
-    g, coef, aff = _bn_backward(rt, out, y, vec, bn, ACT_NONE, count, defer_apply=True)
+    g, coef, aff = _bn_backward(rt, out, y, vec, c.bn, ACT_NONE, c.count, defer_apply=True)
     # ---- data gradient (main stream)
     w_alg = torch.empty(G, Cin, Cout + Cin, dtype=torch.bfloat16, device=dev)
     cadd = torch.empty(G, Cin, dtype=torch.float32, device=dev)
@@ -723,25 +790,15 @@ def _conv1x1_backward_alg(rt, out, x, y, vec, bn, cs, d, count, sole_consumer, m
         wb = (w2d.unsqueeze(1) * aff[:, 1].t().unsqueeze(2)).reshape(Cout, G * Cin)
         m_pre = gemm_f32(wb, w2d, trans_a=True, trans_b=False)
     call("adamml_alg_pack", ptr(w2), ptr(aff), ptr(m_pre), ptr(w_alg), ptr(cadd), Cout, Cin, G)
-    acc = 1
-    if x.grad is None:
-        x.grad = torch.empty_like(x.data)
-        acc = 0
-    tgt = x.src if x.src is not None else x
+    acc, sums, tail = _claim_grad_and_sums(c)
     if (Cout, Cin) == (256, 64):
         kern = "alg_stream_kernel"            # csrc/conv1x1_stream.hip serves this shape (bench.py groups launches by device kernel)
-    if sole_consumer and acc == 0 and tgt.vec is not None and tgt.pre_sums is None:
-        sums = rt.bwd_arena.take(G * 2 * Cin * STAT_SLOTS)
-        hip.next_meta = (2 * macs, 3 * in_b + out_b + w_b, kern, R_FUSED)
-        call("adamml_conv_bwd_data_alg", byref(d), ptr(g), ptr(x.data), ptr(x.scale), ptr(x.shift), ptr(w_alg), ptr(cadd), ptr(x.grad), 0,
-             ptr(tgt.data), ptr(tgt.vec), tgt.act, ptr(sums))
-        tgt.pre_sums = sums
-    else:
-        hip.next_meta = (2 * macs, in_b * (2 + acc) + out_b + w_b, kern, R_FUSED)
-        call("adamml_conv_bwd_data_alg", byref(d), ptr(g), ptr(x.data), ptr(x.scale), ptr(x.shift), ptr(w_alg), ptr(cadd), ptr(x.grad), acc,
-             None, None, 0, None)
+    hip.next_meta = (2 * macs, in_b * (2 + acc + (0 if sums is None else 1)) + out_b + w_b, kern, R_FUSED)
+    call("adamml_conv_bwd_data_alg", byref(d), ptr(g), ptr(x.data), ptr(x.scale), ptr(x.shift), ptr(w_alg), ptr(cadd), ptr(x.grad), acc,
+         *tail)
     # ---- weight gradient (weight-gradient stream): products over the pixels, then the per-group combination
     with _on_wgrad_stream(rt, (g, x.data, x.scale, aff, P)):
+        Gm, sv = c.Gm, c.sv
         if Gm is None:            # (conv_bn_add computed the Gram matrix and the column sums in the forward pass: its statistics)
             Gm, sv = _gram_colsum(rt, x, d)
         wg_pre = None
@@ -751,37 +808,22 @@ def _conv1x1_backward_alg(rt, out, x, y, vec, bn, cs, d, count, sole_consumer, m
         call("adamml_alg_wgrad_combine", ptr(w2), ptr(aff), ptr(P), ptr(Gm), ptr(wg_pre), ptr(sv), ptr(cs.weight.grad), Cout, Cin, G)
 
 
-def _conv1x1_backward_dual(rt, out, x, y, vec, bn, cs, d, count, sole_consumer, macs, in_b, out_b, w_b, kern):
+def _conv1x1_backward_dual(c):
     """Backward of a 1x1 / stride-1 conv followed by a linear (no activation) train-mode BatchNorm -- bn3 and the stride-1
     downsample BN of a bottleneck, the projection conv of an inverted residual.  After the BatchNorm-backward sums are
     finalised, the data-gradient kernel reads (g, z) directly and forms dz = A g + B z + C in its loader; dz is written
     once, as a side output, for the weight-gradient kernel.  Saves one full pass over the layer's largest tensor."""
-    G = rt.groups
-    C = d.Cout
-    g, coef, aff = _bn_backward(rt, out, y, vec, bn, ACT_NONE, count, defer_apply=True)
+    x, y, cs, d = c.x, c.y, c.cs, c.d
+    g, coef, aff = _bn_backward(c.rt, c.out, y, c.vec, c.bn, ACT_NONE, c.count, defer_apply=True)
     need_w = cs.weight.requires_grad
     dz = torch.empty_like(y) if need_w else None
-    acc = 1
-    if x.grad is None:
-        x.grad = torch.empty_like(x.data)
-        acc = 0
-    tgt = x.src if x.src is not None else x
-    if sole_consumer and acc == 0 and tgt.vec is not None and tgt.pre_sums is None:
-        sums = rt.bwd_arena.take(G * 2 * d.Cin * STAT_SLOTS)
-        hip.next_meta = (2 * macs, 2 * in_b + (3 if need_w else 2) * out_b + w_b, kern, R_FUSED)
-        call("adamml_conv_bwd_data_dual", byref(d), ptr(g), ptr(y), ptr(aff), ptr(dz), ptr(cs.w_dgrad), ptr(x.grad), 0, ptr(tgt.data),
-             ptr(tgt.vec), tgt.act, ptr(sums))
-        tgt.pre_sums = sums
-    else:
-        hip.next_meta = (2 * macs, in_b * (1 + acc) + (3 if need_w else 2) * out_b + w_b, kern, R_FUSED)
-        call("adamml_conv_bwd_data_dual", byref(d), ptr(g), ptr(y), ptr(aff), ptr(dz), ptr(cs.w_dgrad), ptr(x.grad), acc, None, None, 0,
-             None)
+    acc, sums, tail = _claim_grad_and_sums(c)
+    hip.next_meta = (2 * c.macs, c.in_b * (1 + acc + (0 if sums is None else 1)) + (3 if need_w else 2) * c.out_b + c.w_b, c.lab[1],
+                     R_FUSED)
+    call("adamml_conv_bwd_data_dual", byref(d), ptr(g), ptr(y), ptr(aff), ptr(dz), ptr(cs.w_dgrad), ptr(x.grad), acc,
+         *tail)
     if need_w:
-        with _on_wgrad_stream(rt, (dz, x.data, x.scale)):
-            hip.next_meta = (2 * macs, in_b + out_b + 2 * w_b, None, R_WGRAD)
-            ws = hip.wgrad_workspace(d, cs.cin_true, dz.device)
-            call("adamml_conv_bwd_weight", byref(d), ptr(dz), ptr(x.data), ptr(x.scale), ptr(x.shift), ptr(cs.weight.grad), cs.cin_true,
-                 ptr(ws), ws.numel() * 4)
+        _launch_wgrad(c, dz)
 
 
 def _residual_fusable(x, d):
@@ -805,6 +847,11 @@ def _accum_grad(t, g):
         call("adamml_bn_act_add", ptr(t.grad), None, None, 0, ACT_NONE, ptr(g), None, None, 0, ptr(t.grad), n, g.shape[-1], 1)
 
 
+def _idn_args(idn):
+    """(data, scale, shift, group stride) of the lazy identity operand of a residual add; all null without one"""
+    return (ptr(idn.data), ptr(idn.scale), ptr(idn.shift), idn.gs) if idn is not None else (None, None, None, 0)
+
+
 def add_act(rt, z, idn, act, idn_sole=False):
     """out = act(value(z) + value(idn)); idn may be None (pure materialisation).  z must have no other consumer;
     idn_sole=True promises the same for a lazily normalised idn (the downsample branch of a bottleneck)."""
@@ -816,9 +863,7 @@ def add_act(rt, z, idn, act, idn_sole=False):
     P = n // G * h * w
     # 1 bit per element of act'(out): what the fused residual backward needs of `out` (None when nothing will be masked)
     mask_t = torch.empty(n, h, w, C // 8, dtype=torch.uint8, device=out_t.device) if (rt.tape.need_grad and act != ACT_NONE) else None
-    call("adamml_bn_act_add_mask", ptr(z.data), ptr(z.scale), ptr(z.shift), z.gs, act, ptr(idn.data) if idn is not None else None,
-         ptr(idn.scale) if idn is not None else None, ptr(idn.shift) if idn is not None else None,
-         idn.gs if idn is not None else 0, ptr(out_t), ptr(mask_t), P, C, G)
+    call("adamml_bn_act_add_mask", ptr(z.data), ptr(z.scale), ptr(z.shift), z.gs, act, *_idn_args(idn), ptr(out_t), ptr(mask_t), P, C, G)
     out = Lazy(out_t)
     out.res = (z, idn, act, idn_sole, mask_t)
     if rt.tape.need_grad:
@@ -844,8 +889,8 @@ def _add_backward(rt, out, out_t, z, idn, act, idn_sole, P, C):
         return
     g2 = torch.empty_like(g) if act != ACT_NONE else g
     if fa or fb:
-        sa = rt.bwd_arena.take(G * 2 * C * STAT_SLOTS) if fa else None
-        sb = rt.bwd_arena.take(G * 2 * C * STAT_SLOTS) if fb else None
+        sa = _take_sums(rt, C) if fa else None
+        sb = _take_sums(rt, C) if fb else None
         call("adamml_residual_bwd", ptr(g), ptr(out_t), act, ptr(g2), ptr(z.ensure_data()) if fa else None,
              ptr(z.vec) if fa else None, ptr(sa), ptr(idn.data) if fb else None, ptr(idn.vec) if fb else None, ptr(sb),
              P, C, G)
@@ -888,6 +933,148 @@ def conv_bn_add_tpool_supported(rt, x, cs, idn, act, frames, mode):
     return bool(hip.load().adamml_conv_fwd_bn_add_tpool_supported(byref(d), frames, act, 1 if x.scale is not None else 0))
 
 
+_ADD_LABELS = ("conv_gemm_kernel", None, None, None, None, None, None)      # the `lab` of a conv_bn_add record: only kern is read
+
+
+def _bn_add_vectors(rt, x, cs, bn, d, count):
+    """-> (vec [G,4,C], Gm, sv) of conv_bn_add.  Train: the statistics from the Gram matrix and column sums of x; eval: Gm = sv = None."""
+    G = rt.groups
+    dev = x.data.device
+    C, Cin = d.Cout, d.Cin
+    if rt.training:
+        Gm, sv = _gram_colsum(rt, x, d)
+        sums = torch.empty(G * 2 * C, dtype=torch.float64, device=dev)
+        call("adamml_gram_stats", ptr(cs.w_fwd), ptr(Gm), ptr(sv), ptr(sums), C, Cin, G)
+        if rt.sync.enabled:                  # SyncBatchNorm: the (already collapsed) sums are all-reduced, as SyncCtx.reduce does
+            sums = interleave.exchange(sums, rt.sync.group)
+        vec = torch.empty(G, 4, C, dtype=torch.float32, device=dev)
+        call("adamml_bn_finalize", ptr(sums), 1, G, float(count * rt.sync.world), ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean),
+             ptr(bn.running_var), BN_MOMENTUM, BN_EPS, ptr(vec), C)
+        rt.touched_bns.append(bn)
+        return vec, Gm, sv
+    # [G][4][C] with (scale, shift) of the eval-mode affine in rows 0 / 1 of every group (the epilogue reads nothing else): stream-ordered
+    # C-ABI copies, so that a launch plan records them
+    ev = _bn_eval_vectors(rt, bn, C, dev)
+    c4 = getattr(bn, "_hip_eval_vec4", None)
+    if c4 is not None and c4[0] is ev and c4[1].shape[0] == G and hip.recorder is None:
+        return c4[1], None, None             # (built from this very eval-affine tensor: valid as long as that cache entry is)
+    vec = torch.empty(G, 4, C, dtype=torch.float32, device=dev)
+    for gi in range(G):
+        call("adamml_copy2d", ptr(vec[gi]), 2 * C * 4, ptr(ev), 2 * C * 4, 2 * C * 4, 1)
+    if hip.recorder is None:
+        bn._hip_eval_vec4 = (ev, vec)
+    return vec, None, None
+
+
+def _bn_add_forward(rt, x, cs, d, vec, idn, act, tpool, next_cs, work):
+    """The forward launch of conv_bn_add -> (out_t, mask_t, code_t, nxt): pooling too (out_t pooled, code_t for its backward), running the
+    NEXT block's conv1 too (nxt, for Lazy.next_pre), or plain.  mask_t: 1 bit per element of act'(out), for the fused residual backward."""
+    (macs, in_b, out_b, w_b), kern = work, _ADD_LABELS[0]
+    G, C, count, dev, need_grad = rt.groups, d.Cout, d.N * d.OH * d.OW, x.data.device, rt.tape.need_grad
+    if tpool:
+        to = tpool // 2
+        out_t = torch.empty(G * d.N // tpool * to, d.OH, d.OW, C, dtype=torch.bfloat16, device=dev)        # POOLED block output
+        code_t = torch.empty(G * d.N // tpool * to, d.OH, d.OW, C // 8, dtype=torch.int16, device=dev) if need_grad else None
+        kern_tp = (kern, "conv1x1_fadd_tpool_kernel", "conv1x1_fadd_tpool_stream_kernel")[hip.load().adamml_conv_fwd_bn_add_tpool_streams(byref(d), tpool)]
+        hip.next_meta = (2 * macs, in_b + 1.5 * out_b + w_b + (out_b / 16 if code_t is not None else 0), kern_tp, R_FUSED)
+        call("adamml_conv_fwd_bn_add_tpool", byref(d), ptr(x.data), ptr(cs.w_fwd), ptr(x.scale), ptr(x.shift), ptr(vec), ptr(idn.data), None, None, 0,
+             act, tpool, ptr(out_t), ptr(code_t))
+        return out_t, None, code_t, None
+    out_t = torch.empty(G * d.N, d.OH, d.OW, C, dtype=torch.bfloat16, device=dev)
+    mask_t = torch.empty(G * d.N, d.OH, d.OW, C // 8, dtype=torch.uint8, device=dev) if (need_grad and act != ACT_NONE) else None
+    hip.next_meta = (2 * macs, in_b + (2 if idn is not None else 1) * out_b + w_b + (out_b / 16 if mask_t is not None else 0), kern, R_FUSED)
+    if (next_cs is not None and rt.training and next_cs.kh * next_cs.kw == 1 and next_cs.stride == 1
+            and not next_cs.depthwise and next_cs.cin == C and hip.load().adamml_conv_fwd_bn_add_next_supported(byref(d), next_cs.weight.shape[0])):
+        # the NEXT block's conv1 consumes the block-output tile while it is still in LDS (csrc/conv1x1_fadd_next.hip): conv_bn(out, next_cs)
+        # finds its raw output and statistics here and launches nothing
+        Cn = next_cs.weight.shape[0]
+        y_n = torch.empty(G * d.N, d.OH, d.OW, Cn, dtype=torch.bfloat16, device=dev)
+        st_n = rt.fwd_arena.take(G * 2 * Cn * STAT_SLOTS)
+        hip.next_meta = (2 * macs + 2.0 * count * G * C * Cn, in_b + (2 if idn is not None else 1) * out_b + w_b + 2.0 * G * count * Cn + 2.0 * C * Cn
+                         + (out_b / 16 if mask_t is not None else 0), "conv1x1_fadd_next_kernel", R_FUSED)
+        call("adamml_conv_fwd_bn_add_next", byref(d), ptr(x.data), ptr(cs.w_fwd), ptr(x.scale), ptr(x.shift), ptr(vec),
+             *_idn_args(idn), act, ptr(out_t), ptr(mask_t), ptr(next_cs.w_fwd), ptr(y_n), ptr(st_n))
+        return out_t, mask_t, None, (next_cs, y_n, st_n)
+    if idn is not None and hip.load().adamml_conv_fwd_bn_add_streams(byref(d)):
+        hip.next_meta = hip.next_meta[:2] + ("conv1x1_fadd_stream_kernel", R_FUSED)       # (the layer-2 shape: csrc/conv1x1_fadd_stream.hip)
+    call("adamml_conv_fwd_bn_add", byref(d), ptr(x.data), ptr(cs.w_fwd), ptr(x.scale), ptr(x.shift), ptr(vec),
+         *_idn_args(idn), act, ptr(out_t), ptr(mask_t))
+    return out_t, mask_t, None, None
+
+
+def _bn_add_register_backward(c, out, out_t, mask_t, code_t, idn, idn_sole, tpool):
+    """Records the backward of a conv_bn_add call: the algebraic backward of its conv (c.out = the raw conv output as a never
+    materialised lazy tensor), the add's and, with tpool, the fused pool's.  out: the Lazy the call returns."""
+    rt, z = c.rt, c.out
+    # `blk` = the full-rate block output as the residual machinery sees it; with the pool fused it is never materialised (data None):
+    # its gradient arrives from the pool's backward below, already masked, with the sum(g') of bn3 accumulated (res_done)
+    blk = out if not tpool else Lazy(None)
+    if tpool:
+        blk._shape = z._shape
+    blk.res = (z, idn, c.act, idn_sole, mask_t)
+    rt.tape.record(lambda: _bn_add_conv_backward(c))
+    rt.tape.record(lambda: _add_backward(rt, blk, out_t if not tpool else None, z, idn, c.act, idn_sole, c.count, c.d.Cout))
+    if tpool:
+        rt.tape.record(lambda: _bn_add_pool_backward(c, out, blk, code_t, tpool))
+
+
+def _bn_add_raw_output(rt, x, cs, d, vec):
+    """The raw conv output of a conv_bn_add call as a (never materialised) lazy tensor: the generic residual machinery only needs its
+    BatchNorm vectors; recompute() writes it should a reduction pass have to read it."""
+    C = d.Cout
+    full_shape = (rt.groups * d.N, d.OH, d.OW, C)
+    z = Lazy(None, vec[0, 0], vec[0, 1], ACT_NONE, gs=4 * C)
+    z._shape = torch.Size(full_shape)
+    z.vec = vec
+    z.alg = True
+    z.recompute = lambda: _bn_add_recompute(x, cs, d, full_shape)
+    z.alg_in = (x, d)
+    return z
+
+
+def _bn_add_recompute(x, cs, d, shape):
+    """The raw conv output of a conv_bn_add call, which its forward never stored (Lazy.recompute)."""
+    y = torch.empty(shape, dtype=torch.bfloat16, device=x.data.device)
+    _launch_conv_fwd(cs, d, x, y, False, None)
+    return y
+
+
+def _bn_add_conv_backward(c):
+    z = c.out
+    if z.grad is None:
+        return
+    if z.pre_sums is None:
+        z.ensure_data()              # the producer of g' could not fuse the BatchNorm-backward sums: the reduction pass reads z
+    _conv1x1_backward_alg(c, z.data if z.data is not None else _Meta(tuple(z.shape), c.x.data.device))
+
+
+def _bn_add_pool_backward(c, out, blk, code_t, tpool):
+    """Backward of the pool in conv_bn_add's epilogue: the gradient of the full-rate block output (already masked) and the sum(g') of bn3."""
+    rt, x, cs, d, z = c.rt, c.x, c.cs, c.d, c.out
+    G, C, dev = rt.groups, d.Cout, x.data.device
+    g, out.grad = out.grad, None
+    if g is None:
+        return
+    gx = torch.empty(tuple(z.shape), dtype=torch.bfloat16, device=dev)
+    sa = _take_sums(rt, C)
+    lib = hip.load()
+    if z.alg and x.requires_grad and cs.weight.requires_grad and _alg_supported(cs, d) \
+            and lib.adamml_temporal_pool_bwd_code_prod_supported(tpool, C, d.Cin):
+        # the expanded gradient AND the product g'^T a the algebraic backward of conv3 needs first, from one pass (the product
+        # kernel read the 4.6 GB of g' back)
+        P = torch.empty(G, C, d.Cin, dtype=torch.float32, device=dev)
+        ws = hip.scratch(lib.adamml_temporal_pool_bwd_code_prod_workspace(d.N // tpool, tpool, d.OH * d.OW, C, d.Cin, G), dev)
+        hip.next_meta = (2 * c.macs, c.in_b + 1.5 * c.out_b + c.out_b / 16, "tpool_bwd_prod_kernel", R_WGRAD)
+        call("adamml_temporal_pool_bwd_code_prod", ptr(g), ptr(code_t), ptr(gx), ptr(sa), ptr(x.data), ptr(x.scale), ptr(x.shift), x.gs, x.act,
+             ptr(P), ptr(ws), ws.numel() * 4, d.N // tpool, tpool, d.OH * d.OW, C, d.Cin, G)
+        z.prod = P
+    else:
+        call("adamml_temporal_pool_bwd_code", ptr(g), ptr(code_t), ptr(gx), ptr(sa), d.N // tpool, tpool, d.OH * d.OW, C, G)
+    z.pre_sums, z.sums_partial = sa, True
+    blk.res_done = True
+    blk.grad = gx
+
+
 def conv_bn_add(rt, x, cs, bn, idn, act, idn_sole=False, tpool=0, next_cs=None):
     """out = act(BatchNorm(conv1x1(x)) + value(idn)) in ONE kernel whose epilogue normalises, adds and activates
     (adamml_conv_fwd_bn_add): the raw conv output is never written to HBM nor re-read by a separate add pass.
@@ -902,134 +1089,23 @@ def conv_bn_add(rt, x, cs, bn, idn, act, idn_sole=False, tpool=0, next_cs=None):
     if idn is not None and idn.act != ACT_NONE:
         raise RuntimeError("conv_bn_add: the identity operand must be linear (no pending activation)")
     d = cs.desc(x.shape, x.act, G, x.gs)
-    dev = x.data.device
-    C, Cin = d.Cout, d.Cin
+    C = d.Cout
     count = d.N * d.OH * d.OW
-    need_grad = rt.tape.need_grad
     macs = float(count) * G * C * cs.cin_true
     in_b, out_b, w_b = 2.0 * G * count * cs.cin_true, 2.0 * G * count * C, 2.0 * C * cs.cin_true
-    kern = "conv_gemm_kernel"
-    Gm = sv = None
-    if rt.training:
-        Gm, sv = _gram_colsum(rt, x, d)
-        sums = torch.empty(G * 2 * C, dtype=torch.float64, device=dev)
-        call("adamml_gram_stats", ptr(cs.w_fwd), ptr(Gm), ptr(sv), ptr(sums), C, Cin, G)
-        if rt.sync.enabled:                  # SyncBatchNorm: the (already collapsed) sums are all-reduced, as SyncCtx.reduce does
-            sums = interleave.exchange(sums, rt.sync.group)
-        vec = torch.empty(G, 4, C, dtype=torch.float32, device=dev)
-        call("adamml_bn_finalize", ptr(sums), 1, G, float(count * rt.sync.world), ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean),
-             ptr(bn.running_var), BN_MOMENTUM, BN_EPS, ptr(vec), C)
-        rt.touched_bns.append(bn)
-    else:
-        # [G][4][C] with (scale, shift) of the eval-mode affine in rows 0 / 1 of every group (the epilogue reads nothing else): stream-ordered
-        # C-ABI copies, so that a launch plan records them
-        ev = _bn_eval_vectors(rt, bn, C, dev)
-        c4 = getattr(bn, "_hip_eval_vec4", None)
-        if c4 is not None and c4[0] is ev and c4[1].shape[0] == G and hip.recorder is None:
-            vec = c4[1]                      # (built from this very eval-affine tensor: valid as long as that cache entry is)
-        else:
-            vec = torch.empty(G, 4, C, dtype=torch.float32, device=dev)
-            for gi in range(G):
-                call("adamml_copy2d", ptr(vec[gi]), 2 * C * 4, ptr(ev), 2 * C * 4, 2 * C * 4, 1)
-            if hip.recorder is None:
-                bn._hip_eval_vec4 = (ev, vec)
-    if tpool:
-        to = tpool // 2
-        out_t = torch.empty(G * d.N // tpool * to, d.OH, d.OW, C, dtype=torch.bfloat16, device=dev)        # POOLED block output
-        code_t = torch.empty(G * d.N // tpool * to, d.OH, d.OW, C // 8, dtype=torch.int16, device=dev) if need_grad else None
-        mask_t = None
-        kern_tp = (kern, "conv1x1_fadd_tpool_kernel", "conv1x1_fadd_tpool_stream_kernel")[hip.load().adamml_conv_fwd_bn_add_tpool_streams(byref(d), tpool)]
-        hip.next_meta = (2 * macs, in_b + 1.5 * out_b + w_b + (out_b / 16 if code_t is not None else 0), kern_tp, R_FUSED)
-        call("adamml_conv_fwd_bn_add_tpool", byref(d), ptr(x.data), ptr(cs.w_fwd), ptr(x.scale), ptr(x.shift), ptr(vec), ptr(idn.data), None, None, 0,
-             act, tpool, ptr(out_t), ptr(code_t))
-        full_shape = (G * d.N, d.OH, d.OW, C)
-    else:
-        out_t = torch.empty(G * d.N, d.OH, d.OW, C, dtype=torch.bfloat16, device=dev)
-        mask_t = torch.empty(G * d.N, d.OH, d.OW, C // 8, dtype=torch.uint8, device=dev) if (need_grad and act != ACT_NONE) else None
-        hip.next_meta = (2 * macs, in_b + (2 if idn is not None else 1) * out_b + w_b + (out_b / 16 if mask_t is not None else 0), kern, R_FUSED)
-        nxt = None
-        if (next_cs is not None and rt.training and next_cs.kh * next_cs.kw == 1 and next_cs.stride == 1
-                and not next_cs.depthwise and next_cs.cin == C and hip.load().adamml_conv_fwd_bn_add_next_supported(byref(d), next_cs.weight.shape[0])):
-            # the NEXT block's conv1 consumes the block-output tile while it is still in LDS (csrc/conv1x1_fadd_next.hip): conv_bn(out, next_cs)
-            # finds its raw output and statistics here and launches nothing
-            Cn = next_cs.weight.shape[0]
-            y_n = torch.empty(G * d.N, d.OH, d.OW, Cn, dtype=torch.bfloat16, device=dev)
-            st_n = rt.fwd_arena.take(G * 2 * Cn * STAT_SLOTS)
-            hip.next_meta = (2 * macs + 2.0 * count * G * C * Cn, in_b + (2 if idn is not None else 1) * out_b + w_b + 2.0 * G * count * Cn + 2.0 * C * Cn
-                             + (out_b / 16 if mask_t is not None else 0), "conv1x1_fadd_next_kernel", R_FUSED)
-            call("adamml_conv_fwd_bn_add_next", byref(d), ptr(x.data), ptr(cs.w_fwd), ptr(x.scale), ptr(x.shift), ptr(vec),
-                 ptr(idn.data) if idn is not None else None, ptr(idn.scale) if idn is not None else None,
-                 ptr(idn.shift) if idn is not None else None, idn.gs if idn is not None else 0, act, ptr(out_t), ptr(mask_t),
-                 ptr(next_cs.w_fwd), ptr(y_n), ptr(st_n))
-            nxt = (next_cs, y_n, st_n)
-        else:
-            if idn is not None and hip.load().adamml_conv_fwd_bn_add_streams(byref(d)):
-                hip.next_meta = hip.next_meta[:2] + ("conv1x1_fadd_stream_kernel", R_FUSED)       # (the layer-2 shape: csrc/conv1x1_fadd_stream.hip)
-            call("adamml_conv_fwd_bn_add", byref(d), ptr(x.data), ptr(cs.w_fwd), ptr(x.scale), ptr(x.shift), ptr(vec),
-                 ptr(idn.data) if idn is not None else None, ptr(idn.scale) if idn is not None else None,
-                 ptr(idn.shift) if idn is not None else None, idn.gs if idn is not None else 0, act, ptr(out_t), ptr(mask_t))
-        full_shape = tuple(out_t.shape)
+    vec, Gm, sv = _bn_add_vectors(rt, x, cs, bn, d, count)
+    out_t, mask_t, code_t, nxt = _bn_add_forward(rt, x, cs, d, vec, idn, act, tpool, next_cs, (macs, in_b, out_b, w_b))
     out = Lazy(out_t)
-    if rt.capture is not None and "aux" in rt.capture:           # (otherwise only reachable through the backward closures below)
+    if rt.capture is not None and "aux" in rt.capture:           # (otherwise only reachable through the backward functions of this call)
         rt.capture["aux"][id(out)] = (code_t if tpool else None, mask_t, vec)
     if not tpool:
         out.next_pre = nxt
         if nxt is not None:
             rt.pre_pending += 1
-    if not need_grad:
-        return out
-    # the raw conv output as a (never materialised) lazy tensor: the generic residual machinery only needs its BatchNorm vectors
-    z = Lazy(None, vec[0, 0], vec[0, 1], ACT_NONE, gs=4 * C)
-    z._shape = torch.Size(full_shape)
-    z.vec = vec
-    z.alg = True
-
-    def recompute():
-        y = torch.empty(full_shape, dtype=torch.bfloat16, device=dev)
-        call("adamml_conv_fwd", byref(d), ptr(x.data), ptr(cs.w_fwd), ptr(x.scale), ptr(x.shift), ptr(y), None)
-        return y
-    z.recompute = recompute
-    z.alg_in = (x, d)
-    # `blk` = the full-rate block output as the residual machinery sees it; with the pool fused it is never materialised (data None):
-    # its gradient arrives from the pool's backward below, already masked, with the sum(g') of bn3 accumulated (res_done)
-    blk = out if not tpool else Lazy(None)
-    if tpool:
-        blk._shape = torch.Size(full_shape)
-    blk.res = (z, idn, act, idn_sole, mask_t)
-
-    def conv_bwd():
-        if z.grad is None:
-            return
-        if z.pre_sums is None:
-            z.ensure_data()              # the producer of g' could not fuse the BatchNorm-backward sums: the reduction pass reads z
-        y = z.data if z.data is not None else _Meta(full_shape, dev)
-        _conv1x1_backward_alg(rt, z, x, y, vec, bn, cs, d, count, True, macs, in_b, out_b, w_b, kern, Gm=Gm, sv=sv)
-    rt.tape.record(conv_bwd)
-    rt.tape.record(lambda: _add_backward(rt, blk, out_t if not tpool else None, z, idn, act, idn_sole, count, C))
-    if tpool:
-        def pool_bwd():
-            g, out.grad = out.grad, None
-            if g is None:
-                return
-            gx = torch.empty(full_shape, dtype=torch.bfloat16, device=dev)
-            sa = rt.bwd_arena.take(G * 2 * C * STAT_SLOTS)
-            lib = hip.load()
-            if z.alg and x.requires_grad and cs.weight.requires_grad and _alg_supported(cs, d) \
-                    and lib.adamml_temporal_pool_bwd_code_prod_supported(tpool, C, d.Cin):
-                # the expanded gradient AND the product g'^T a the algebraic backward of conv3 needs first, from one pass (the product
-                # kernel read the 4.6 GB of g' back)
-                P = torch.empty(G, C, d.Cin, dtype=torch.float32, device=dev)
-                ws = hip.scratch(lib.adamml_temporal_pool_bwd_code_prod_workspace(d.N // tpool, tpool, d.OH * d.OW, C, d.Cin, G), dev)
-                hip.next_meta = (2 * macs, in_b + 1.5 * out_b + out_b / 16, "tpool_bwd_prod_kernel", R_WGRAD)
-                call("adamml_temporal_pool_bwd_code_prod", ptr(g), ptr(code_t), ptr(gx), ptr(sa), ptr(x.data), ptr(x.scale), ptr(x.shift), x.gs, x.act,
-                     ptr(P), ptr(ws), ws.numel() * 4, d.N // tpool, tpool, d.OH * d.OW, C, d.Cin, G)
-                z.prod = P
-            else:
-                call("adamml_temporal_pool_bwd_code", ptr(g), ptr(code_t), ptr(gx), ptr(sa), d.N // tpool, tpool, d.OH * d.OW, C, G)
-            z.pre_sums, z.sums_partial = sa, True
-            blk.res_done = True
-            blk.grad = gx
-        rt.tape.record(pool_bwd)
+    if rt.tape.need_grad:
+        z = _bn_add_raw_output(rt, x, cs, d, vec)
+        c = _ConvCall(rt, x, None, z, vec, bn, cs, d, count, act, True, False, False, macs, in_b, out_b, w_b, _ADD_LABELS, Gm, sv)
+        _bn_add_register_backward(c, out, out_t, mask_t, code_t, idn, idn_sole, tpool)
     return out
 
 

@@ -1,0 +1,150 @@
+"""What the host executor (adamml_amd/runtime.py) launches, checked without a GPU: tools/launch_trace.py runs the models' own `_run`
+and reverse tape on CPU tensors with every C-ABI launch logged instead of issued (the host logic never reads a tensor value; the
+dispatch probes are host functions of the built library).  Two runs give the same trace line for line, and the entry-point expectations
+tests/test_executor_gpu.py writes down for its rows hold for the same rows here."""
+import importlib.util
+import os
+
+import pytest
+
+import __graft_entry__ as ge
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def built():
+    ge.build()
+    return ge.LIB
+
+
+@pytest.fixture(scope="module")
+def runs(built):
+    spec = importlib.util.spec_from_file_location("launch_trace", os.path.join(ROOT, "tools", "launch_trace.py"))
+    lt = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(lt)
+    return lt, lt.trace(), lt.trace()
+
+
+@pytest.fixture(scope="module")
+def rows(runs):
+    return {r.label: r for r in runs[1]}
+
+
+def test_two_runs_give_the_same_trace(runs):
+    lt, a, b = runs
+    assert [r.label for r in a] == [label for label, _ in lt.ROWS]
+    for ra, rb in zip(a, b):
+        assert ra.lines == rb.lines, ra.label
+        assert sum(ra.counts.values()) > 0
+    assert lt.digest(a) == lt.digest(b)
+    # nothing address-like reaches a line: pointers are ordinals, everything else a scalar of the call
+    assert not [ln for r in a for ln in r.lines if "data_ptr" in ln or " 0x" in ln]
+
+
+def test_the_patches_are_undone(runs):
+    from adamml_amd import hip, runtime
+    assert runtime.call is hip.call and runtime.ptr is hip.ptr and hip.call.__module__ == "adamml_amd.hip"
+    assert runtime._on_wgrad_stream.__enter__.__qualname__ == "_on_wgrad_stream.__enter__"
+
+
+def residual_bwd_channels(r):
+    """channel counts of the adamml_residual_bwd launches (its last three arguments are P, C, G)"""
+    return [a[-2] for n, a, _ in r.log if n == "adamml_residual_bwd"]
+
+
+def test_resnet50_streaming_forms(rows):
+    r = rows["resnet50-streaming"]
+    n = r.counts
+    assert n["adamml_conv_fwd_bn_add_next"] == 2 and r.net.rt.pre_dropped == 0 and r.net.rt.pre_pending == 0
+    assert n["adamml_conv_fwd_bn_add_tpool"] >= 2
+    assert n["adamml_temporal_pool_bwd_code_prod"] == 1
+    assert n["adamml_conv_bwd_data_res_prod"] >= 1 and n["adamml_conv_bwd_data_res"] >= 1
+    assert n["adamml_alg_sumfix"] >= 1
+    assert n["adamml_maxpool2d_bwd_bn_apply"] == 1
+    assert n["adamml_temporal_pool_fwd"] == 1 and n["adamml_temporal_pool_bwd_res"] == 1
+    assert not [c for c in residual_bwd_channels(r) if c in (256, 512)]
+
+
+def test_resnet50_tile_and_fallback_forms_grouped(rows):
+    r = rows["resnet50-tile-g3"]
+    n = r.counts
+    assert n["adamml_conv_bwd_data_res_prod"] == 0
+    assert n["adamml_conv_bwd_data_res"] >= 1 and n["adamml_conv_bwd_weight_grouped"] >= 1
+    assert n["adamml_conv_fwd_bn_add_tpool"] == 2 and n["adamml_conv_fwd_bn_add_next"] == 2 and r.net.rt.pre_dropped == 0
+
+
+def test_resnet50_without_t_stride(rows):
+    n = rows["resnet50-without-t-stride"].counts
+    assert n["adamml_temporal_pool_fwd"] == 0 and n["adamml_conv_fwd_bn_add_tpool"] == 0
+    assert n["adamml_conv_fwd_bn_add"] + n["adamml_conv_fwd_bn_add_next"] == 7 and n["adamml_residual_bwd"] >= 1
+
+
+def test_resnet50_avg_pooling(rows):
+    n = rows["resnet50-avg"].counts
+    assert n["adamml_conv_fwd_bn_add_tpool"] == 0 and n["adamml_temporal_pool_fwd"] == 3
+    assert n["adamml_temporal_pool_bwd_res"] == 0 and n["adamml_temporal_pool_bwd"] == 3
+    assert n["adamml_residual_bwd"] >= 1
+
+
+def test_resnet50_partly_frozen(rows):
+    n = rows["resnet50-frozen-stem-layer1"].counts
+    assert n["adamml_conv_stem_bwd_weight"] == 0
+    assert n["adamml_temporal_pool_fwd"] == 2 and n["adamml_temporal_pool_bwd_res"] == 1
+    assert n["adamml_conv_bwd_data_alg"] == 4 and n["adamml_conv_bwd_data_dual"] == 4
+
+
+def _mobilenet_expectations(n):
+    assert n["adamml_dwconv_bwd_fused"] == 17
+    assert n["adamml_dwconv_bwd_weight"] == 0 and n["adamml_dwconv_bwd_data"] == 0 and n["adamml_dwconv_bwd_data_bn"] == 0
+    assert n["adamml_conv_bwd_data_dual"] >= 17
+
+
+def test_sound_mobilenet_v2(rows):
+    n = rows["sound-mobilenetv2-g2"].counts
+    assert n["adamml_conv_stem1_fwd"] == 1
+    _mobilenet_expectations(n)
+
+
+def test_policy_mobilenet_v2(rows):
+    n = rows["policy-mobilenetv2-g2"].counts
+    assert n["adamml_temporal_pool_fwd"] == 2 and n["adamml_temporal_pool_bwd_res"] == 2
+    _mobilenet_expectations(n)
+
+
+def test_forward_only_rows_launch_no_backward(rows):
+    for label in ("resnet50-train-nograd", "resnet50-eval", "policy-mobilenetv2-train-nograd"):
+        r = rows[label]
+        assert not [n for n in r.counts if "_bwd" in n], label
+        assert not [e for e in r.log if e[2] is None], label            # no weight-gradient stream marker either
+    assert rows["resnet50-eval"].counts["adamml_bn_finalize"] == 0 and rows["resnet50-train-nograd"].counts["adamml_bn_finalize"] == 53
+
+
+def test_unfused_depthwise_forms(rows):
+    """frozen depthwise weights: no fused depthwise backward, the data gradient still produces the expansion's sums; a depthwise conv that
+    shares its input (no model has one) takes the unfused weight gradient and the accumulating data gradient"""
+    n = rows["policy-mobilenetv2-frozen-depthwise"].counts
+    assert n["adamml_dwconv_bwd_fused"] == 0 and n["adamml_dwconv_bwd_data_bn"] == 17 and n["adamml_dwconv_bwd_weight"] == 0
+    r = rows["ops-shared-depthwise-input"]
+    assert r.counts["adamml_dwconv_bwd_weight"] == 1 and r.counts["adamml_act_bwd_from_output"] == 1
+    assert [a[-1] for n_, a, _ in r.log if n_ == "adamml_dwconv_bwd_data"] == [1]            # acc = 1: it adds to the gradient already there
+
+
+def test_a_step_leaves_nothing_to_the_cycle_collector(runs):
+    """The activations of a step are freed by reference counting when the step ends: a Lazy (or a backward record holding one) that sits in a
+    reference cycle keeps gigabytes alive until the cycle collector happens to run, and the next steps run out of memory."""
+    import gc
+    lt = runs[0]
+    gc.collect()
+    flags = gc.get_debug()
+    gc.set_debug(gc.DEBUG_SAVEALL)
+    try:
+        r = lt.trace(lt.ROWS[1:2] + lt.ROWS[5:6])            # a ResNet-50 row (conv_bn_add, fused pool) and a MobileNetV2 row
+        del r
+        gc.collect()
+        left = sorted({type(o).__name__ for o in gc.garbage if type(o).__module__ == "adamml_amd.runtime"}
+                      - {"NetRT", "Arena", "SyncCtx", "ConvState", "Tape"})       # (a model and what it owns are one cycle, freed with it)
+    finally:
+        gc.set_debug(flags)
+        del gc.garbage[:]
+    assert not left, left

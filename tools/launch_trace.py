@@ -1,0 +1,234 @@
+"""Host-only launch trace of the executor (adamml_amd/runtime.py): every model row runs its own `_run` and its reverse tape on CPU
+tensors with `call` replaced by a logger -- the host logic never reads a tensor value, and the *_supported / *_streams / *_workspace
+probes answer without a GPU.  One line per launch: entry point, every argument (a ConvDesc by its sixteen fields, a pointer by the
+ordinal of its first appearance, None for a null pointer) and hip.next_meta; a marker line where the weight-gradient stream context
+is entered / left.  Two trees issue the same launches exactly when their traces are byte-identical.
+Usage: python tools/launch_trace.py [--package DIR] [--out FILE]     (DIR: the tree whose adamml_amd is traced, default: this one)"""
+import collections
+import contextlib
+import hashlib
+import os
+import sys
+
+import torch
+
+
+def _resnet(frames, frozen=None, **kw):
+    from adamml_amd.resnet import ResNet
+    net = ResNet(50, num_frames=frames, num_classes=11, dropout=0.0, **kw)
+    return net, ([p for m in frozen(net) for p in m.parameters()] if frozen else [])
+
+
+def _frames(net, n, hw):
+    return torch.zeros(n, hw, hw, net.input_cpad(hw, hw), dtype=torch.bfloat16)
+
+
+def _mobilenet(which, frozen=None):
+    if which == "sound":
+        from adamml_amd.sound_mobilenet_v2 import MobileNetV2
+        net, x = MobileNetV2(num_classes=11, input_channels=1, dropout=0.0), torch.zeros(4, 2, 64, 64)
+    else:
+        from adamml_amd.policy_net import MobileNetV2
+        net, x = MobileNetV2(num_frames=4, input_channels=3), torch.zeros(2 * 4 * 4, 64, 64, 8, dtype=torch.bfloat16)
+    return net, x, (frozen(net) if frozen else [])
+
+
+def _depthwise_weights(net):
+    return [m.weight for m in net.modules() if isinstance(m, torch.nn.Conv2d) and m.groups > 1]
+
+
+def _all_but(net, params):
+    return [p for p in net.parameters() if id(p) not in {id(q) for q in params}]
+
+
+def _resnet_row(frames, hw, clips, groups, mode="grad", frozen=None, **kw):
+    def make():
+        net, fz = _resnet(frames, frozen, **kw)
+        return net, _frames(net, groups * clips * frames, hw), groups, mode, fz
+    return make
+
+
+def _mobilenet_row(which, mode="grad", frozen=None):
+    def make():
+        net, x, fz = _mobilenet(which, frozen)
+        return net, x, 2, mode, fz
+    return make
+
+
+# label -> () -> (net, input, BatchNorm groups, "grad" | "train-nograd" | "eval", frozen parameters).  The first seven are the rows of
+# tests/test_executor_gpu.py (same shapes, groups and frozen sets); the rest reach the launches those leave out.
+ROWS = (
+    ("resnet50-streaming", _resnet_row(8, 92, 8, 1)),
+    ("resnet50-tile-g3", _resnet_row(4, 44, 2, 3)),
+    ("resnet50-without-t-stride", _resnet_row(4, 44, 2, 1, without_t_stride=True)),
+    ("resnet50-avg", _resnet_row(12, 44, 1, 1, pooling_method="avg")),
+    ("resnet50-frozen-stem-layer1", _resnet_row(4, 44, 2, 3, frozen=lambda n: [n.conv1, n.bn1, n.layer1])),
+    ("sound-mobilenetv2-g2", _mobilenet_row("sound")),
+    ("policy-mobilenetv2-g2", _mobilenet_row("policy")),
+    ("resnet50-train-nograd", _resnet_row(4, 44, 2, 3, mode="train-nograd")),
+    ("resnet50-eval", _resnet_row(4, 44, 2, 3, mode="eval")),
+    ("policy-mobilenetv2-train-nograd", _mobilenet_row("policy", mode="train-nograd")),
+    ("sound-mobilenetv2-eval", _mobilenet_row("sound", mode="eval")),
+    ("policy-mobilenetv2-frozen-depthwise", _mobilenet_row("policy", frozen=_depthwise_weights)),
+    # only the depthwise weights train: their inputs take no gradient, the unfused depthwise weight gradient runs
+    ("policy-mobilenetv2-depthwise-only", _mobilenet_row("policy", frozen=lambda n: _all_but(n, _depthwise_weights(n)))),
+    # no BatchNorm trains: its producers' data gradients need no sums, the bare data gradients and the unfused activation mask run
+    ("sound-mobilenetv2-frozen-batchnorm", _mobilenet_row("sound", frozen=lambda n: [p for p in n.parameters() if p.dim() == 1])),
+    ("resnet50-frozen-conv-weights", _resnet_row(4, 44, 2, 1, frozen=lambda n: [_W([p for p in n.parameters() if p.dim() == 4])])),
+    ("ops-shared-depthwise-input", lambda: (_Ops(), torch.zeros(4, 12, 12, 8, dtype=torch.bfloat16), 2, "grad", [])),
+)
+
+
+class _W:
+    def __init__(self, params):
+        self.params = params
+
+    def parameters(self):
+        return self.params
+
+
+class _Ops(torch.nn.Module):
+    """No model: executor ops driven directly, for the forms no model's graph produces -- a depthwise conv that is not the sole
+    consumer of its input (unfused weight gradient, accumulating data gradient) and an activated add of two plain tensors."""
+
+    def __init__(self):
+        super().__init__()
+        from adamml_amd import runtime
+        self.pw, self.dw = torch.nn.Conv2d(8, 16, 1, bias=False), torch.nn.Conv2d(16, 16, 3, padding=1, groups=16, bias=False)
+        self.bn1, self.bn2 = torch.nn.BatchNorm2d(16), torch.nn.BatchNorm2d(16)
+        self.rt = runtime.NetRT()
+        self.cs = (runtime.ConvState(self.pw.weight, 1, 0), runtime.ConvState(self.dw.weight, 1, 1, depthwise=True))
+
+    def _run(self, x, groups, need_grad):
+        from adamml_amd import runtime as R
+        rt = self.rt
+        tape = rt.begin_forward(x.device, self.training, need_grad, groups)
+        for cs in self.cs:
+            cs.pack_rows(need_grad)
+        h = R.conv_bn(rt, R.Lazy(x, requires_grad=False), self.cs[0], self.bn1, R.ACT_RELU)
+        a = R.conv_bn(rt, h, self.cs[1], self.bn2, R.ACT_RELU)
+        out = R.add_act(rt, R.materialize(rt, a), R.materialize(rt, h), R.ACT_RELU)
+        rt.end_forward()
+        tape.record(lambda: setattr(out, "grad", tape.grad_out))
+        return out.data, tape
+
+
+SITES = None        # --sites: a set collecting (file, line) of every statement that launched
+
+
+class _Ptr(int):
+    """what the replaced `ptr` returns: an address the logger turns into an ordinal"""
+
+
+class Row:
+    __slots__ = ("label", "net", "log", "lines", "counts")
+
+
+@contextlib.contextmanager
+def _patched(log):
+    """`call`, `ptr` and hip._stream replaced in every loaded adamml_amd module; the weight-gradient stream context writes markers"""
+    from adamml_amd import hip, runtime
+    ids, keep = {}, []                  # ordinal by first appearance in a launch; every tensor stays alive, so no address is reused
+
+    def ptr(t):
+        keep.append(t)
+        return None if t is None else _Ptr(t.data_ptr())
+
+    def norm(a):
+        if isinstance(a, _Ptr):
+            return "p%d" % ids.setdefault(int(a), len(ids))
+        d = getattr(a, "_obj", None)
+        return tuple(getattr(d, f[0]) for f in d._fields_) if isinstance(d, hip.ConvDesc) else a
+
+    def call(name, *args):
+        if SITES is not None:
+            SITES.add((os.path.basename(sys._getframe(1).f_code.co_filename), sys._getframe(1).f_lineno))
+        log.append((name, tuple(norm(a) for a in args), hip.next_meta))
+        hip.next_meta = (0.0, 0.0)              # (as under hip.LaunchProfiler: a launch shows the meta written FOR it)
+
+    def marker(name, real):
+        def method(self, *a):
+            log.append((name, tuple(norm(ptr(t)) for t in self.tensors), None))
+            return real(self, *a)
+        return method
+
+    mods = [m for n, m in list(sys.modules.items()) if m is not None and (n == "adamml_amd" or n.startswith("adamml_amd."))]
+    saved = [(m, n, getattr(m, n)) for m in mods for n, real in (("call", hip.call), ("ptr", hip.ptr)) if getattr(m, n, None) is real]
+    ws = runtime._on_wgrad_stream
+    saved += [(hip, "_stream", hip._stream), (ws, "__enter__", ws.__enter__), (ws, "__exit__", ws.__exit__), (hip, "_wgrad_ws", hip._wgrad_ws)]
+    try:
+        for m, n, _ in saved[:-4]:
+            setattr(m, n, call if n == "call" else ptr)
+        hip._stream = lambda: 0
+        hip._wgrad_ws = {}                      # (a scratch buffer grown by an earlier run would change the workspace sizes passed)
+        ws.__enter__, ws.__exit__ = marker("wgrad_stream_enter", ws.__enter__), marker("wgrad_stream_exit", ws.__exit__)
+        yield
+    finally:
+        for m, n, v in saved:
+            setattr(m, n, v)
+
+
+def trace(rows=ROWS):
+    """-> [Row]: the launches of every row, in order"""
+    import adamml_amd.resnet, adamml_amd.sound_mobilenet_v2, adamml_amd.policy_net  # noqa: F401,E401  (loaded before `call` is replaced)
+    log, out = [], []
+    with _patched(log):
+        for label, make in rows:
+            torch.manual_seed(0)
+            net, x, groups, mode, frozen = make()
+            for p in frozen:
+                p.requires_grad_(False)
+            n0 = len(log)
+            net.train(mode != "eval")
+            if mode == "grad":
+                for p in net.parameters():
+                    p.grad = torch.zeros_like(p) if p.requires_grad else None
+                y, tape = net._run(x, groups, True)
+                net.rt.bwd_arena.reset(x.device)
+                tape.grad_out = torch.zeros(tuple(y.shape))
+                tape.backward()
+            else:
+                with torch.no_grad():
+                    net._run(x, groups, False)
+            r = Row()
+            r.label, r.net, r.log = label, net, log[n0:]
+            r.lines = ["%s %r %r" % e for e in r.log]
+            r.counts = collections.Counter(e[0] for e in r.log if e[2] is not None)
+            out.append(r)
+    return out
+
+
+def digest(rows):
+    return hashlib.sha256("".join(ln + "\n" for r in rows for ln in ["# " + r.label] + r.lines).encode()).hexdigest()
+
+
+def main(argv):
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if "--package" in argv:
+        root = os.path.abspath(argv[argv.index("--package") + 1])
+    sys.path.insert(0, root)
+    if "--sites" in argv:
+        globals()["SITES"] = set()
+    rows = trace()
+    if SITES is not None:
+        # the `call(...)` statements of runtime.py no row reached (a launch is reported at a line of the statement's own span)
+        import ast
+        src = open(os.path.join(root, "adamml_amd", "runtime.py")).read()
+        hit = {ln for f, ln in SITES if f == "runtime.py"}
+        for node in sorted((n for n in ast.walk(ast.parse(src)) if isinstance(n, ast.Call)), key=lambda n: n.lineno):
+            if isinstance(node, ast.Call) and getattr(node.func, "id", None) == "call" and not hit & set(range(node.lineno, node.end_lineno + 1)):
+                print("unreached runtime.py:%d %s" % (node.lineno, src.split("\n")[node.lineno - 1].strip()[:100]))
+    for r in rows:
+        print("%-40s %5d launches, %2d entry points, %s" % (r.label, sum(r.counts.values()), len(r.counts), digest([r])[:16]))
+    total = collections.Counter()
+    for r in rows:
+        total += r.counts
+    print("all rows: %d launches, %d entry points" % (sum(total.values()), len(total)))
+    print("sha256 %s" % digest(rows))
+    if "--out" in argv:
+        with open(argv[argv.index("--out") + 1], "w") as f:
+            f.writelines(ln + "\n" for r in rows for ln in ["# " + r.label] + r.lines)
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])
