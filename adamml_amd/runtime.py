@@ -459,6 +459,8 @@ def conv_bn(rt, x, cs, bn, act, sole_consumer=False, last_consumer=False):
     else:
         vec = _bn_eval_vectors(rt, bn, C, dev)
         out = Lazy(y, vec[0], vec[1], act)
+    # nothing below this tensor takes a gradient (a frozen conv and BatchNorm on an input that needs none): its consumers stop here
+    out.requires_grad = bool(x.requires_grad or cs.weight.requires_grad or bn.weight.requires_grad or bn.bias.requires_grad)
     if rt.tape.need_grad:
         c = _ConvCall(rt, x, y, out, vec, bn, cs, d, count, act, sole_consumer, last_consumer, stem, macs, in_b, out_b, w_b, lab)
         rt.tape.record(lambda: _conv_backward(c))
@@ -1242,6 +1244,7 @@ def head(rt, x, fc, frames, dropout_p, keep_mask=None):
             call("adamml_head_bwd", ptr(g), ptr(keep_mask), inv_keep, ptr(fc.weight), ptr(gx), ptr(g_rows), clips, frames, h * w, C, K)
         if need_w:
             gemm_f32(g_rows if g_rows is not None else g, feat, out=fc.weight.grad, trans_a=True, trans_b=False, accumulate=True)   # dW += gy^T feat
+        if fc.bias is not None and fc.bias.requires_grad:        # (a frozen bias keeps its buffer as it is, or has none)
             call("adamml_colsum_f32", ptr(g), ptr(fc.bias.grad), clips, K, 1)                                                     # db += sum_n g
         if x.requires_grad:
             _accum_grad(x, gx)

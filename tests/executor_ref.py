@@ -2,7 +2,8 @@
 
 Plain CPU module (it never touches torch.cuda).  Three parts:
 
-Recorder.  Wraps the executor entry points (OPS; `gap` is the policy net's output op) in the namespaces of the model modules (MODULES) through pytest's monkeypatch and keeps,
+Recorder.  Wraps the executor entry points (OPS; `gap` is the policy net's output op) in the namespaces of the model modules and of the
+op-level graphs of tools/executor_ops.py (MODULES) through pytest's monkeypatch and keeps,
 for every call in order, the op, its bound arguments (flags included) and a snapshot of the returned Lazy: data, vec (scale, shift, mean,
 invstd), act, gs, the 1-bit mask of a residual add, and what NetRT.capture["aux"] filed for it (codes / mask / vec of conv_bn_add, idx of
 maxpool3x3s2).  The production `_run` methods are driven unchanged.
@@ -37,8 +38,11 @@ Bound, per parameter-gradient tensor:   rel-L2(hip, ref) <= K e_emu + alg_term
   the reference (e_emu = 0, alg_term = 0) has a zero bound.
 """
 import importlib
+import importlib.util
 import inspect
 import math
+import os
+import sys
 
 import torch
 import torch.nn.functional as F
@@ -52,7 +56,7 @@ K = 4.0
 SMALL = 1e-3
 EPS, MOMENTUM = 1e-5, 0.1
 OPS = ("conv_bn", "conv_stem1_bn", "conv_bn_add", "add_act", "materialize", "maxpool3x3s2", "temporal_pool", "head", "gap")
-MODULES = ("adamml_amd.resnet", "adamml_amd.mobilenet_common", "adamml_amd.sound_mobilenet_v2", "adamml_amd.policy_net")
+MODULES = ("adamml_amd.resnet", "adamml_amd.mobilenet_common", "adamml_amd.sound_mobilenet_v2", "adamml_amd.policy_net", "executor_ops")
 ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 2
 
 
@@ -71,6 +75,17 @@ def rel_l2(a, b):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ recorder
+def ops_module():
+    """tools/executor_ops.py (the op-level graphs, shared with tools/launch_trace.py) as the module `executor_ops`, loaded by path once"""
+    mod = sys.modules.get("executor_ops")
+    if mod is None:
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "executor_ops.py")
+        spec = importlib.util.spec_from_file_location("executor_ops", path)
+        mod = sys.modules["executor_ops"] = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+    return mod
+
+
 class Snap:
     """what a Lazy held when its producer returned (tensors by reference: the executor never rewrites them)"""
     __slots__ = ("data", "vec", "scale", "shift", "act", "gs", "mask", "alg", "shape")
@@ -114,7 +129,7 @@ class Recorder:
 
     def install(self, monkeypatch):
         for m in MODULES:
-            mod = importlib.import_module(m)
+            mod = ops_module() if m == "executor_ops" else importlib.import_module(m)
             for n in OPS:
                 if hasattr(mod, n):
                     monkeypatch.setattr(mod, n, self.wrap(n, getattr(mod, n)))
@@ -157,9 +172,12 @@ def taps2d(v, OH, OW):
 
 
 class Replay:
-    def __init__(self, calls, groups, params, running, dtype=torch.float64, force=True, round_grads=False, check=None, training=True):
+    def __init__(self, calls, groups, params, running, dtype=torch.float64, force=True, round_grads=False, check=None, training=True, recomputed_z=False):
         """params: id(Parameter) -> leaf of `dtype`; running: id(BatchNorm module) -> [running_mean, running_var, num_batches_tracked]
-        as they were BEFORE the recorded step (updated in place here, in float64)."""
+        as they were BEFORE the recorded step (updated in place here, in float64).
+        recomputed_z (emulator only): the BatchNorm-backward reduction of every conv_bn_add read the raw conv output as Lazy.recompute wrote
+        it, rounded to bf16 (no producer of its gradient left partial sums) -- one more storage point of the run the emulator then rounds at."""
+        self.recomputed_z = bool(recomputed_z and round_grads)
         self.calls, self.G, self.p, self.running = calls, groups, params, running
         self.dt, self.force, self.round, self.training = dtype, force, round_grads, training
         self.check = (dtype == torch.float64 and force) if check is None else check
@@ -334,6 +352,8 @@ class Replay:
         a, exact = self._operand(x, True)
         w = self._weight(cs, True)
         z = self._hook(a @ w.reshape(cs.cout, -1).t())                              # never stored: no forcing
+        if self.recomputed_z:
+            z = st(z, bf(z.detach()))
         code_t, mask_t, vec = c.aux if c.aux is not None else (None, None, None)
         scale, shift = self._bn(i, z, bn, None if vec is None else _VecOnly(vec, z.shape),
                                 stat_err=lambda zg: gram_stat_err(exact.reshape(G, -1, exact.shape[-1]), w.detach().double().reshape(cs.cout, -1)))
@@ -508,6 +528,12 @@ class Replay:
             sc, sh, gs = _svec(sn)
             ref, ab, n = E.gap_fwd_ref(_cpu(sn.data), sc, sh, gs, sn.act, NT // self.G, H * W, self.G)
             self.fwd[i] = ("gap", R.err_ratio(_cpu(c.out[0]), ref, ab, n, R.RHO_F32))
+
+    def output_of(self, lz):
+        """Designates the output of a graph that ends in neither `head` nor `gap` (tools/executor_ops.py): the value of the Lazy `lz`, a
+        tensor one of the recorded calls returned.  backward / backward_alg then take the gradient w.r.t. that value [G*N, H, W, C]."""
+        self.logits = self._val(lz)
+        return self
 
     def backward(self, g):
         """-> id(Parameter) -> gradient"""

@@ -6,7 +6,9 @@ Every row drives one forward and one backward of a real model through its own `_
   * checks every BatchNorm's vectors, running statistics and num_batches_tracked,
   * checks every parameter gradient against  K e_emu + alg_term  (K = 4, shared with the CPU test),
   * asserts a written expectation of the entry points that ran (hip.LaunchProfiler).
-Shapes are the smallest that reach the branch (the host-side *_supported / *_streams probes answer without a GPU)."""
+Shapes are the smallest that reach the branch (the host-side *_supported / *_streams probes answer without a GPU).
+Partial freezes run in two variants (the frozen parameters' gradient buffers kept, or none at all); the forward-only rows (train mode
+under no_grad, eval mode) replay the forward alone; the op-level rows drive the graphs of tools/executor_ops.py through the same run_row."""
 import collections
 import time
 
@@ -52,7 +54,27 @@ def cls_of(name, t):
     return "fc" if name.startswith(("fc.", "classifier.")) else "conv" if t.dim() == 4 else "gamma" if name.endswith("weight") else "beta"
 
 
-def run_row(net, x, groups, out_cols, monkeypatch, frozen=(), label="", frozen_buffers=True):
+def check_forward(rep, net, running=True):
+    """the common checks of a replayed forward: every op teacher-forced, the BatchNorm vectors, the undecided share, the running statistics"""
+    bad = {i: v for i, v in rep.fwd.items() if not v[1] <= 1.0}
+    assert not bad, "teacher-forced forward: %s" % bad
+    badv = {i: v for i, v in rep.vec_ratio.items() if not v <= 1.0}
+    assert not badv, "BatchNorm vectors: %s" % badv
+    assert rep.undecided_share() <= FR.UNDECIDED_CAP
+    if not running:
+        return 0.0
+    stat = 0.0
+    for m in net.modules():
+        if isinstance(m, torch.nn.BatchNorm2d) and id(m) in rep.stat_tol:
+            trm, trv = rep.stat_tol[id(m)]
+            stat = max(stat, E.vec_ratio(m.running_mean, rep.running[id(m)][0], trm), E.vec_ratio(m.running_var, rep.running[id(m)][1], trv))
+            assert int(m.num_batches_tracked) == rep.running[id(m)][2]
+    print("  running statistics max err/tol %.3f" % stat)
+    assert stat <= 1.0
+    return stat
+
+
+def run_row(net, x, groups, out_cols, monkeypatch, frozen=(), label="", frozen_buffers=True, recomputed_z=False):
     """-> dict: names (Counter of entry points), log ([(entry point, args)]), rep (the float64 replay), res (id -> (err, bound)), ..."""
     t0 = time.time()
     net.to(DEV)
@@ -66,7 +88,7 @@ def run_row(net, x, groups, out_cols, monkeypatch, frozen=(), label="", frozen_b
         net.flat_owner.ensure_grads()
     else:                                          # (the policy trunk's flat buffers belong to the joint net around it)
         for p in net.parameters():
-            p.grad = torch.zeros_like(p)
+            p.grad = torch.zeros_like(p) if p.requires_grad else None
     sentinel = {}
     for m in (frozen if frozen_buffers else ()):
         for p in m.parameters():
@@ -100,9 +122,12 @@ def run_row(net, x, groups, out_cols, monkeypatch, frozen=(), label="", frozen_b
     t1 = time.time()
     got = {id(p): p.grad.detach().cpu().clone() for _, p in named if p.requires_grad}
     rep = X.Replay(rec.calls, groups, p64, run0)
+    emu = X.Replay(rec.calls, groups, p32, X.running_of(net), dtype=torch.float32, round_grads=True, recomputed_z=recomputed_z)
+    if getattr(net, "out_lazy", None) is not None:      # an op-level graph (tools/executor_ops.py): no head, its output is the Lazy it kept
+        rep.output_of(net.out_lazy)
+        emu.output_of(net.out_lazy)
     ref = rep.backward(g)
     pert = rep.backward_alg(g)
-    emu = X.Replay(rec.calls, groups, p32, X.running_of(net), dtype=torch.float32, round_grads=True)
     bnd = X.bounds(ref, emu.backward(g), X.alg_terms(ref, pert))
     res = X.compare(got, ref, bnd)
     t2 = time.time()
@@ -129,21 +154,7 @@ def run_row(net, x, groups, out_cols, monkeypatch, frozen=(), label="", frozen_b
         if b > 0:
             share[cls_of(names[k], got[k])] = max(share[cls_of(names[k], got[k])], (b - X.K * bnd[k][0]) / b)
     print("  largest alg_term / bound per class:", {c: round(v, 3) for c, v in share.items()})
-    # ---- forward, op by op
-    bad = {i: v for i, v in rep.fwd.items() if not v[1] <= 1.0}
-    assert not bad, "teacher-forced forward: %s" % bad
-    badv = {i: v for i, v in rep.vec_ratio.items() if not v <= 1.0}
-    assert not badv, "BatchNorm vectors: %s" % badv
-    assert rep.undecided_share() <= FR.UNDECIDED_CAP
-    # ---- running statistics
-    stat = 0.0
-    for m in net.modules():
-        if isinstance(m, torch.nn.BatchNorm2d) and id(m) in rep.stat_tol:
-            trm, trv = rep.stat_tol[id(m)]
-            stat = max(stat, E.vec_ratio(m.running_mean, rep.running[id(m)][0], trm), E.vec_ratio(m.running_var, rep.running[id(m)][1], trv))
-            assert int(m.num_batches_tracked) == rep.running[id(m)][2]
-    print("  running statistics max err/tol %.3f" % stat)
-    assert stat <= 1.0
+    check_forward(rep, net)
     # ---- gradients
     k, wr = X.worst(res)
     print("  worst gradient err/bound %.3f at %s" % (wr, names[k]))
@@ -154,7 +165,7 @@ def run_row(net, x, groups, out_cols, monkeypatch, frozen=(), label="", frozen_b
         assert p.grad is buf and bool((buf == 0.25).all()), "a frozen parameter's gradient buffer was touched: " + names[i]
     if not frozen_buffers:                         # no algebraic, dual or weight-gradient path was handed (or made) a buffer for them
         assert all(p.grad is None for m in frozen for p in m.parameters())
-    return dict(names=counts, log=log, rep=rep, res=res, pnames=names, net=net, ref=ref, got=got)
+    return dict(names=counts, log=log, rep=rep, res=res, pnames=names, net=net, ref=ref, got=got, out=out.detach().cpu().clone())
 
 
 def resnet(frames, **kw):
@@ -295,28 +306,38 @@ def _mobilenet_expectations(n):
     assert n["adamml_conv_bwd_data_dual"] >= 17                      # every projection (and the expansions behind a fused depthwise backward)
 
 
-def test_sound_mobilenet_v2(monkeypatch):
+def sound_net():
+    """-> (net, the fp32 [B, G, H, W] input, G, the shape of the logits)"""
     from adamml_amd.sound_mobilenet_v2 import MobileNetV2
     torch.manual_seed(0)
     net = MobileNetV2(num_classes=11, input_channels=1, dropout=0.0)
     randomize_convs(net, 2)
     randomize(net, 3)
     G, B = 2, 4
-    x = torch.randn(B, G, 64, 64, generator=gen(6))
-    r = run_row(net, x, G, lambda xx: (G * B, 11), monkeypatch, label="sound-mobilenetv2-g2")
-    assert r["names"]["adamml_conv_stem1_fwd"] == 1
-    _mobilenet_expectations(r["names"])
+    return net, torch.randn(B, G, 64, 64, generator=gen(6)), G, (G * B, 11)
 
 
-def test_policy_mobilenet_v2(monkeypatch):
+def policy_net():
+    """-> (net, 2 x 4 clips of 4 bf16 frames 64 x 64, G, the shape of the features)"""
     from adamml_amd.policy_net import MobileNetV2
     torch.manual_seed(0)
     net = MobileNetV2(num_frames=4, input_channels=3)
     randomize_convs(net, 4)
     randomize(net, 5)
     G, clips = 2, 4
-    x = frames_input(G * clips * 4, 64, 3, 8, 7)
-    r = run_row(net, x, G, lambda xx: (G * clips * net.out_frames, 1280), monkeypatch, label="policy-mobilenetv2-g2")
+    return net, frames_input(G * clips * 4, 64, 3, 8, 7), G, (G * clips * net.out_frames, 1280)
+
+
+def test_sound_mobilenet_v2(monkeypatch):
+    net, x, G, shape = sound_net()
+    r = run_row(net, x, G, lambda xx: shape, monkeypatch, label="sound-mobilenetv2-g2")
+    assert r["names"]["adamml_conv_stem1_fwd"] == 1
+    _mobilenet_expectations(r["names"])
+
+
+def test_policy_mobilenet_v2(monkeypatch):
+    net, x, G, shape = policy_net()
+    r = run_row(net, x, G, lambda xx: shape, monkeypatch, label="policy-mobilenetv2-g2")
     assert r["names"]["adamml_temporal_pool_fwd"] == 2 and r["names"]["adamml_temporal_pool_bwd_res"] == 2
     _mobilenet_expectations(r["names"])
 
@@ -368,3 +389,268 @@ def test_eval_vector_cache_follows_raw_pointer_writes(monkeypatch):
         assert not torch.equal(b, c)
     finally:
         net.rt.capture = None
+
+
+# ------------------------------------------------------------------------------------------------- partial freezes of the other models
+class Params:
+    """a frozen set given as parameters (run_row freezes `.parameters()` of every entry)"""
+
+    def __init__(self, params):
+        self.params = list(params)
+
+    def parameters(self):
+        return self.params
+
+
+def depthwise_weights(net):
+    return [m.weight for m in net.modules() if isinstance(m, torch.nn.Conv2d) and m.groups > 1]
+
+
+def all_but(net, params):
+    keep = {id(p) for p in params}
+    return [p for p in net.parameters() if id(p) not in keep]
+
+
+def no_frozen_weight_gradient(r):
+    """-> the entry points that compute a weight gradient (the fused depthwise backward among them) and ran, with their counts"""
+    n = r["names"]
+    return {k: v for k, v in n.items() if ("bwd_weight" in k or k in ("adamml_alg_wgrad_combine", "adamml_dwconv_bwd_fused")) and v}
+
+
+BUFFERS = ["grad-buffers-kept", "grad-none"]
+
+
+@pytest.mark.parametrize("buffers", BUFFERS)
+def test_policy_mobilenet_v2_frozen_depthwise(monkeypatch, buffers):
+    """The 17 depthwise weights frozen: no fused depthwise backward (it would write their gradient); the depthwise data gradient still hands
+    the expansion its BatchNorm-backward sums (adamml_dwconv_bwd_data_bn)."""
+    net, x, G, shape = policy_net()
+    r = run_row(net, x, G, lambda xx: shape, monkeypatch, frozen=[Params(depthwise_weights(net))], label="policy-mobilenetv2-frozen-depthwise-" + buffers,
+                frozen_buffers=buffers == BUFFERS[0])
+    n = r["names"]
+    assert n["adamml_dwconv_bwd_fused"] == 0 and n["adamml_dwconv_bwd_data_bn"] == 17 and n["adamml_dwconv_bwd_weight"] == 0
+    assert n["adamml_conv_bwd_weight"] == 35 and n["adamml_conv_bwd_data_dual"] == 17
+    assert len(r["res"]) == len(list(net.parameters())) - 17
+
+
+@pytest.mark.parametrize("buffers", BUFFERS)
+def test_policy_mobilenet_v2_depthwise_only(monkeypatch, buffers):
+    """Only the depthwise weights train.  The first block's depthwise conv reads the stem's output, below which nothing takes a gradient:
+    its backward is the unfused weight gradient alone.  The other 16 take the fused backward (their expansions' inputs lead to trainable
+    depthwise weights further down).  No dense conv's weight gradient runs."""
+    net, x, G, shape = policy_net()
+    dw = depthwise_weights(net)
+    r = run_row(net, x, G, lambda xx: shape, monkeypatch, frozen=[Params(all_but(net, dw))], label="policy-mobilenetv2-depthwise-only-" + buffers,
+                frozen_buffers=buffers == BUFFERS[0])
+    n = r["names"]
+    assert n["adamml_dwconv_bwd_weight"] >= 1
+    assert n["adamml_dwconv_bwd_weight"] + n["adamml_dwconv_bwd_fused"] == 17
+    assert set(no_frozen_weight_gradient(r)) <= {"adamml_dwconv_bwd_weight", "adamml_dwconv_bwd_fused"}, no_frozen_weight_gradient(r)
+    assert len(r["res"]) == 17 and {r["got"][k].dim() for k in r["res"]} == {4}
+
+
+@pytest.mark.parametrize("buffers", BUFFERS)
+def test_sound_mobilenet_v2_frozen_batchnorm(monkeypatch, buffers):
+    """Every 1-D parameter frozen (gamma, beta, the classifier's bias): the BatchNorms still normalise with batch statistics and still
+    update running mean / var / num_batches_tracked (run_row's common checks), their backward still carries the mean and variance terms.
+    Entry points, written down: the same backward forms as the all-trainable row (the data gradients do not depend on who trains),
+    adamml_bn_bwd_finalize[_affine] with null dgamma / dbeta, and no adamml_colsum_f32 (the classifier's bias gradient)."""
+    net, x, G, shape = sound_net()
+    r = run_row(net, x, G, lambda xx: shape, monkeypatch, frozen=[Params([p for p in net.parameters() if p.dim() == 1])],
+                label="sound-mobilenetv2-frozen-batchnorm-" + buffers, frozen_buffers=buffers == BUFFERS[0])
+    n = r["names"]
+    assert n["adamml_bn_finalize"] == 52 and n["adamml_conv_stem1_fwd"] == 1 and n["adamml_conv_stem1_bwd_weight"] == 1
+    assert n["adamml_dwconv_bwd_fused"] == 17 and n["adamml_conv_bwd_data_dual"] == 17 and n["adamml_conv_bwd_weight"] == 34
+    assert n["adamml_bn_bwd_finalize"] + n["adamml_bn_bwd_finalize_affine"] == 52
+    assert n["adamml_gemm_f32"] == 1 and n["adamml_colsum_f32"] == 0
+    # null dgamma / dbeta in every BatchNorm-backward finalize (arguments 6 and 7)
+    fin = [a for name, a in r["log"] if name in ("adamml_bn_bwd_finalize", "adamml_bn_bwd_finalize_affine")]
+    assert len(fin) == 52 and all(a[6] is None and a[7] is None for a in fin)
+    assert {r["got"][k].dim() for k in r["res"]} == {2, 4}
+
+
+@pytest.mark.parametrize("buffers", BUFFERS)
+def test_resnet50_frozen_conv_weights(monkeypatch, buffers):
+    """Every 4-D parameter frozen, the BatchNorms and fc train: no weight gradient, no algebraic backward (it exists to save the pass the
+    weight gradient needs) and no conv_bn_add in train mode (its backward is the algebraic one): conv_bn + add_act everywhere."""
+    net = resnet(4)
+    r = resnet_row(net, 44, 2, 1, monkeypatch, "resnet50-frozen-conv-weights-" + buffers,
+                   frozen=lambda n: [Params([p for p in n.parameters() if p.dim() == 4])], frozen_buffers=buffers == BUFFERS[0])
+    n = r["names"]
+    assert not no_frozen_weight_gradient(r), no_frozen_weight_gradient(r)
+    assert not [k for k in n if "_bwd_weight" in k] and n["adamml_alg_wgrad_combine"] == 0
+    assert n["adamml_gram_colsum"] == 0 and n["adamml_alg_pack"] == 0 and n["adamml_conv_bwd_data_alg"] == 0
+    assert n["adamml_conv_fwd_bn_add"] + n["adamml_conv_fwd_bn_add_next"] + n["adamml_conv_fwd_bn_add_tpool"] == 0
+    assert n["adamml_conv_fwd"] == 52 and n["adamml_bn_act_add_mask"] == 16 and n["adamml_conv_bwd_data_dual"] == 8
+    assert not [k for k in r["res"] if r["got"][k].dim() == 4] and len(r["res"]) == 2 * 53 + 2
+
+
+# ------------------------------------------------------------------------------------------------------------------- forward-only rows
+def forward_only(net, x, groups, monkeypatch, label, training, nbn):
+    """One forward under torch.no_grad() with need_grad = False, replayed (no backward) -> (output, Counter of entry points, replay).
+    training: net.train() (batch statistics, running statistics updated) or net.eval() (the affines of the running statistics)."""
+    t0 = time.time()
+    net.to(DEV)
+    if getattr(net, "flat_owner", None) is not None:
+        net.flat_owner.ensure(torch.device(DEV, torch.cuda.current_device()))
+    net.train(training)
+    named = list(net.named_parameters())
+    p64, _ = X.leaves(named, torch.float64)
+    run0 = X.running_of(net)
+    entered = []
+    with monkeypatch.context() as mp:
+        rec = X.Recorder()
+        rec.install(mp)
+        enter = runtime._on_wgrad_stream.__enter__
+        mp.setattr(runtime._on_wgrad_stream, "__enter__", lambda self: (entered.append(1), enter(self))[1])
+        log = []
+        real_call = runtime.call
+        mp.setattr(runtime, "call", lambda name, *a: (log.append((name, a)), real_call(name, *a))[1])
+        rt = net.rt
+        rt.capture = {"aux": {}}
+        hip.profiler = hip.LaunchProfiler()
+        try:
+            with torch.no_grad():
+                out, tape = net._run(x.to(DEV), groups, False)
+            torch.cuda.synchronize()
+            counts = collections.Counter(r[0] for r in hip.profiler.records)
+        finally:
+            hip.profiler = None
+            rt.capture = None
+    t1 = time.time()
+    rep = X.Replay(rec.calls, groups, p64, run0, training=training)
+    fw = collections.defaultdict(float)
+    for op, r in rep.fwd.values():
+        fw[op] = max(fw[op], r)
+    print("\nROW %s: hip %.2f s, replay %.2f s, %d ops, %d BatchNorm vectors" % (label, t1 - t0, time.time() - t1, len(rec.calls), len(rep.vec_ratio)))
+    print("  entry points:", {k: v for k, v in sorted(counts.items())})
+    print("  forward max err/tol:", {k: round(v, 3) for k, v in fw.items()}, "vectors %.3f" % max(rep.vec_ratio.values()),
+          "undecided share %.5f" % rep.undecided_share())
+    assert len(rep.fwd) == len(rec.calls) and len(rep.vec_ratio) == nbn, (len(rep.fwd), len(rec.calls), len(rep.vec_ratio))
+    check_forward(rep, net, running=training)
+    if training:
+        assert len(rep.stat_tol) == nbn
+    else:                     # eval mode leaves the running statistics alone
+        for m in net.modules():
+            if isinstance(m, torch.nn.BatchNorm2d):
+                assert torch.equal(m.running_mean.cpu().double(), run0[id(m)][0]) and int(m.num_batches_tracked) == run0[id(m)][2]
+    assert not [k for k in counts if "_bwd" in k], counts
+    assert not entered and not tape.fns
+    # nothing was allocated for a backward: no mask of an add (argument 10 / 12), no pool codes or selected-z tensor (last / argument 7)
+    where = {"adamml_bn_act_add_mask": 10, "adamml_conv_fwd_bn_add": 12, "adamml_conv_fwd_bn_add_next": 12, "adamml_conv_fwd_bn_add_tpool": 13,
+             "adamml_maxpool2d_fwd": 7}
+    assert not [(name, a[where[name]]) for name, a in log if name in where and a[where[name]] is not None]
+    assert rt.pre_pending == 0 and rt.pre_dropped == 0
+    assert bool(torch.isfinite(out).all())
+    return out.detach().cpu().clone(), counts, rep
+
+
+def test_resnet50_train_nograd(monkeypatch):
+    """net.train() under torch.no_grad() (tile-g3 shape): conv_bn_add on `conv_bn_add_supported(..., need_grad=False)`, no masks, no codes,
+    running statistics updated.  The grad-mode step straight after meets its bound: nothing of the tape state was left behind."""
+    net = resnet(4)
+    x = frames_input(3 * 2 * 4, 44, 3, net.input_cpad(44, 44), 5)
+    out, n, rep = forward_only(net, x, 3, monkeypatch, "resnet50-train-nograd", True, 53)
+    assert n["adamml_bn_finalize"] == 53 and n["adamml_gram_stats"] == 7
+    assert n["adamml_conv_fwd_bn_add"] + n["adamml_conv_fwd_bn_add_next"] + n["adamml_conv_fwd_bn_add_tpool"] == 7
+    r = resnet_row(net, 44, 2, 3, monkeypatch, "resnet50-grad-step-after-train-nograd")
+    assert r["names"]["adamml_conv_fwd_bn_add_tpool"] == 2 and net.rt.pre_pending == 0
+    print("  no-grad logits == grad-mode logits bit for bit: %s" % torch.equal(out, r["out"]))
+
+
+def test_policy_mobilenet_v2_train_nograd(monkeypatch):
+    net, x, G, shape = policy_net()
+    out, n, rep = forward_only(net, x, G, monkeypatch, "policy-mobilenetv2-train-nograd", True, 52)
+    assert tuple(out.shape) == shape
+    assert n["adamml_bn_finalize"] == 52 and n["adamml_dwconv_fwd"] == 17 and n["adamml_temporal_pool_fwd"] == 2
+    assert n["adamml_conv_fwd_bn_add"] == 0           # train mode: the projections are not expanding convs, no Gram-matrix statistics
+    r = run_row(net, x, G, lambda xx: shape, monkeypatch, label="policy-mobilenetv2-grad-step-after-train-nograd")
+    _mobilenet_expectations(r["names"])
+    print("  no-grad features == grad-mode features bit for bit: %s" % torch.equal(out, r["out"]))
+
+
+def _mobilenet_eval(net, x, G, shape, monkeypatch, label):
+    # non-trivial running statistics first (fresh ones make every eval affine (gamma / sqrt(1 + eps), beta)): one train-mode forward
+    net.to(DEV)
+    if getattr(net, "flat_owner", None) is not None:
+        net.flat_owner.ensure(torch.device(DEV, torch.cuda.current_device()))
+    net.train()
+    with torch.no_grad():
+        net._run(x.to(DEV), G, False)
+    torch.cuda.synchronize()
+    assert all(float(m.running_mean.abs().max()) > 0 for m in net.modules() if isinstance(m, torch.nn.BatchNorm2d))
+    out, n, rep = forward_only(net, x, G, monkeypatch, label, False, 52)
+    assert tuple(out.shape) == shape
+    assert n["adamml_bn_finalize"] == 0 and n["adamml_bn_eval_affine"] == 52
+    assert n["adamml_conv_fwd_bn_add"] == 10          # eval mode: every residual block's projection + BatchNorm + add is one kernel
+    return n
+
+
+def test_sound_mobilenet_v2_eval(monkeypatch):
+    """the eval forward AdaMML._forward_skipping runs at inference: the fp32 one-channel [B, G, H, W] stem, 52 eval affines"""
+    net, x, G, shape = sound_net()
+    n = _mobilenet_eval(net, x, G, shape, monkeypatch, "sound-mobilenetv2-eval")
+    assert n["adamml_conv_stem1_fwd"] == 1 and n["adamml_head_fwd"] == 1
+
+
+def test_policy_mobilenet_v2_eval(monkeypatch):
+    """bf16 frames, the two temporal pools, 52 eval affines"""
+    net, x, G, shape = policy_net()
+    n = _mobilenet_eval(net, x, G, shape, monkeypatch, "policy-mobilenetv2-eval")
+    assert n["adamml_temporal_pool_fwd"] == 2 and n["adamml_gap_fwd"] == 1
+
+
+# ----------------------------------------------------------------------------------------------- op-level rows (tools/executor_ops.py)
+def ops_row(label, monkeypatch, **kw):
+    O = X.ops_module()
+    net = O.make(label)
+    randomize_convs(net, 8)
+    randomize(net, 9)
+    x = net.make_input()
+    return run_row(net, x, O.GROUPS, net.out_shape, monkeypatch, label=label, **kw)
+
+
+def launches(r, name):
+    return [a for n, a in r["log"] if n == name]
+
+
+def test_ops_shared_depthwise_input(monkeypatch):
+    r = ops_row("ops-shared-depthwise-input", monkeypatch)
+    n = r["names"]
+    assert n["adamml_dwconv_bwd_weight"] == 1 and n["adamml_act_bwd_from_output"] == 1 and n["adamml_dwconv_bwd_fused"] == 0
+    assert [a[-1] for a in launches(r, "adamml_dwconv_bwd_data")] == [1]            # acc = 1: it adds to the gradient already there
+
+
+@pytest.mark.parametrize("form", ["conv_bn", "conv_bn_add"])
+def test_ops_alg_gemm_arm(monkeypatch, form):
+    """256 -> 512: the Cin >= ALG_GEMM_CIN arm of _conv1x1_backward_alg at G = 2 (W^T diag(B_g) W and W G_g through adamml_gemm_f32, read back
+    as m_pre / wg_pre).  conv_bn_add: adamml_conv_fwd_bn_add_supported admits the descriptor; G comes from the forward."""
+    fused = form == "conv_bn_add"
+    # conv_bn_add never stores the raw conv output; here nothing hands its BatchNorm backward partial sums, so adamml_residual_bwd reads it
+    # as Lazy.recompute writes it, in bf16: a storage point the emulator is told of (the second adamml_conv_fwd is that recomputation)
+    r = ops_row("ops-alg-gemm-arm" + ("-fused" if fused else ""), monkeypatch, recomputed_z=fused)
+    n = r["names"]
+    assert n["adamml_conv_fwd"] == 2 and n["adamml_residual_bwd"] == (1 if fused else 0)
+    assert n["adamml_gemm_f32"] == 2 and n["adamml_alg_pack"] == 1 and n["adamml_alg_wgrad_combine"] == 1 and n["adamml_conv_bwd_data_alg"] == 1
+    assert [a[2] is not None for a in launches(r, "adamml_alg_pack")] == [True]                    # m_pre
+    assert [a[4] is not None for a in launches(r, "adamml_alg_wgrad_combine")] == [True]           # wg_pre
+    assert [(a[-3], a[-2], a[-1]) for a in launches(r, "adamml_alg_pack")] == [(512, 256, 2)]
+    assert n["adamml_gram_colsum"] == 1 and n["adamml_conv_fwd_bn_add"] == (1 if form == "conv_bn_add" else 0)
+    assert len(r["rep"].alg) == 1
+
+
+@pytest.mark.parametrize("order,acc", [("pool-first", 1), ("conv-first", 0)])
+def test_ops_unfused_maxpool(monkeypatch, order, acc):
+    r = ops_row("ops-unfused-maxpool-" + order, monkeypatch)
+    n = r["names"]
+    assert [a[-1] for a in launches(r, "adamml_maxpool2d_bwd")] == [acc] and n["adamml_maxpool2d_bwd_bn_apply"] == 0
+    assert [a[-1] for a in launches(r, "adamml_conv_bwd_data")] == [1 - acc]
+    # h's gradient is that of its activated value: its own BatchNorm backward applies the ReLU mask (act = 1) in the reduce and apply passes
+    assert [a[3] for a in launches(r, "adamml_bn_bwd_reduce")] == [1] and 1 in [a[3] for a in launches(r, "adamml_bn_bwd_apply")]
+
+
+def test_ops_accumulating_add(monkeypatch):
+    r = ops_row("ops-accumulating-add", monkeypatch)
+    accum = [a for a in launches(r, "adamml_bn_act_add") if a[1] is None and a[2] is None and a[5] is not None]
+    assert len(accum) >= 1 and all(a[0] == a[9] for a in accum)          # in place: t.grad += g
+    assert r["names"]["adamml_residual_bwd"] == 2

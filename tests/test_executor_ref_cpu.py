@@ -1,6 +1,7 @@
 """tests/executor_ref.py can fail: its replay is anchored to torch, and a torch emulation of the host executor (bf16 storage at the
 runtime's storage points, Gram-matrix statistics for conv_bn_add, the algebraic dW = A.(g'^T a) + B.(W G) + C (x) s and dx forms in
-float32) passes the shared bound at K while each of seven planted executor defects misses it by at least a factor 2.  No GPU."""
+float32) passes the shared bound at K while each of seven planted executor defects misses it by at least a factor 2.  The op-level
+graphs of tools/executor_ops.py (the arms no model reaches) get the same three anchors at the end of the file, with six more defects.  No GPU."""
 import math
 import types
 
@@ -105,7 +106,7 @@ class AlgConvBN(torch.autograd.Function):
     """o = BatchNorm(bf16(bf16(W) a)) of a 1x1 conv, train mode, per group; backward in the algebraic form of _conv1x1_backward_alg:
     it reads g', a and the float32 MASTER weight, never z.  gram: statistics from G = a^T a and s = sum a (conv_bn_add)."""
     @staticmethod
-    def forward(ctx, a, w, gamma, beta, gram, hold, no_mean_term, share_vec):
+    def forward(ctx, a, w, gamma, beta, gram, hold, no_mean_term, share_vec, gemm_defect=0, direct=False):
         G, P, Cin = a.shape
         wb = bf(w)
         zb = bf(a @ wb.t())
@@ -122,29 +123,45 @@ class AlgConvBN(torch.autograd.Function):
         shift = beta - mean * scale
         hold.y, hold.vec, hold.var = zb, torch.stack([scale, shift, mean, inv], 1), var
         ctx.save_for_backward(a, w, gamma, mean, inv)
-        ctx.flags = (no_mean_term, share_vec)
+        ctx.flags = (no_mean_term, share_vec, gemm_defect)
+        ctx.zb = zb if direct else None
         return zb * scale.unsqueeze(1) + shift.unsqueeze(1)
 
     @staticmethod
     def backward(ctx, g):
         a, w, gamma, mean, inv = ctx.saved_tensors
-        no_mean_term, share_vec = ctx.flags
+        no_mean_term, share_vec, gemm_defect = ctx.flags
+        Cout = w.shape[0]
         G, P, Cin = a.shape
         g = bf(g)
         if share_vec:                                   # planted (e): every group reads group 0's vectors
             mean, inv = mean[:1].expand_as(mean), inv[:1].expand_as(inv)
         s1 = g.sum(1)
         Pm = torch.einsum("gpo,gpi->goi", g, a)
-        s2 = inv * ((w.unsqueeze(0) * Pm).sum(2) - (0.0 if no_mean_term else mean * s1))          # adamml_alg_sumfix
+        if ctx.zb is not None:          # the producer of g' left no partial sums: adamml_bn_bwd_reduce / adamml_residual_bwd read the stored (recomputed) z
+            s2 = (g * ((ctx.zb - mean.unsqueeze(1)) * inv.unsqueeze(1))).sum(1)
+        else:
+            s2 = inv * ((w.unsqueeze(0) * Pm).sum(2) - (0.0 if no_mean_term else mean * s1))          # adamml_alg_sumfix
         k0, k1, k2 = gamma * inv, s1 / P, s2 / P
         A, B, C = k0, -k0 * k2 * inv, k0 * (k2 * mean * inv - k1)
         wa = bf(w.t().unsqueeze(0) * A.unsqueeze(1))                                              # adamml_alg_pack: bf16 entries
-        M = bf(torch.einsum("oi,go,oj->gij", w, B, w))
+        if Cin >= 256:
+            # the ALG_GEMM_CIN arm: W^T diag(B_g) W for all groups as one product [G*Cin, Cout] x [Cout, Cin], W G_g as [Cout, Cin] x [Cin, G*Cin].
+            # planted (6): the operand is laid out [Cout][Cin][G] (1) / [Cin][Cin][G] (2) and read as [..][G][Cin] -- the same bytes at G = 1
+            wb = (w.unsqueeze(2) * B.t().unsqueeze(1)) if gemm_defect == 1 else (w.unsqueeze(1) * B.t().unsqueeze(2))
+            M = bf((wb.reshape(Cout, G * Cin).t() @ w).reshape(G, Cin, Cin))
+        else:
+            M = bf(torch.einsum("oi,go,oj->gij", w, B, w))
         epi = torch.einsum("oi,go->gi", w, C)
         dx = bf(torch.einsum("gpo,gco->gpc", g, wa) + torch.einsum("gpj,gcj->gpc", a, M) + epi.unsqueeze(1))
         Gm, sv = a.transpose(1, 2) @ a, a.sum(1)
-        dw = (A.unsqueeze(2) * Pm + B.unsqueeze(2) * torch.einsum("oj,gji->goi", w, Gm) + C.unsqueeze(2) * sv.unsqueeze(1)).sum(0)
-        return dx, dw, s2.sum(0), s1.sum(0), None, None, None, None
+        if Cin >= 256:
+            gm = Gm.permute(1, 2, 0) if gemm_defect == 2 else Gm.permute(1, 0, 2)
+            WG = (w @ gm.reshape(Cin, G * Cin)).reshape(Cout, G, Cin).permute(1, 0, 2)
+        else:
+            WG = torch.einsum("oj,gji->goi", w, Gm)
+        dw = (A.unsqueeze(2) * Pm + B.unsqueeze(2) * WG + C.unsqueeze(2) * sv.unsqueeze(1)).sum(0)
+        return dx, dw, s2.sum(0), s1.sum(0), None, None, None, None, None, None
 
 
 class Emu:
@@ -159,6 +176,7 @@ class Emu:
         self.count = {}
         self.state = {}
         self.logits = None
+        self.direct_sums = False      # True: no producer of g' leaves partial sums (the op-level graphs): sum(g' zhat) from the stored z, no sumfix
 
     def _hit(self, kind):
         i = self.count.get(kind, 0)
@@ -166,13 +184,16 @@ class Emu:
         return self.defects.get(kind) == i
 
     def use(self, x):
-        st = self.state.setdefault(id(x), [getattr(x, "val", None), 0, x])
+        st = self.state.setdefault(id(x), [getattr(x, "val", None), 0, x, len(self.state)])
         if st[0] is None:
             st[0] = x.data.float()
         k = st[1]
         st[1] += 1
         # planted (d): the second consumer in tape order (conv1; reversed first) loses its gradient to the downsample's write
         drop = k == 1 and self._hit("two_consumers")
+        # planted (1), (2): (t, k) -- the k-th consumer (forward order) of the t-th tensor that got a consumer loses its gradient: the consumer
+        # recorded BEFORE it runs its backward AFTER it and overwrote the gradient it had to add to (acc dropped)
+        drop = drop or self.defects.get("drop_use") == (st[3], k)
         return Branch.apply(st[0], drop)
 
     def _running(self, bn, mean, var, n):
@@ -206,7 +227,8 @@ class Emu:
         hold = types.SimpleNamespace()
         a = a4.reshape(G, -1, a4.shape[-1])
         hit_c, hit_e = (self._hit("sumfix"), self._hit("group_vec")) if gram else (False, False)
-        o = AlgConvBN.apply(a, self.p[id(cs.weight)].reshape(cs.cout, -1), self.p[id(bn.weight)], self.p[id(bn.bias)], gram, hold, hit_c, hit_e)
+        o = AlgConvBN.apply(a, self.p[id(cs.weight)].reshape(cs.cout, -1), self.p[id(bn.weight)], self.p[id(bn.bias)], gram, hold, hit_c, hit_e,
+                            self.defects.get("gemm_transposed", 0), self.direct_sums)
         self._running(bn, hold.vec[:, 2], hold.var, a.shape[1])
         shp = tuple(a4.shape[:3]) + (cs.cout,)
         return o.reshape(shp), hold.y.reshape(shp), hold.vec.detach()
@@ -232,6 +254,9 @@ class Emu:
         yg = y.reshape(G, -1, y.shape[-1])
         n = yg.shape[1]
         mean, var = yg.mean(1), yg.var(1, unbiased=False)
+        if not bn.weight.requires_grad and self._hit("frozen_bn_constant"):
+            # planted (5): a BatchNorm with frozen gamma / beta back-propagated as the constant affine map it is in eval mode
+            mean, var = mean.detach(), var.detach()
         inv = (var + X.EPS).rsqrt()
         scale = self.p[id(bn.weight)] * inv
         shift = self.p[id(bn.bias)] - mean * scale
@@ -247,6 +272,11 @@ class Emu:
         y = q(F.conv2d(a, self.p[id(cs.weight)], stride=2, padding=1).permute(0, 2, 3, 1))
         return self._bn_out(rt.groups, y, bn, act)
 
+    def materialize(self, rt, x):
+        y = q(self.use(x))
+        y.register_hook(bf)
+        return ELazy(y.detach().to(torch.bfloat16), None, ACT_NONE, y, requires_grad=x.requires_grad)
+
     def gap(self, rt, x):
         v = self.use(x)
         self.logits = v.reshape(v.shape[0], -1, v.shape[-1]).mean(1)
@@ -260,7 +290,7 @@ class Emu:
 
     def conv_bn_add(self, rt, x, cs, bn, idn, act, idn_sole=False, tpool=0, next_cs=None):
         o, _, vec = self._alg(q(self.use(x)), cs, bn, True)
-        iv = self.use(idn)
+        iv = self.use(idn) if idn is not None else torch.zeros_like(o)
         if tpool:
             out, code = TPool.apply(o, iv, tpool, self._hit("tie_last"))
             lz = ELazy(out.detach().to(torch.bfloat16), None, ACT_NONE, out)
@@ -268,7 +298,7 @@ class Emu:
             return lz
         out = AddAct.apply(o, iv, act, self._hit("drop_identity"), self._hit("no_mask"))
         lz = ELazy(out.detach().to(torch.bfloat16), None, ACT_NONE, out)
-        mask = E.mask_bits_ref(lz.data, act)
+        mask = E.mask_bits_ref(lz.data, act) if act != ACT_NONE else None
         lz.res = (None, idn, act, idn_sole, mask)
         rt.capture["aux"][id(lz)] = (None, mask, vec)
         return lz
@@ -280,7 +310,10 @@ class Emu:
         taps = X.taps2d(v, OH, OW)
         pad = X.taps2d(torch.ones_like(v.detach()), OH, OW) == 0
         idx = X.first_argmax(torch.where(pad, torch.full_like(taps.detach(), -math.inf), taps.detach()))
-        y = q(torch.gather(taps, 0, idx.unsqueeze(0))[0])
+        y = torch.gather(taps, 0, idx.unsqueeze(0))[0]
+        if self._hit("first_tap"):                # planted (3): the gradient goes to the window's first tap, not to the recorded one
+            y = taps[0] + (y - taps[0]).detach()
+        y = q(y)
         y.register_hook(bf)
         lz = ELazy(y.detach().to(torch.bfloat16), None, ACT_NONE, y)
         rt.capture["aux"][id(lz)] = idx.to(torch.uint8)
@@ -560,3 +593,150 @@ def test_forcing_leaves_little_undecided(clean):
     share = rep.undecided_share()
     print("undecided share %.4f" % share)
     assert rep.und[1] > 0 and share <= FR.UNDECIDED_CAP
+
+
+# ------------------------------------------------------------------------------- op-level graphs (tools/executor_ops.py): the new forms
+O = X.ops_module()
+
+OPS_ENTRY = ("conv_bn", "conv_bn_add", "add_act", "materialize", "maxpool3x3s2")
+
+
+def he(module, seed):
+    g = torch.Generator().manual_seed(seed)
+    for m in module.modules():
+        if isinstance(m, nn.Conv2d):
+            fan = m.weight.shape[1] * m.weight.shape[2] * m.weight.shape[3]
+            m.weight.data = torch.randn(m.weight.shape, generator=g) * (2.0 / fan) ** 0.5
+
+
+def one_d(net):
+    return [p for p in net.parameters() if p.dim() == 1]
+
+
+def depthwise(net):
+    return [m.weight for m in net.modules() if isinstance(m, nn.Conv2d) and m.groups > 1]
+
+
+# label of executor_ops.ROWS, frozen set: every new form, and the two partial freezes the model rows take (frozen BatchNorm vectors,
+# frozen depthwise weights) on a graph small enough for the CPU
+OPS_CASES = [("ops-shared-depthwise-input", None), ("ops-shared-depthwise-input", depthwise), ("ops-alg-gemm-arm", None),
+             ("ops-alg-gemm-arm-fused", None), ("ops-unfused-maxpool-pool-first", None), ("ops-unfused-maxpool-conv-first", None),
+             ("ops-accumulating-add", None), ("ops-accumulating-add", one_d)]
+OPS_IDS = [c[0] + ("-frozen-" + c[1].__name__ if c[1] else "") for c in OPS_CASES]
+
+
+def ops_case(label, frozen=None):
+    net = O.make(label)
+    he(net, 7)
+    randomize(net, 8)
+    for p in (frozen(net) if frozen else ()):
+        p.requires_grad_(False)
+    return net, net.make_input()
+
+
+def ops_emulate(monkeypatch, net, x, G, defects=None):
+    """the graph of an executor_ops net with the torch emulation as its executor, recorded -> (emu, recorder, output ELazy, g)"""
+    emu = Emu(net, G, defects)
+    emu.direct_sums = True
+    rec = X.Recorder()
+    with monkeypatch.context() as mp:
+        for n in OPS_ENTRY:
+            mp.setattr(O, n, rec.wrap(n, getattr(emu, n)))
+        mp.setattr(O, "conv_bn_add_supported", lambda *a, **k: True)
+        out = net.graph(emu.rt, ELazy(x, requires_grad=False))
+    g = bf(torch.randn(tuple(out.shape), generator=torch.Generator().manual_seed(3)))
+    out.val.backward(g)
+    return emu, rec, out, g
+
+
+def ops_judge(monkeypatch, label, frozen=None, defects=None, G=O.GROUPS):
+    """-> (worst err / bound, where, worst running-statistic err / tol, replay, emulation)"""
+    net, x = ops_case(label, frozen)
+    emu, rec, out, g = ops_emulate(monkeypatch, net, x, G, defects)
+    named = list(net.named_parameters())
+    p64, names = X.leaves(named, torch.float64)
+    rep = X.Replay(rec.calls, G, p64, X.running_of(net)).output_of(out)
+    ref = rep.backward(g)
+    pert = rep.backward_alg(g)
+    p32, _ = X.leaves(named, torch.float32)
+    em = X.Replay(rec.calls, G, p32, X.running_of(net), dtype=torch.float32, round_grads=True, recomputed_z=label.endswith("-fused")).output_of(out)
+    res = X.compare(emu.grads(), ref, X.bounds(ref, em.backward(g), X.alg_terms(ref, pert)))
+    k, wr = X.worst(res)
+    stat = 0.0
+    for m in net.modules():
+        if isinstance(m, nn.BatchNorm2d):
+            trm, trv = rep.stat_tol[id(m)]
+            stat = max(stat, E.vec_ratio(emu.running[id(m)][0], rep.running[id(m)][0], trm),
+                       E.vec_ratio(emu.running[id(m)][1], rep.running[id(m)][1], trv))
+            assert emu.running[id(m)][2] == rep.running[id(m)][2] == G
+    return wr, names[k], stat, rep, emu
+
+
+@pytest.mark.parametrize("label,frozen", OPS_CASES, ids=OPS_IDS)
+def test_unforced_replay_is_torch_autograd_ops(monkeypatch, label, frozen):
+    """Replay.output_of on a graph without a head; a shared input, a pool that is not the sole consumer, a tensor added twice and the
+    frozen sets fall out of autograd: the unforced replay IS float64 torch autograd of the same modules, group by group"""
+    net, x = ops_case(label, frozen)
+    G = O.GROUPS
+    emu, rec, out, g = ops_emulate(monkeypatch, net, x, G)
+    net.double()
+    named = list(net.named_parameters())
+    p64, _ = X.leaves(named, torch.float64)
+    rep = X.Replay(rec.calls, G, p64, X.running_of(net), force=False).output_of(out)
+    got = rep.backward(g)
+    net.train()
+    net.zero_grad()
+    want = torch.cat([net.torch_forward(c) for c in x.double().permute(0, 3, 1, 2).chunk(G)]).permute(0, 2, 3, 1)
+    want.backward(g.double())
+    assert X.rel_l2(rep.logits, want) <= 1e-12
+    assert set(got) == {id(p) for _, p in named if p.requires_grad} and all(p.grad is None for _, p in named if not p.requires_grad)
+    gmax = max(p.grad.norm().item() for _, p in named if p.requires_grad)
+    for n, p in named:
+        if p.requires_grad:
+            assert (got[id(p)] - p.grad).norm().item() <= 1e-12 * max(p.grad.norm().item(), X.SMALL * gmax), n
+    for m in net.modules():
+        if isinstance(m, nn.BatchNorm2d):
+            assert X.rel_l2(rep.running[id(m)][0], m.running_mean) <= 1e-12 and X.rel_l2(rep.running[id(m)][1], m.running_var) <= 1e-12
+            assert rep.running[id(m)][2] == int(m.num_batches_tracked) == G
+
+
+@pytest.mark.parametrize("label,frozen", OPS_CASES, ids=OPS_IDS)
+def test_emulated_ops_pass_the_bound(monkeypatch, label, frozen):
+    wr, where, stat, rep, _ = ops_judge(monkeypatch, label, frozen)
+    print("%s: worst err/bound %.3f at %s; running statistics %.3f; forward %.3f" % (label, wr, where, stat, max(v[1] for v in rep.fwd.values())))
+    assert wr <= 1.0 and stat <= 1.0, (wr, where, stat)
+    assert max(v[1] for v in rep.fwd.values()) <= 1.0, rep.fwd
+    assert max(rep.vec_ratio.values()) <= 1.0, rep.vec_ratio
+    assert rep.undecided_share() <= FR.UNDECIDED_CAP
+    assert len(rep.alg) == (1 if "alg" in label else 0)
+
+
+# (row, frozen set, defect).  drop_use (t, k): see Emu.use -- in ops-shared-depthwise-input tensor 1 is h (consumers: the depthwise conv, then
+# materialize, whose gradient is there first and which the depthwise data gradient must ADD to); in ops-unfused-maxpool-pool-first tensor 1
+# is h (consumers: the pool, then the strided conv, whose data gradient is there first and which adamml_maxpool2d_bwd must add to)
+OPS_DEFECTS = [("1-depthwise-data-gradient-overwrites", "ops-shared-depthwise-input", None, {"drop_use": (1, 1)}),
+               ("2-maxpool-backward-overwrites", "ops-unfused-maxpool-pool-first", None, {"drop_use": (1, 1)}),
+               ("3-maxpool-backward-first-tap", "ops-unfused-maxpool-conv-first", None, {"first_tap": 0}),
+               ("4-act-bwd-from-output-mask-skipped", "ops-shared-depthwise-input", None, {"no_mask": 0}),
+               ("5-frozen-batchnorm-as-constant-affine", "ops-accumulating-add", one_d, {"frozen_bn_constant": 1}),
+               ("6-gemm-arm-wtbw-group-channel-transposed", "ops-alg-gemm-arm", None, {"gemm_transposed": 1}),
+               ("6-gemm-arm-wg-group-channel-transposed", "ops-alg-gemm-arm", None, {"gemm_transposed": 2}),
+               ("6-gemm-arm-wg-transposed-gram-from-forward", "ops-alg-gemm-arm-fused", None, {"gemm_transposed": 2})]
+
+
+@pytest.mark.parametrize("name,label,frozen,defect", OPS_DEFECTS, ids=[d[0] for d in OPS_DEFECTS])
+def test_planted_ops_defect_misses_the_bound(monkeypatch, name, label, frozen, defect):
+    wr, where, stat = ops_judge(monkeypatch, label, frozen, defect)[:3]
+    print("%s: worst err/bound %.2f at %s, running statistics %.2f" % (name, wr, where, stat))
+    assert max(wr, stat) >= 2.0, (name, wr, where, stat)
+
+
+@pytest.mark.parametrize("which", [1, 2])
+def test_gemm_arm_transposition_is_invisible_with_one_group(monkeypatch, which):
+    """[Cout][Cin][G] read as [Cout][G][Cin] is the same buffer at G = 1: the defect every G = 1 row passes.  The same graph, input and
+    defect as above in ONE BatchNorm group gives bit for bit the clean gradients (and meets the bound)."""
+    clean = ops_judge(monkeypatch, "ops-alg-gemm-arm", G=1)
+    planted = ops_judge(monkeypatch, "ops-alg-gemm-arm", None, {"gemm_transposed": which}, G=1)
+    assert clean[0] <= 1.0 and planted[0] <= 1.0, (clean[:2], planted[:2])
+    a, b = clean[4].grads(), planted[4].grads()
+    assert len(a) == len(b) == 6 and all(torch.equal(u, v) for u, v in zip(a.values(), b.values()))

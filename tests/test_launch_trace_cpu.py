@@ -33,7 +33,7 @@ def rows(runs):
 
 def test_two_runs_give_the_same_trace(runs):
     lt, a, b = runs
-    assert [r.label for r in a] == [label for label, _ in lt.ROWS]
+    assert [r.label for r in a] == [label for label, _ in lt.ROWS] and len(set(r.label for r in a)) == len(a)
     for ra, rb in zip(a, b):
         assert ra.lines == rb.lines, ra.label
         assert sum(ra.counts.values()) > 0
@@ -113,11 +113,23 @@ def test_policy_mobilenet_v2(rows):
 
 
 def test_forward_only_rows_launch_no_backward(rows):
-    for label in ("resnet50-train-nograd", "resnet50-eval", "policy-mobilenetv2-train-nograd"):
+    for label in ("resnet50-train-nograd", "resnet50-eval", "policy-mobilenetv2-train-nograd", "sound-mobilenetv2-eval", "policy-mobilenetv2-eval"):
         r = rows[label]
         assert not [n for n in r.counts if "_bwd" in n], label
         assert not [e for e in r.log if e[2] is None], label            # no weight-gradient stream marker either
+        assert r.net.rt.pre_pending == 0 and r.net.rt.pre_dropped == 0
     assert rows["resnet50-eval"].counts["adamml_bn_finalize"] == 0 and rows["resnet50-train-nograd"].counts["adamml_bn_finalize"] == 53
+    n = rows["resnet50-train-nograd"].counts
+    assert n["adamml_gram_stats"] == 7 and n["adamml_conv_fwd_bn_add"] + n["adamml_conv_fwd_bn_add_next"] + n["adamml_conv_fwd_bn_add_tpool"] == 7
+    n = rows["policy-mobilenetv2-train-nograd"].counts
+    assert n["adamml_bn_finalize"] == 52 and n["adamml_dwconv_fwd"] == 17 and n["adamml_temporal_pool_fwd"] == 2 and n["adamml_conv_fwd_bn_add"] == 0
+    for label in ("sound-mobilenetv2-eval", "policy-mobilenetv2-eval"):
+        n = rows[label].counts
+        assert n["adamml_bn_finalize"] == 0 and n["adamml_bn_eval_affine"] == 52 and n["adamml_conv_fwd_bn_add"] == 10, label
+    n = rows["sound-mobilenetv2-eval"].counts
+    assert n["adamml_conv_stem1_fwd"] == 1 and n["adamml_head_fwd"] == 1
+    n = rows["policy-mobilenetv2-eval"].counts
+    assert n["adamml_temporal_pool_fwd"] == 2 and n["adamml_gap_fwd"] == 1
 
 
 def test_unfused_depthwise_forms(rows):
@@ -128,6 +140,82 @@ def test_unfused_depthwise_forms(rows):
     r = rows["ops-shared-depthwise-input"]
     assert r.counts["adamml_dwconv_bwd_weight"] == 1 and r.counts["adamml_act_bwd_from_output"] == 1
     assert [a[-1] for n_, a, _ in r.log if n_ == "adamml_dwconv_bwd_data"] == [1]            # acc = 1: it adds to the gradient already there
+
+
+def weight_gradient_launches(n):
+    return {k: v for k, v in n.items() if ("bwd_weight" in k or k in ("adamml_alg_wgrad_combine", "adamml_dwconv_bwd_fused")) and v}
+
+
+def launches(r, name):
+    return [a for n, a, m in r.log if n == name and m is not None]
+
+
+def test_policy_mobilenet_v2_frozen_depthwise(rows):
+    """frozen depthwise weights: no fused depthwise backward, the data gradient still produces the expansion's sums"""
+    n = rows["policy-mobilenetv2-frozen-depthwise"].counts
+    assert n["adamml_dwconv_bwd_fused"] == 0 and n["adamml_dwconv_bwd_data_bn"] == 17 and n["adamml_dwconv_bwd_weight"] == 0
+    assert n["adamml_conv_bwd_weight"] == 35 and n["adamml_conv_bwd_data_dual"] == 17
+
+
+def test_policy_mobilenet_v2_depthwise_only(rows):
+    n = rows["policy-mobilenetv2-depthwise-only"].counts
+    assert n["adamml_dwconv_bwd_weight"] >= 1
+    assert n["adamml_dwconv_bwd_weight"] + n["adamml_dwconv_bwd_fused"] == 17
+    assert set(weight_gradient_launches(n)) <= {"adamml_dwconv_bwd_weight", "adamml_dwconv_bwd_fused"}
+
+
+def test_sound_mobilenet_v2_frozen_batchnorm(rows):
+    r = rows["sound-mobilenetv2-frozen-batchnorm"]
+    n = r.counts
+    assert n["adamml_bn_finalize"] == 52 and n["adamml_conv_stem1_fwd"] == 1 and n["adamml_conv_stem1_bwd_weight"] == 1
+    assert n["adamml_dwconv_bwd_fused"] == 17 and n["adamml_conv_bwd_data_dual"] == 17 and n["adamml_conv_bwd_weight"] == 34
+    assert n["adamml_bn_bwd_finalize"] + n["adamml_bn_bwd_finalize_affine"] == 52
+    assert n["adamml_gemm_f32"] == 1 and n["adamml_colsum_f32"] == 0
+    fin = launches(r, "adamml_bn_bwd_finalize") + launches(r, "adamml_bn_bwd_finalize_affine")
+    assert len(fin) == 52 and all(a[6] is None and a[7] is None for a in fin)
+
+
+def test_resnet50_frozen_conv_weights(rows):
+    n = rows["resnet50-frozen-conv-weights"].counts
+    assert not weight_gradient_launches(n)
+    assert not [k for k in n if "_bwd_weight" in k] and n["adamml_alg_wgrad_combine"] == 0
+    assert n["adamml_gram_colsum"] == 0 and n["adamml_alg_pack"] == 0 and n["adamml_conv_bwd_data_alg"] == 0
+    assert n["adamml_conv_fwd_bn_add"] + n["adamml_conv_fwd_bn_add_next"] + n["adamml_conv_fwd_bn_add_tpool"] == 0
+    assert n["adamml_conv_fwd"] == 52 and n["adamml_bn_act_add_mask"] == 16 and n["adamml_conv_bwd_data_dual"] == 8
+
+
+def test_ops_shared_depthwise_input(rows):
+    """a depthwise conv that shares its input (no model has one) takes the unfused weight gradient and the accumulating data gradient"""
+    r = rows["ops-shared-depthwise-input"]
+    n = r.counts
+    assert n["adamml_dwconv_bwd_weight"] == 1 and n["adamml_act_bwd_from_output"] == 1 and n["adamml_dwconv_bwd_fused"] == 0
+    assert [a[-1] for a in launches(r, "adamml_dwconv_bwd_data")] == [1]            # acc = 1: it adds to the gradient already there
+
+
+@pytest.mark.parametrize("form", ["conv_bn", "conv_bn_add"])
+def test_ops_alg_gemm_arm(rows, form):
+    r = rows["ops-alg-gemm-arm" + ("-fused" if form == "conv_bn_add" else "")]
+    n = r.counts
+    assert n["adamml_gemm_f32"] == 2 and n["adamml_alg_pack"] == 1 and n["adamml_alg_wgrad_combine"] == 1 and n["adamml_conv_bwd_data_alg"] == 1
+    assert [a[2] is not None for a in launches(r, "adamml_alg_pack")] == [True]                    # m_pre
+    assert [a[4] is not None for a in launches(r, "adamml_alg_wgrad_combine")] == [True]           # wg_pre
+    assert [(a[-3], a[-2], a[-1]) for a in launches(r, "adamml_alg_pack")] == [(512, 256, 2)]
+    assert n["adamml_gram_colsum"] == 1 and n["adamml_conv_fwd_bn_add"] == (1 if form == "conv_bn_add" else 0)
+
+
+@pytest.mark.parametrize("order,acc", [("pool-first", 1), ("conv-first", 0)])
+def test_ops_unfused_maxpool(rows, order, acc):
+    r = rows["ops-unfused-maxpool-" + order]
+    assert [a[-1] for a in launches(r, "adamml_maxpool2d_bwd")] == [acc] and r.counts["adamml_maxpool2d_bwd_bn_apply"] == 0
+    assert [a[-1] for a in launches(r, "adamml_conv_bwd_data")] == [1 - acc]
+    assert [a[3] for a in launches(r, "adamml_bn_bwd_reduce")] == [1] and 1 in [a[3] for a in launches(r, "adamml_bn_bwd_apply")]
+
+
+def test_ops_accumulating_add(rows):
+    r = rows["ops-accumulating-add"]
+    accum = [a for a in launches(r, "adamml_bn_act_add") if a[1] is None and a[2] is None and a[5] is not None]
+    assert len(accum) >= 1 and all(a[0] == a[9] for a in accum)          # in place: t.grad += g
+    assert r.counts["adamml_residual_bwd"] == 2
 
 
 def test_a_step_leaves_nothing_to_the_cycle_collector(runs):

@@ -55,8 +55,36 @@ def _mobilenet_row(which, mode="grad", frozen=None):
     return make
 
 
-# label -> () -> (net, input, BatchNorm groups, "grad" | "train-nograd" | "eval", frozen parameters).  The first seven are the rows of
-# tests/test_executor_gpu.py (same shapes, groups and frozen sets); the rest reach the launches those leave out.
+# the op-level graphs of tools/executor_ops.py (the forms no model's graph produces), defined there once for the GPU test, the CPU test and
+# this trace: a depthwise conv sharing its input, the adamml_gemm_f32 arm of the algebraic backward (conv_bn and conv_bn_add), the unfused
+# max-pool backward writing / accumulating, the accumulating _accum_grad
+_OPS_ROWS = ("ops-shared-depthwise-input", "ops-alg-gemm-arm", "ops-alg-gemm-arm-fused", "ops-unfused-maxpool-pool-first",
+             "ops-unfused-maxpool-conv-first", "ops-accumulating-add")
+
+
+def _executor_ops():
+    """tools/executor_ops.py as the module `executor_ops` (loaded from this directory once; the tests load the same file under the same name,
+    so the graphs they record and the ones traced here are one module)"""
+    mod = sys.modules.get("executor_ops")
+    if mod is None:
+        import importlib.util
+        spec = importlib.util.spec_from_file_location("executor_ops", os.path.join(os.path.dirname(os.path.abspath(__file__)), "executor_ops.py"))
+        mod = sys.modules["executor_ops"] = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+    return mod
+
+
+def _ops_row(label):
+    def make():
+        executor_ops = _executor_ops()
+        net = executor_ops.make(label)
+        return net, torch.zeros_like(net.make_input()), executor_ops.GROUPS, "grad", []
+    return make
+
+
+# label -> () -> (net, input, BatchNorm groups, "grad" | "train-nograd" | "eval", frozen parameters).  Every row is a row of
+# tests/test_executor_gpu.py too (same shapes, groups and frozen sets; resnet50-eval is its eval-vector-cache test), where what the launches
+# compute is checked; tests/test_launch_trace_cpu.py asserts the same entry-point expectations for both.
 ROWS = (
     ("resnet50-streaming", _resnet_row(8, 92, 8, 1)),
     ("resnet50-tile-g3", _resnet_row(4, 44, 2, 3)),
@@ -75,8 +103,8 @@ ROWS = (
     # no BatchNorm trains: its producers' data gradients need no sums, the bare data gradients and the unfused activation mask run
     ("sound-mobilenetv2-frozen-batchnorm", _mobilenet_row("sound", frozen=lambda n: [p for p in n.parameters() if p.dim() == 1])),
     ("resnet50-frozen-conv-weights", _resnet_row(4, 44, 2, 1, frozen=lambda n: [_W([p for p in n.parameters() if p.dim() == 4])])),
-    ("ops-shared-depthwise-input", lambda: (_Ops(), torch.zeros(4, 12, 12, 8, dtype=torch.bfloat16), 2, "grad", [])),
-)
+    ("policy-mobilenetv2-eval", _mobilenet_row("policy", mode="eval")),
+) + tuple((label, _ops_row(label)) for label in _OPS_ROWS)
 
 
 class _W:
@@ -85,32 +113,6 @@ class _W:
 
     def parameters(self):
         return self.params
-
-
-class _Ops(torch.nn.Module):
-    """No model: executor ops driven directly, for the forms no model's graph produces -- a depthwise conv that is not the sole
-    consumer of its input (unfused weight gradient, accumulating data gradient) and an activated add of two plain tensors."""
-
-    def __init__(self):
-        super().__init__()
-        from adamml_amd import runtime
-        self.pw, self.dw = torch.nn.Conv2d(8, 16, 1, bias=False), torch.nn.Conv2d(16, 16, 3, padding=1, groups=16, bias=False)
-        self.bn1, self.bn2 = torch.nn.BatchNorm2d(16), torch.nn.BatchNorm2d(16)
-        self.rt = runtime.NetRT()
-        self.cs = (runtime.ConvState(self.pw.weight, 1, 0), runtime.ConvState(self.dw.weight, 1, 1, depthwise=True))
-
-    def _run(self, x, groups, need_grad):
-        from adamml_amd import runtime as R
-        rt = self.rt
-        tape = rt.begin_forward(x.device, self.training, need_grad, groups)
-        for cs in self.cs:
-            cs.pack_rows(need_grad)
-        h = R.conv_bn(rt, R.Lazy(x, requires_grad=False), self.cs[0], self.bn1, R.ACT_RELU)
-        a = R.conv_bn(rt, h, self.cs[1], self.bn2, R.ACT_RELU)
-        out = R.add_act(rt, R.materialize(rt, a), R.materialize(rt, h), R.ACT_RELU)
-        rt.end_forward()
-        tape.record(lambda: setattr(out, "grad", tape.grad_out))
-        return out.data, tape
 
 
 SITES = None        # --sites: a set collecting (file, line) of every statement that launched
