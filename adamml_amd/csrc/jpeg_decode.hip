@@ -1,7 +1,11 @@
 // Baseline JPEG frames decoded on the GPU, byte-exact to libjpeg(-turbo) as Pillow uses it (utils/video_dataset.py:51-66 opens every
-// frame with PIL.Image.open; adamml_amd/jpeg.py parses the headers and packs the batch).  Three kernels on one stream:
+// frame with PIL.Image.open; adamml_amd/jpeg.py parses the headers and packs the batch).  Four kernels on one stream:
 //
-//   1. jpeg_entropy_kernel   Huffman decode.  Segments (the scan split at its restart markers) are independent and sequential: one
+//   0. jpeg_parallel_kernel  Huffman decode of the images whose scan is ONE segment (no restart markers): self-synchronising
+//      subsequences, one lane each, one workgroup per image (section 1b below).  It returns at once for every other image, and an
+//      image it cannot vouch for (anything but a clean stream) it hands to kernel 1 through a word in the image's plane region.
+//   1. jpeg_entropy_kernel   Huffman decode of every other image, and of those kernel 0 gave up (their coefficients cleared
+//      first); it returns at once for the images kernel 0 finished.  Segments (the scan split at its restart markers) are independent and sequential: one
 //      lane decodes one segment, JE_LANES segments per wave, one image per workgroup.  What the decoding lane touches lives in LDS:
 //      the image's Huffman tables, built here from BITS / HUFFVAL (an 8-bit first-level table + the canonical max-code walk for the
 //      longer codes), the zigzag order, and a 16-byte window of the lane's bitstream that is refilled with 16-byte loads issued one
@@ -18,7 +22,10 @@
 // [0, meta_len - table size], every bitstream address into [0, src_bytes), every workspace block into [0, blocks) and every output
 // address into [0, y_bytes).  A bad segment sets status bits (1 ran past its end, 2 no code matches / DC category > 11,
 // 4 coefficient index > 63) and its remaining blocks stay zero; 8 marks a descriptor that had to be clamped, 16 a segment with a byte or
-// more left over after its last MCU.  Nothing traps or spins.
+// more left over after its last MCU.  Nothing traps or spins.  Kernel 0 keeps to the same rules: its rounds number at most the
+// (clamped) subsequence count, a subsequence's decode at most its bits, its records live in LDS at indices below that count, its
+// bytes come from inside the segment the record names (checked against src_bytes before anything is read), and it waits on nothing
+// but its own workgroup's barriers.  Status is kernel 1's alone: what kernel 0 keeps is an image on which both agree, bit for bit.
 #include "common.h"
 #include "../../include/adamml_hip.h"
 
@@ -178,21 +185,11 @@ __device__ __forceinline__ int symbol(Reader& r, const HuffLds& h) {
 
 __device__ __forceinline__ int extend(int v, int s) { return (s == 0 || v >= (1 << (s - 1))) ? v : v - (1 << s) + 1; }
 
-__global__ void __launch_bounds__(JE_THREADS)
-jpeg_entropy_kernel(const uint8_t* __restrict__ src, int64_t src_bytes, const int* __restrict__ meta, int meta_len, int16_t* __restrict__ coef,
-                    int64_t total_blocks, int* __restrict__ status) {
-    __shared__ HuffLds huff[6];                      // DC of components 0..2, AC of components 0..2
-    __shared__ u32x4 window[JE_LANES];
-    __shared__ uint8_t zigzag[64];
-    const int img = blockIdx.y, lane = threadIdx.x;
-    const int* d = meta + (size_t)img * JD;
-    int flag = 0;
-    const Image im = load_image(d, total_blocks, flag);
-    const int nseg = clampi(d[5], 0, im.mw * im.mh);
-    if (blockIdx.x == 0 && lane == 0 && (flag || nseg != d[5])) atomicOr(status + img, ST_BAD_DESC);
-    if ((int)blockIdx.x * JE_LANES >= nseg) return;
-
-    zigzag[lane] = JPEG_ZIGZAG[lane];
+// The image's Huffman tables and the zigzag order into LDS: the work of 64 lanes (`active`: lane < 64); every thread of the workgroup
+// calls it (it holds barriers).
+__device__ __forceinline__ void build_tables(HuffLds* huff, uint8_t* zigzag, const int* __restrict__ d, const Image& im,
+                                             const int* __restrict__ meta, int meta_len, int lane, bool active) {
+    if (active) zigzag[lane] = JPEG_ZIGZAG[lane];
     for (int t = 0; t < 2 * im.ncomp; ++t) {
         HuffLds& h = huff[t < im.ncomp ? t : 3 + t - im.ncomp];
         const int* tab = meta + table_at(d[(t < im.ncomp ? 9 : 12 - im.ncomp) + t], JHUFF, meta_len);
@@ -207,18 +204,20 @@ jpeg_entropy_kernel(const uint8_t* __restrict__ src, int64_t src_bytes, const in
             maxcode[l] = b ? code - 1 : -1;
             code <<= 1;
         }
-        const uint32_t w = (uint32_t)tab[16 + lane];
-        reinterpret_cast<uint32_t*>(h.val)[lane] = w;
-        if (lane < 17) {
-            int mc = -1, vo = 0;
+        if (active) {
+            const uint32_t w = (uint32_t)tab[16 + lane];
+            reinterpret_cast<uint32_t*>(h.val)[lane] = w;
+            if (lane < 17) {
+                int mc = -1, vo = 0;
 #pragma unroll
-            for (int l = 1; l <= 16; ++l)
-                if (l == lane) mc = maxcode[l], vo = valoff[l];
-            h.maxcode[lane] = mc;
-            h.valoff[lane] = vo;
+                for (int l = 1; l <= 16; ++l)
+                    if (l == lane) mc = maxcode[l], vo = valoff[l];
+                h.maxcode[lane] = mc;
+                h.valoff[lane] = vo;
+            }
         }
         __syncthreads();
-        for (int j = 0; j < 4; ++j) {
+        for (int j = 0; j < 4 && active; ++j) {
             const int pre = lane + 64 * j;
             int e = 0;
 #pragma unroll
@@ -230,6 +229,370 @@ jpeg_entropy_kernel(const uint8_t* __restrict__ src, int64_t src_bytes, const in
         }
     }
     __syncthreads();
+}
+
+// ---- 1b. entropy decode of a marker-less scan: self-synchronising subsequences ------------------------------------------------------
+//
+// A scan without restart markers is ONE segment; jpeg_entropy_kernel would walk it with one lane.  jpeg_parallel_kernel cuts it into
+// subsequences of JP_SUBSEQ raw bytes (byte stuffing in place), one lane each, one workgroup per image:
+//   1. every lane decodes its subsequence from a GUESSED state (bit position = its first byte, block 0 of an MCU, DC next) up to the
+//      subsequence's end and records its exit state and the blocks it completed;
+//   2. rounds of "decode my subsequence again from my predecessor's exit state" (only the lanes whose input changed) until a round
+//      changes nothing: subsequence 0 starts from the true state, so after round i subsequence i does too -- at most as many rounds
+//      as subsequences, far fewer on real content because a Huffman decoder started at a wrong bit falls into step within a few
+//      dozen symbols.  A guessed state that meets a code no table entry matches just records "unknown", which its successor
+//      ignores (from a true state it is the stream that is bad: step 3 meets the same code again and gives the image up);
+//   3. a prefix sum of the block counts gives every subsequence its first block; one more decode from the now TRUE states stores the
+//      coefficients, the DC coefficient as the DIFFERENCE the stream holds;
+//   4. per component a prefix sum of the DC differences in scan order.
+// A state is one word: raw bit position << 9 | block in MCU << 6 | next zigzag index (0 = DC next).  The position always names a
+// data byte, never the 00 of a stuffed FF 00: whoever consumes the last bit of an FF steps over the 00 with it.  A subsequence owns
+// the symbols (code + magnitude bits) that BEGIN in its bytes, so one that begins inside a code or inside magnitude bits starts
+// where its predecessor stopped, a few bits in.
+// JP_SUBSEQ = 128: synchronisation costs about as many symbols whatever the size, so the rounds fall with the size (18 at 128 B, 12
+// at 256 B on a full frame) while the lanes per frame -- the point of the exercise -- fall too; at 128 B a 44 KB frame has 340
+// lanes, its 18 rounds decode every subsequence 2.3 times on average, and JP_MAXSUB = 2048 records (24 KB of LDS) cover files up to
+// 256 KB.  Measured on a step's 2 880 frames of 50 KB (profiles/jpeg_decode.json): 64 B 23.7 ms, 128 B 23.1 ms, 256 B 21.9 ms for the
+// whole decode -- the IDCT and colour stages dominate, and 256 B is the next thing to try.
+// The stage takes no decision about a damaged stream: whenever what it sees could differ from the sequential walk in status or in a
+// single coefficient (an unknown state after the rounds, a bad code / index / DC category from a true state, a marker, a block count
+// that is not the image's, a stream that overruns or has a byte or more left over, a DC prefix outside int16 where the sequential
+// walk saturates per step) it sets the image's "gave up" word -- the first word of the image's own plane region, idle until the
+// IDCT -- and jpeg_entropy_kernel, launched after it over all images, clears the image's coefficients and decodes it as ever.
+
+constexpr int JP_SUBSEQ = ADAMML_JPEG_SUBSEQ_BYTES;
+constexpr int JP_MAXSUB = 2048;
+constexpr int JP_THREADS = 256;
+constexpr int JP_PER = JP_MAXSUB / JP_THREADS;     // subsequences per thread at the cap
+constexpr uint32_t JP_UNKNOWN = 0xFFFFFFFFu;
+
+// Whether image `d` takes the parallel stage -- structural, the same answer in both entropy kernels: one segment that is the whole
+// scan, nothing clamped, at most JP_MAXSUB subsequences.  off / len: the segment's bytes.
+__device__ __forceinline__ bool parallel_eligible(const int* __restrict__ d, const int* __restrict__ meta, int meta_len, int64_t src_bytes,
+                                                  const Image& im, int flag, int& off, int& len) {
+    off = 0, len = 0;
+    if (flag || d[5] != 1 || d[4] < 0 || d[4] > meta_len - JSEG) return false;
+    const int* sg = meta + d[4];
+    if (sg[0] < 0 || sg[1] < 1 || sg[1] > JP_MAXSUB * JP_SUBSEQ || (int64_t)sg[0] + sg[1] > src_bytes) return false;
+    if (sg[2] != 0 || sg[3] != im.mw * im.mh) return false;
+    off = sg[0], len = sg[1];
+    return true;
+}
+
+__device__ __forceinline__ int* gave_up_word(uint8_t* planes, const Image& im, int64_t total_blocks) {
+    return reinterpret_cast<int*>(planes + clampl(im.blk0, 0, total_blocks - 1) * 64);
+}
+
+// Bit reader that knows where it is: `pos` is the raw bit position (relative to the segment) of the next unconsumed bit.  `stf` runs
+// beside `acc` with a 1 at the last bit of every FF data byte, whose consumption carries `pos` over the stuffed 00 as well.  Bytes
+// come from the segment through an aligned 8-byte word; from the segment's end on they are zero.
+struct PReader {
+    const uint8_t* src;       // the whole buffer: 16-byte aligned, a multiple of 16 bytes
+    int off, len;             // the segment: off + len <= src_bytes
+    uint64_t acc, stf, cw;
+    int64_t cwi;
+    int n, p, pos;
+    bool marker;              // an FF that no 00 follows was loaded
+
+    __device__ __forceinline__ int byte(int i) {
+        if (i < 0 || i >= len) return 0;
+        const int64_t a = (int64_t)off + i;
+        if ((a >> 3) != cwi) {
+            cwi = a >> 3;
+            cw = *reinterpret_cast<const uint64_t*>(src + cwi * 8);
+        }
+        return (int)((cw >> (8 * (a & 7))) & 255);
+    }
+    __device__ __forceinline__ void fill() {
+#pragma unroll 1
+        for (int i = 0; i < 8 && n <= 56; ++i) {
+            const int v = byte(p);
+            ++p;
+            const bool ff = v == 0xFF;
+            if (ff) {
+                if (byte(p) == 0 && p < len)
+                    ++p;
+                else
+                    marker = true;
+            }
+            acc = (acc << 8) | (uint64_t)v;
+            stf = (stf << 8) | (uint64_t)(ff ? 1 : 0);
+            n += 8;
+        }
+    }
+    __device__ __forceinline__ void start(int pos0) {
+        pos = pos0, p = pos0 >> 3, acc = 0, stf = 0, n = 0, cwi = -1, cw = 0, marker = false;
+        fill();
+        n -= pos0 & 7;
+    }
+    __device__ __forceinline__ void consume(int k) {                // 0 <= k <= 16 <= n
+        const uint64_t m = (stf >> (n - k)) & ((1u << k) - 1);
+        pos += k + 8 * __popcll(m);
+        n -= k;
+    }
+    __device__ __forceinline__ int bits(int k) {
+        const int v = (int)((acc >> (n - k)) & ((1u << k) - 1));
+        consume(k);
+        return v;
+    }
+};
+
+__device__ __forceinline__ int psymbol(PReader& r, const HuffLds& h) {
+    r.fill();
+    const int look = (int)((r.acc >> (r.n - 16)) & 0xFFFF);
+    const int e = h.look[look >> 8];
+    if (e) {
+        r.consume(e >> 8);
+        return e & 255;
+    }
+    for (int l = 9; l <= 16; ++l) {
+        const int code = look >> (16 - l);
+        if (code <= h.maxcode[l]) {
+            r.consume(l);
+            return h.val[clampi(h.valoff[l] + code, 0, 255)];
+        }
+    }
+    return -1;
+}
+
+// Block `g` of the image in scan order (block `rr` of its MCU) -> its 64 coefficients in the workspace.
+__device__ __forceinline__ int16_t* scan_block(int16_t* __restrict__ coef, const Image& im, int64_t total_blocks, int64_t g, int rr, int bpm) {
+    const int m = (int)(g / bpm);
+    const int hs2 = im.hs * im.hs;
+    const int c = im.ncomp == 1 ? 0 : (rr < hs2 ? 0 : rr - hs2 + 1);
+    const int hv = c == 0 ? im.hs : 1, b = c == 0 ? rr : 0;
+    const int bw = c == 0 ? im.bw0 : im.bw1;
+    const int64_t base = c == 0 ? 0 : (int64_t)im.nb0 + (int64_t)(c - 1) * im.mw * im.mh;
+    const int by = (m / im.mw) * hv + b / hv, bx = (m % im.mw) * hv + b % hv;
+    return coef + ws_block(im, base + (int64_t)by * bw + bx, total_blocks) * 64;
+}
+
+// Decode the symbols that begin in [state's position, end) from state `st`; returns the exit state, or JP_UNKNOWN when a code, an
+// index or a DC category is bad.  count: blocks completed.  STORE: block `g` (scan order) is the one in progress at `st`; stops at
+// the image's last block; coefficients are stored, the DC as its difference; fail: set when the image must take the sequential walk.
+template <bool STORE>
+__device__ __forceinline__ uint32_t decode_subsequence(PReader& r, uint32_t st, int end, const Image& im, int bpm, const HuffLds* huff,
+                                                       const uint8_t* zigzag, int& count, int16_t* __restrict__ coef, int64_t total_blocks,
+                                                       int64_t g, bool last, bool& fail) {
+    count = 0;
+    if (st == JP_UNKNOWN) {
+        fail = true;
+        return JP_UNKNOWN;
+    }
+    int rr = min((int)((st >> 6) & 7), bpm - 1), k = (int)(st & 63);
+    const int hs2 = im.hs * im.hs;
+    r.start((int)(st >> 9));
+    int16_t* blk = nullptr;
+    if (STORE) {
+        if (g % bpm != rr) fail = true;
+        blk = scan_block(coef, im, total_blocks, g, rr, bpm);
+    }
+    bool bad = false;
+#pragma unroll 1
+    for (int it = 0; it < JP_SUBSEQ * 8 + 64 && r.pos < end; ++it) {      // every symbol is at least one bit
+        if (STORE && g >= im.nblk) break;
+        const int c = im.ncomp == 1 ? 0 : (rr < hs2 ? 0 : rr - hs2 + 1);
+        if (k == 0) {
+            const int t = psymbol(r, huff[c]);
+            if (t < 0 || t > 11) {
+                bad = true;
+                break;
+            }
+            const int v = extend(r.bits(t), t);
+            if (STORE) blk[0] = (int16_t)v;
+            k = 1;
+        } else {
+            const int rs = psymbol(r, huff[3 + c]);
+            if (rs < 0) {
+                bad = true;
+                break;
+            }
+            const int run = rs >> 4, size = rs & 15;
+            if (size == 0) {
+                k = run == 15 ? k + 16 : 64;
+            } else {
+                k += run;
+                if (k > 63) {
+                    bad = true;
+                    break;
+                }
+                const int v = extend(r.bits(size), size);
+                if (STORE) blk[zigzag[k]] = (int16_t)v;
+                ++k;
+            }
+        }
+        if (k >= 64) {
+            k = 0;
+            rr = rr + 1 == bpm ? 0 : rr + 1;
+            ++count;
+            if (STORE) {
+                ++g;
+                blk = scan_block(coef, im, total_blocks, g, rr, bpm);
+            }
+        }
+    }
+    if (STORE) {
+        const int stream_end = r.len * 8;
+        if (bad || r.marker || r.pos > stream_end) fail = true;           // bad stream, a marker, or bits from past the end
+        if (r.pos < end) {                                                // stopped at the image's last block: what is left over?
+            const int at = r.pos >> 3;
+            const int whole = (r.pos & 7) == 0 ? at : (r.byte(at) == 0xFF ? at + 2 : at + 1);      // the first untouched data byte
+            if (g < im.nblk || whole < r.len) fail = true;
+        }
+        if (last && g != im.nblk) fail = true;                            // the stream ended before the image did
+    }
+    if (bad) return JP_UNKNOWN;
+    return ((uint32_t)min(r.pos, (1 << 22) - 1) << 9) | ((uint32_t)rr << 6) | (uint32_t)k;
+}
+
+__global__ void __launch_bounds__(JP_THREADS)
+jpeg_parallel_kernel(const uint8_t* __restrict__ src, int64_t src_bytes, const int* __restrict__ meta, int meta_len, int16_t* __restrict__ coef,
+                     uint8_t* __restrict__ planes, int64_t total_blocks) {
+    __shared__ HuffLds huff[6];
+    __shared__ uint8_t zigzag[64];
+    __shared__ uint32_t s_in[JP_MAXSUB], s_out[JP_MAXSUB];      // entry and exit state per subsequence; s_out later: its first block
+    __shared__ int s_cnt[JP_MAXSUB];                            // blocks it completed
+    __shared__ int64_t s_scan[JP_THREADS];
+    const int img = blockIdx.x, tid = threadIdx.x;
+    const int* d = meta + (size_t)img * JD;
+    int flag = 0, off, len;
+    const Image im = load_image(d, total_blocks, flag);
+    if (!parallel_eligible(d, meta, meta_len, src_bytes, im, flag, off, len)) return;
+    build_tables(huff, zigzag, d, im, meta, meta_len, tid, tid < 64);
+
+    const int nsub = clampi((len + JP_SUBSEQ - 1) / JP_SUBSEQ, 1, JP_MAXSUB);
+    const int bpm = im.ncomp == 3 ? im.hs * im.hs + 2 : 1;
+    PReader r;
+    r.src = src, r.off = off, r.len = len;
+    r.start(0);
+
+    // 1. guessed starts (subsequence 0: the true one); a subsequence that begins on the 00 of a stuffed FF 00 begins one byte later
+    unsigned need = 0;
+    for (int j = 0; j < JP_PER; ++j) {
+        const int i = tid + j * JP_THREADS;
+        if (i >= nsub) break;
+        int at = i * JP_SUBSEQ;
+        if (i > 0 && r.byte(at) == 0 && r.byte(at - 1) == 0xFF) ++at;
+        s_in[i] = (uint32_t)(at * 8) << 9;
+        need |= 1u << j;
+    }
+    // 2. rounds: decode where the entry state changed, then take the predecessor's exit state
+    bool fail = false, settled = false;
+#pragma unroll 1
+    for (int round = 0; round < nsub; ++round) {
+        for (int j = 0; j < JP_PER; ++j) {
+            const int i = tid + j * JP_THREADS;
+            if (i >= nsub || !((need >> j) & 1)) continue;
+            int count = 0;
+            bool ignored = false;
+            s_out[i] = decode_subsequence<false>(r, s_in[i], min((i + 1) * JP_SUBSEQ, len) * 8, im, bpm, huff, zigzag, count, coef, total_blocks,
+                                                 0, false, ignored);
+            s_cnt[i] = count;
+        }
+        __syncthreads();
+        need = 0;
+        for (int j = 0; j < JP_PER; ++j) {
+            const int i = tid + j * JP_THREADS;
+            if (i >= nsub || i == 0) continue;
+            const uint32_t from = s_out[i - 1];
+            if (from != JP_UNKNOWN && from != s_in[i]) {             // an unknown exit tells its successor nothing
+                s_in[i] = from;
+                need |= 1u << j;
+            }
+        }
+        if (!__syncthreads_or(need != 0)) {              // the workgroup's "nothing changed"
+            settled = true;
+            break;
+        }
+    }
+    fail = !settled;
+    // 3. first block of every subsequence: thread t sums the JP_PER consecutive counts from t * JP_PER, the threads scan
+    int64_t sum = 0;
+    for (int j = 0; j < JP_PER; ++j) {
+        const int i = tid * JP_PER + j;
+        if (i < nsub) {
+            sum += s_cnt[i];
+            if (s_in[i] == JP_UNKNOWN) fail = true;
+        }
+    }
+    s_scan[tid] = sum;
+    __syncthreads();
+    for (int step = 1; step < JP_THREADS; step <<= 1) {
+        const int64_t add = tid >= step ? s_scan[tid - step] : 0;
+        __syncthreads();
+        s_scan[tid] += add;
+        __syncthreads();
+    }
+    int64_t first = s_scan[tid] - sum;
+    for (int j = 0; j < JP_PER; ++j) {
+        const int i = tid * JP_PER + j;
+        if (i < nsub) {
+            s_out[i] = (uint32_t)clampl(first, 0, 0x7fffffff);
+            first += s_cnt[i];
+        }
+    }
+    if (!__syncthreads_or(fail)) {
+        for (int j = 0; j < JP_PER; ++j) {
+            const int i = tid + j * JP_THREADS;
+            if (i >= nsub) break;
+            int count = 0;
+            decode_subsequence<true>(r, s_in[i], min((i + 1) * JP_SUBSEQ, len) * 8, im, bpm, huff, zigzag, count, coef, total_blocks,
+                                     (int64_t)s_out[i], i == nsub - 1, fail);
+        }
+    }
+    // 4. DC: per component the prefix sum of the differences in scan order, thread t a run of consecutive blocks
+    if (!__syncthreads_or(fail)) {
+        for (int c = 0; c < im.ncomp; ++c) {
+            const int rr0 = c == 0 ? 0 : im.hs * im.hs + c - 1;
+            const int per_mcu = c == 0 ? im.hs * im.hs : 1;
+            const int64_t nb = c == 0 ? im.nb0 : (int64_t)im.mw * im.mh;
+            const int64_t chunk = (nb + JP_THREADS - 1) / JP_THREADS;
+            const int64_t lo = min(tid * chunk, nb), hi = min(lo + chunk, nb);
+            sum = 0;
+            for (int64_t b = lo; b < hi; ++b) sum += *scan_block(coef, im, total_blocks, b / per_mcu * bpm, rr0 + (int)(b % per_mcu), bpm);
+            __syncthreads();
+            s_scan[tid] = sum;
+            __syncthreads();
+            for (int step = 1; step < JP_THREADS; step <<= 1) {
+                const int64_t add = tid >= step ? s_scan[tid - step] : 0;
+                __syncthreads();
+                s_scan[tid] += add;
+                __syncthreads();
+            }
+            int64_t pred = s_scan[tid] - sum;
+            for (int64_t b = lo; b < hi; ++b) {
+                int16_t* dc = scan_block(coef, im, total_blocks, b / per_mcu * bpm, rr0 + (int)(b % per_mcu), bpm);
+                pred += *dc;
+                if (pred < -32768 || pred > 32767) fail = true;         // the sequential walk saturates here: leave it to it
+                *dc = (int16_t)clampl(pred, -32768, 32767);
+            }
+        }
+    }
+    const int gave_up = __syncthreads_or(fail);
+    if (tid == 0) *gave_up_word(planes, im, total_blocks) = gave_up ? 1 : 0;
+}
+
+__global__ void __launch_bounds__(JE_THREADS)
+jpeg_entropy_kernel(const uint8_t* __restrict__ src, int64_t src_bytes, const int* __restrict__ meta, int meta_len, int16_t* __restrict__ coef,
+                    uint8_t* __restrict__ planes, int64_t total_blocks, int* __restrict__ status) {
+    __shared__ HuffLds huff[6];                      // DC of components 0..2, AC of components 0..2
+    __shared__ u32x4 window[JE_LANES];
+    __shared__ uint8_t zigzag[64];
+    const int img = blockIdx.y, lane = threadIdx.x;
+    const int* d = meta + (size_t)img * JD;
+    int flag = 0;
+    const Image im = load_image(d, total_blocks, flag);
+    const int nseg = clampi(d[5], 0, im.mw * im.mh);
+    if (blockIdx.x == 0 && lane == 0 && (flag || nseg != d[5])) atomicOr(status + img, ST_BAD_DESC);
+    if ((int)blockIdx.x * JE_LANES >= nseg) return;
+    int par_off, par_len;
+    if (parallel_eligible(d, meta, meta_len, src_bytes, im, flag, par_off, par_len)) {      // jpeg_parallel_kernel had this image:
+        if (*gave_up_word(planes, im, total_blocks) == 0) return;                           // done, or it gave up -- then from scratch
+        u32x4* mine = reinterpret_cast<u32x4*>(coef + im.blk0 * 64);
+        for (int64_t j = lane; j < im.nblk * 8; j += JE_THREADS) mine[j] = u32x4{0, 0, 0, 0};
+    }
+
+    build_tables(huff, zigzag, d, im, meta, meta_len, lane, true);
 
     const int nmcu = im.mw * im.mh;
     const int seg_at = d[4];
@@ -424,6 +787,12 @@ extern "C" size_t adamml_jpeg_decode_workspace(int64_t total_blocks) {
     return total_blocks < 1 ? 0 : (size_t)total_blocks * 192;      // int16 coefficients + uint8 planes, 64 of each per block
 }
 
+extern "C" int adamml_jpeg_decode_parallel_supported(int H, int W, int components, int sampling, int segments, int64_t coded_bytes) {
+    if (H < 1 || H > 65535 || W < 1 || W > 65535 || (int64_t)H * W > JPEG_MAX_PIXELS) return 0;
+    if ((components != 1 && components != 3) || (sampling != 1 && sampling != 2)) return 0;
+    return segments == 1 && coded_bytes >= 1 && coded_bytes <= (int64_t)JP_MAXSUB * JP_SUBSEQ ? 1 : 0;
+}
+
 extern "C" int adamml_jpeg_decode_u8(const uint8_t* src, int64_t src_bytes, const int32_t* meta, int meta_len, uint8_t* y, int64_t y_bytes,
                                      int32_t* status, void* workspace, int64_t workspace_bytes, int N, hipStream_t stream) {
     if (N < 0 || N > 65535) return adamml_set_error(ADAMML_EINVAL, "jpeg_decode_u8: N = %d outside [0, 65535]", N);
@@ -443,7 +812,9 @@ extern "C" int adamml_jpeg_decode_u8(const uint8_t* src, int64_t src_bytes, cons
     uint8_t* planes = static_cast<uint8_t*>(workspace) + total_blocks * 128;
     if (hipMemsetAsync(coef, 0, (size_t)total_blocks * 128, stream) != hipSuccess || hipMemsetAsync(status, 0, (size_t)N * 4, stream) != hipSuccess)
         return adamml_set_error(ADAMML_EINVAL, "jpeg_decode_u8: clearing the workspace failed");
-    hipLaunchKernelGGL(jpeg_entropy_kernel, dim3(JE_GRID, N), dim3(JE_THREADS), 0, stream, src, src_bytes, meta, meta_len, coef, total_blocks, status);
+    hipLaunchKernelGGL(jpeg_parallel_kernel, dim3(N), dim3(JP_THREADS), 0, stream, src, src_bytes, meta, meta_len, coef, planes, total_blocks);
+    hipLaunchKernelGGL(jpeg_entropy_kernel, dim3(JE_GRID, N), dim3(JE_THREADS), 0, stream, src, src_bytes, meta, meta_len, coef, planes, total_blocks,
+                       status);
     hipLaunchKernelGGL(jpeg_idct_kernel, dim3(JI_GRID, N), dim3(JI_THREADS), 0, stream, meta, meta_len, coef, planes, total_blocks);
     hipLaunchKernelGGL(jpeg_colour_kernel, dim3(JC_GRID, N), dim3(JC_THREADS), 0, stream, meta, planes, total_blocks, y, y_bytes);
     return adamml_check_launch("jpeg_decode_u8");

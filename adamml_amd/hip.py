@@ -183,6 +183,8 @@ def load():
     lib.adamml_dwconv_bwd_fused_workspace.restype = c_size_t
     lib.adamml_jpeg_decode_workspace.argtypes = [_L]
     lib.adamml_jpeg_decode_workspace.restype = c_size_t
+    lib.adamml_jpeg_decode_parallel_supported.argtypes = [_I, _I, _I, _I, _I, _L]
+    lib.adamml_jpeg_decode_parallel_supported.restype = c_int
     lib.adamml_conv_stem_supported.argtypes = [_DESC]
     lib.adamml_conv_stem_supported.restype = c_int
     lib.adamml_plan_run.argtypes = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int]

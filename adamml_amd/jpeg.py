@@ -16,12 +16,14 @@ import torch
 from . import hip, runtime
 
 __all__ = ['Batch', 'Info', 'Unsupported', 'decode', 'parse', 'Placement', 'ZIGZAG', 'DESC', 'STATUS_OVERRUN', 'STATUS_BAD_CODE',
-           'STATUS_BAD_INDEX', 'STATUS_BAD_DESC', 'STATUS_LEFTOVER', 'MAX_PIXELS']
+           'STATUS_BAD_INDEX', 'STATUS_BAD_DESC', 'STATUS_LEFTOVER', 'MAX_PIXELS', 'SUBSEQ_BYTES']
 
 DESC = 22                  # ints per image descriptor (include/adamml_hip.h)
 SEG = 4                    # ints per segment record
 HUFF = 80                  # ints per Huffman table: BITS[16], then HUFFVAL[256] as 64 little-endian words
 MAX_PIXELS = 1 << 24       # default pixel cap of parse(): 4096 x 4096
+SUBSEQ_BYTES = 128         # a scan without restart markers is decoded in subsequences of this many bytes, one lane each
+#                            (ADAMML_JPEG_SUBSEQ_BYTES in include/adamml_hip.h; why 128: csrc/jpeg_decode.hip)
 STATUS_OVERRUN, STATUS_BAD_CODE, STATUS_BAD_INDEX, STATUS_BAD_DESC, STATUS_LEFTOVER = 1, 2, 4, 8, 16
 
 ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
@@ -253,7 +255,9 @@ class Batch:
     meta: int32: N image descriptors of DESC words, then per image its segment records (byte offset, length, first MCU, MCU
     count), then the quantisation tables (64 words, natural order) and Huffman tables (BITS, HUFFVAL) -- identical tables stored
     once.  placements: per image a Placement; by default image i is a dense [H, W, C] array at `offsets[i]` (16-byte aligned).
-    infos may carry the files' `parse` results when the caller has them already."""
+    infos may carry the files' `parse` results when the caller has them already.
+    parallel: per image whether its entropy decoding takes the parallel stage for scans without restart markers
+    (adamml_jpeg_decode_parallel_supported) -- a label: the pixels are the same either way."""
 
     def __init__(self, files, placements=None, out_bytes=None, pin_memory=False, infos=None):
         files = list(files)
@@ -327,6 +331,12 @@ class Batch:
     @property
     def device(self):
         return self.data.device
+
+    @property
+    def parallel(self):
+        probe = hip.load().adamml_jpeg_decode_parallel_supported
+        return [bool(probe(inf.height, inf.width, inf.channels, inf.sampling, len(inf.segments), inf.segments[0][1] - inf.segments[0][0]))
+                for inf in self.infos]
 
     def to(self, device, non_blocking=False):
         """A Batch whose buffers live on `device` (asynchronous copies from pinned memory with non_blocking=True)."""

@@ -504,7 +504,16 @@ ADAMML_API int adamml_video_resample_u8(const uint8_t* src, int64_t src_bytes, c
  * kernels terminate and stay inside their buffers whatever meta and src hold.
  * workspace: adamml_jpeg_decode_workspace(total blocks of the batch) bytes, 16-byte aligned: 192 per block (int16 coefficients
  * + uint8 component planes); the call uses workspace_bytes / 192 blocks.
+ * An image whose scan is ONE segment (no restart markers) of at most 2048 * ADAMML_JPEG_SUBSEQ_BYTES bytes is entropy-decoded by a
+ * parallel stage: subsequences of ADAMML_JPEG_SUBSEQ_BYTES bytes, one lane each, decoded from guessed states and re-decoded from
+ * their predecessors' exit states until nothing changes (self-synchronising Huffman decoding), then once more into the workspace.
+ * Its scratch is LDS and the first word of the image's own plane region.  Pixels and status are those of the sequential decode, bit
+ * for bit: whenever the stage meets anything but a clean stream it leaves the image to the sequential kernel inside the same call
+ * (no host synchronisation; not observable from outside).  adamml_jpeg_decode_parallel_supported: 1 when an image of this geometry,
+ * segment count and coded length takes the parallel stage (a host function, a label for tests and tools).
  * Bounds: 0 <= N <= 65535, meta_len >= 22 N + 80, y_bytes >= 1, workspace_bytes >= 192, checked before the pointers; N == 0 is a no-op. */
+#define ADAMML_JPEG_SUBSEQ_BYTES 128
+ADAMML_API int adamml_jpeg_decode_parallel_supported(int H, int W, int components, int sampling, int segments, int64_t coded_bytes);
 ADAMML_API size_t adamml_jpeg_decode_workspace(int64_t total_blocks);
 ADAMML_API int adamml_jpeg_decode_u8(const uint8_t* src, int64_t src_bytes, const int32_t* meta, int meta_len, uint8_t* y, int64_t y_bytes,
                           int32_t* status, void* workspace, int64_t workspace_bytes, int N, hipStream_t stream);
