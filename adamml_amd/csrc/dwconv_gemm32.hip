@@ -1,28 +1,12 @@
 // Depthwise 3x3 convolution (MobileNetV2 blocks: models/sound_mobilenet_v2.py:58, models/policy_net.py:66,80)
 // forward / data-grad / weight-grad as VALU kernels (K = 9 per channel: bandwidth work, not MFMA work), and the
 // fp32 strided GEMM used by the Linear / LSTMCell layers of the policy head and the classifier heads.
-#include "common.h"
+#include "rowwalk.h"
 #include "conv_internal.h"
 #include "../../include/adamml_hip.h"
 
 
 namespace {
-
-constexpr int NT = 256;
-constexpr int MAXC = 2048;
-
-struct ChanMap {
-    int nchunk, rows_per_pass, chunk, rslot;
-    bool active;
-    __device__ ChanMap(int C, int tid) {
-        nchunk = C >> 3;
-        rows_per_pass = NT / nchunk;
-        if (rows_per_pass < 1) rows_per_pass = 1;
-        active = tid < rows_per_pass * nchunk;
-        chunk = tid % nchunk;
-        rslot = tid / nchunk;
-    }
-};
 
 struct DwP {
     const bf16_t* x;
@@ -758,7 +742,7 @@ __global__ __launch_bounds__(NT) void gemm_f32_mfma_kernel(GemmP p) {
 }
 
 static int dw_blocks(size_t P, int C, size_t* ppb_out) {
-    const int rows = NT / (C / 8) > 0 ? NT / (C / 8) : 1;
+    const int rows = rows_per_pass(C);
     size_t ppb = (size_t)rows * 8;
     size_t nblk = (P + ppb - 1) / ppb;
     if (nblk > 4096) { ppb = ((P + 4095) / 4096 + rows - 1) / rows * rows; nblk = (P + ppb - 1) / ppb; }

@@ -1,7 +1,7 @@
 """float64 references and error models of the C-ABI entry points outside the conv / elementwise conformance suites: the algebraic
 BatchNorm backward (csrc/conv_alg.hip alg_*_kernel, csrc/conv1x1_stream.hip), adamml_gemm_f32 (csrc/dwconv_gemm32.hip), the classifier
-head, adamml_colsum_f32 / adamml_lazy_colsum, the input re-layout kernels and the optimizer steps (csrc/elementwise.hip), the policy
-head, the Gumbel gate and the late fusion (csrc/policy_head.hip).
+head, adamml_colsum_f32 / adamml_lazy_colsum, the input re-layout kernels and the optimizer steps (csrc/head.hip, bn.hip, clip_input.hip,
+param.hip), the policy head, the Gumbel gate and the late fusion (csrc/policy_head.hip).
 
 Plain CPU module (it never touches torch.cuda): tests/test_abi_conformance_gpu.py and tests/test_abi_ref_cpu.py import it; the operand
 emulation, the checker and the constants are those of tests/conv_ref.py (check, err_ratio, C_ACC, U32, RHO_*, lazy_operand, bf16) and

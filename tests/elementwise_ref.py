@@ -1,4 +1,4 @@
-"""float64 references and error models of the BatchNorm, pooling, depthwise and stem kernels (csrc/elementwise.hip,
+"""float64 references and error models of the BatchNorm, pooling, depthwise and stem kernels (csrc/bn.hip, csrc/pool.hip,
 csrc/dwconv_gemm32.hip, csrc/dwconv_bwd_fused.hip, csrc/conv_stem.hip).
 
 Plain CPU module (it never touches torch.cuda): tests/test_elementwise_conformance_gpu.py and tests/test_elementwise_ref_cpu.py import it;

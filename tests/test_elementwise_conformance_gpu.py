@@ -1,6 +1,6 @@
 """Conformance of the BatchNorm, pooling, depthwise and stem kernels against float64 references (tests/elementwise_ref.py).
 
-One row per kernel instance the entry points of csrc/elementwise.hip (BatchNorm / residual / pooling launchers), csrc/dwconv_gemm32.hip,
+One row per kernel instance the entry points of csrc/bn.hip and csrc/pool.hip (BatchNorm / residual / pooling launchers), csrc/dwconv_gemm32.hip,
 csrc/dwconv_bwd_fused.hip and csrc/conv_stem.hip can launch; the row id names the entry point and the case, and
 profiles/elementwise_conformance_rows.md lists the kernel instance each row launched.  Operands are generated on the CPU from seeded
 generators (the three large rows generate on the device: 0.3 - 0.6 GB per tensor), outputs are pre-filled with NaN (or a base tensor where

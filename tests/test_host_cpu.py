@@ -200,6 +200,32 @@ def test_internal_launchers_are_declared_once_in_the_internal_header():
     assert used == declared, "declared but neither defined nor called: %s" % sorted(declared - used)
 
 
+def test_row_walk_helpers_live_in_one_header():
+    """The thread map of the row-walking kernels (struct ChanMap), the channel bound MAXC and block_channel_publish are defined in
+    csrc/rowwalk.h and in no csrc/*.hip (two copies of the thread map diverge unnoticed: each file compiles against its own), and every
+    .hip file that uses one of them includes the header."""
+    import glob
+    csrc = os.path.join(ROOT, "adamml_amd", "csrc")
+    strip = lambda src: re.sub(r"//[^\n]*|/\*.*?\*/", " ", src, flags=re.S)
+    define = r"\bstruct\s+ChanMap\b\s*\{|\bconstexpr\s+int\s+MAXC\b|\bvoid\s+block_channel_publish\s*\("
+    header = strip(open(os.path.join(csrc, "rowwalk.h")).read())
+    assert len(re.findall(define, header)) == 3
+    copies, missing, users = {}, [], 0
+    for path in sorted(glob.glob(os.path.join(csrc, "*.hip"))):
+        src = open(path).read()
+        code, name = strip(src), os.path.basename(path)
+        found = re.findall(define, code)
+        if found:
+            copies[name] = found
+        if re.search(r"\b(ChanMap|MAXC|block_channel_publish)\b", code):
+            users += 1
+            if not re.search(r'^#include "rowwalk\.h"', src, flags=re.M):
+                missing.append(name)
+    assert not copies, "row-walk helpers defined outside csrc/rowwalk.h: %s" % copies
+    assert not missing, "files that use a row-walk helper without including csrc/rowwalk.h: %s" % missing
+    assert users >= 3
+
+
 def test_environment_switch_registry_matches_the_code():
     """DESIGN.md appendix B is the complete registry of the ADAMML_* variables the product reads: the names adamml_amd/**/*.py takes from
     os.environ plus the names adamml_amd/csrc/* passes to getenv are exactly its operational and test-hook groups (the infrastructure
