@@ -782,6 +782,9 @@ static int wgrad_launch(const adamml_conv_desc_t* d, const void* dz, const void*
     const int groups = d->groups < 1 ? 1 : d->groups;
     if (ex && ex->per_group && !(workspace && workspace_bytes >= (size_t)groups * pl.nsplit * dw_numel * sizeof(float)))
         return adamml_set_error(ADAMML_EINVAL, "conv_bwd_weight_grouped: workspace too small");
+    // a workspace below the query's answer is ignored as a whole (atomic accumulation).  The query answers the largest of the plans'
+    // sizes; each plan below compares with its own, so a buffer between two of them used to be taken by one plan and not by another
+    if (!ex && workspace && workspace_bytes < adamml_conv_bwd_weight_workspace(d, cin_true)) workspace = nullptr;
     if (!ex && workspace && adamml_conv3x3_c64_wgrad_supported(d, cin_true)) {
         // 3x3 / 64 -> 64: LDS-patch kernel with one partial per workgroup (conv3x3_c64.hip)
         const int nblk = adamml_conv3x3_c64_wgrad_blocks(d, nullptr);

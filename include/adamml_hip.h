@@ -232,7 +232,8 @@ ADAMML_API int adamml_conv_bwd_data_res_prod(const adamml_conv_desc_t* d, const 
 /* autograd w.r.t. the weight: dw (fp32 OIHW, cin_true input channels) += dz^T * im2col(act(x)).  The pixel axis is
  * split over workgroups; with a workspace of adamml_conv_bwd_weight_workspace() bytes the partial tiles are written
  * with plain stores and summed by a second launch (device-scope fp32 atomics run at ~20 G/s on MI355X and would
- * otherwise bound the kernel); workspace == NULL falls back to atomic accumulation. */
+ * otherwise bound the kernel); workspace == NULL, or workspace_bytes below the query's answer, falls back to atomic accumulation
+ * and leaves the workspace alone. */
 ADAMML_API size_t adamml_conv_bwd_weight_workspace(const adamml_conv_desc_t* d, int cin_true);
 ADAMML_API int adamml_conv_bwd_weight(const adamml_conv_desc_t* d, const void* dz, const void* x, const float* in_scale,
                            const float* in_shift, float* dw, int cin_true, void* workspace, size_t workspace_bytes,

@@ -5,11 +5,14 @@ One row per kernel instance or dispatch branch; the row id names the entry point
 the kernel each row launched.  Operands are generated on the CPU from seeded generators, outputs are pre-filled with NaN (or a base
 tensor where the entry point accumulates) so that an element a kernel never writes fails, every call goes through the C ABI with
 hip.call, and the rows assert the library's dispatch probes (adamml_conv_bwd_data_alg_streams, adamml_gemm_f32_uses_mfma,
-adamml_clip_to_nhwc_four_pixel: the launchers call the same functions).  Operand buffers end in NaN slack, so a read past an operand shows in the result.  Tolerances are those derived in
+adamml_clip_to_nhwc_four_pixel: the launchers call the same functions).  Operand buffers end in NaN slack, so a read past an operand shows in the result.
+Every buffer handed to a kernel comes from tests/guarded.py: outputs, accumulators, optimizer state and workspaces inside sentinel bands,
+read-only operands compared bit for bit, both checked at the end of every row and after each launch of a row that launches twice.  Tolerances are those derived in
 tests/abi_ref.py; none is fitted to an observed error: counted roundings everywhere except the policy head and the gate forward, whose
 bound is 16 x the distance of the same computation in float32 on the CPU from float64, measured in the row.  The module prints its
 WORST table (row id -> largest err / tol): pytest -s."""
 import math
+import time
 
 import pytest
 import torch
@@ -23,9 +26,10 @@ pytestmark = pytest.mark.gpu
 
 from adamml_amd import hip  # noqa: E402
 from adamml_amd.hip import ConvDesc, call, ptr, STAT_SLOTS  # noqa: E402
-from tests.test_kernels_gpu import ssum  # noqa: E402
+from tests.guarded import workspace_launches  # noqa: E402
+from tests.test_conv_conformance_gpu import GB, guard, ssum, zstats  # noqa: E402,F401  (guard: the autouse check of every row)
 
-DEV = "cuda"
+T0 = time.time()
 WORST = {}
 NOTES = {}
 NAN = float("nan")
@@ -42,7 +46,7 @@ def report():
     yield
     if WORST:
         k = max(WORST, key=WORST.get)
-        print("\nabi conformance: largest err/tol %.4f (%s) over %d rows" % (WORST[k], k, len(WORST)))
+        print("\nabi conformance: largest err/tol %.4f (%s) over %d rows, %.0f s" % (WORST[k], k, len(WORST), time.time() - T0))
         for rid in sorted(WORST):
             print("  %-64s %.4f   %s" % (rid, WORST[rid], NOTES.get(rid, "")))
 
@@ -52,11 +56,11 @@ def seed_of(rid):
 
 
 def nan_f32(*shape):
-    return torch.full(shape, NAN, dtype=torch.float32, device=DEV)
+    return GB.out(shape, torch.float32)
 
 
 def nan_bf16(*shape):
-    return torch.full(shape, NAN, dtype=torch.bfloat16, device=DEV)
+    return GB.out(shape, torch.bfloat16)
 
 
 def passed(rid, r, what=""):
@@ -77,7 +81,7 @@ def test_alg_pack(row):
     # (an asymmetric m_pre: the kernel copies it, and a transposed read would show)
     m_pre = A.randn32(G, Cin, Cin, seed=seed + 1, scale=0.05) if pre else None
     ref = A.alg_pack_ref(w, aff, m_pre)
-    wd, ad, md = w.to(DEV), aff.to(DEV), m_pre.to(DEV) if pre else None
+    wd, ad, md = GB.frozen(w), GB.frozen(aff), GB.frozen(m_pre) if pre else None
     w_alg, epi = nan_bf16(G, Cin, Cout + Cin), nan_f32(G, Cin)
     call("adamml_alg_pack", ptr(wd), ptr(ad), ptr(md), ptr(w_alg), ptr(epi), Cout, Cin, G)
     wa, m = A.alg_pack_split(w_alg.cpu(), Cout)
@@ -106,8 +110,8 @@ def test_alg_wgrad_combine(row):
     wg = A.randn32(Cout, G * Cin, seed=seed + 4, scale=25.0) if pre else None
     base = A.randn32(Cout, Cin, seed=seed + 5) if "base" in name else torch.zeros(Cout, Cin)
     ref, tol = A.alg_wgrad_combine_ref(w, aff, P, G=None if pre else Gm, wg_pre=wg, s=sv, dw0=base)
-    wd, ad, Pd, Gd, sd, dw = w.to(DEV), aff.to(DEV), P.to(DEV), Gm.to(DEV), sv.to(DEV), base.to(DEV)
-    wgd = wg.to(DEV) if pre else None
+    wd, ad, Pd, Gd, sd, dw = GB.frozen(w), GB.frozen(aff), GB.frozen(P), GB.frozen(Gm), GB.frozen(sv), GB.inout(base)
+    wgd = GB.frozen(wg) if pre else None
     # (G is passed in the wg_pre form too, as the runtime does; it is then not read)
     call("adamml_alg_wgrad_combine", ptr(wd), ptr(ad), ptr(Pd), ptr(Gd), ptr(wgd), ptr(sd), ptr(dw), Cout, Cin, G)
     record(rid, passed(rid, A.ratio(dw.cpu(), ref, tol)), "alg_wgrad_combine_kernel" + (" (wg_pre)" if pre else " (W G formed)"))
@@ -150,7 +154,7 @@ def test_alg_sumfix(name, ratio_mean_std):
     if ratio_mean_std > 1:
         big = (vec[:, 3].double() * vec[:, 2].double() * s1).abs()
         assert (ref.abs() < 1e-2 * big).float().mean().item() > 0.5, rid + ": the operands do not cancel"
-    wd, Pd, vd, sd = w.to(DEV), Pm.to(DEV), vec.to(DEV), bins.to(DEV)
+    wd, Pd, vd, sd = GB.frozen(w), GB.frozen(Pm), GB.frozen(vec), GB.inout(bins)
     call("adamml_alg_sumfix", ptr(wd), ptr(Pd), ptr(vd), ptr(sd), Cout, Cin, G)
     out = ssum(sd).cpu()
     assert torch.equal(out[:, :Cout], s1), rid + ": sum(g') changed"
@@ -183,13 +187,13 @@ def test_conv_bwd_data_alg(row):
     base = E.rand_bf16(G * Pn, Cin, seed=seed + 5) if mode == "acc1" else None
     ref, ab, n, extra, k = A.dgrad_alg_ref(g, a, vf if lazy else None, vf[Cin:] if lazy else None, 1 if lazy else 0, 4 * Cin if lazy else 0,
                                            w_alg, epi, G, tile=not streams, base=base)
-    gd, ad, vd, wd, ed = g.to(DEV), a.to(DEV), vec.to(DEV), w_alg.to(DEV), epi.to(DEV)
-    dx = base.to(DEV) if base is not None else nan_bf16(G * Pn, Cin)
+    gd, ad, vd, wd, ed = GB.frozen(g), GB.frozen(a), GB.frozen(vec), GB.frozen(w_alg), GB.frozen(epi)
+    dx = GB.inout(base) if base is not None else nan_bf16(G * Pn, Cin)
     sc, sh = (ptr(vd.reshape(-1)), ptr(vd.reshape(-1)[Cin:])) if lazy else (None, None)
     kern = "alg_stream_kernel" if streams else "conv_gemm tile kernel (CatIn)"
     if mode == "bn":
         # the epilogue of a sole consumer: the mask of the lazily normalised a itself (z_in = a, its BatchNorm vectors, ReLU)
-        sums = torch.zeros(G, STAT_SLOTS, 2 * Cin, dtype=torch.float64, device=DEV)
+        sums = zstats(G, Cin)
         call("adamml_conv_bwd_data_alg", byref(d), ptr(gd), ptr(ad), sc, sh, ptr(wd), ptr(ed), ptr(dx), 0, ptr(ad), ptr(vd), 1, ptr(sums))
         mask = R.bn_mask(a.reshape(G * Pn, 1, 1, Cin), vec, 1, groups=G).reshape(G * Pn, Cin)
         assert 0.2 < mask.mean().item() < 0.95
@@ -215,7 +219,7 @@ def test_lazy_colsum(name, C, G, P, act, lazy):
     vec = E.bn_vectors(1 if shared else G, C, seed + 1, act or 1)
     vf, gs = vec.reshape(-1), (0 if shared else 4 * C)
     ref, ab, n = A.lazy_colsum_ref(x, vf if lazy else None, vf[C:] if lazy else None, gs, act, G)
-    xd, vd, s = x.to(DEV), vf.to(DEV), nan_f32(G, C)
+    xd, vd, s = GB.frozen(x), GB.frozen(vf), nan_f32(G, C)
     call("adamml_lazy_colsum", ptr(xd), ptr(vd) if lazy else None, ptr(vd[C:]) if lazy else None, gs, act, ptr(s), P, C, G)
     record(rid, A.f32_sum_check(s.cpu(), ref, ab, n, what=rid), "lazy_colsum_kernel")
 
@@ -242,7 +246,7 @@ def lay(values, kind, ld_pad=0, offset=0):
         buf = torch.full((offset + K * ld + SLACK,), NAN, dtype=torch.float32)
         buf[offset:offset + K * ld].view(K, ld)[:, :Rn] = values.t()
         sr, sk = 1, ld
-    d = buf.to(DEV)
+    d = GB.frozen(buf)
     return d, d.data_ptr() + 4 * offset, sr, sk
 
 
@@ -263,10 +267,11 @@ def run_gemm(rid, M, N, K, want_mfma, a_kind="row", b_kind="row", a_pad=0, b_pad
     view = cfull[:, :M].t() if c_t else cfull[:, :N]
     if c0 is not None:
         view.copy_(c0)
-    cd = cfull.to(DEV)
-    bd = bv.to(DEV) if bias else None
+    cd = GB.inout(cfull)
+    bd = GB.frozen(bv) if bias else None
     call("adamml_gemm_f32", pa, a_sm, a_sk, pb, b_sn, b_sk, ptr(cd), 1 if c_t else ldc, ldc if c_t else 1, ptr(bd), act, 1 if accumulate else 0,
          M, N, K)
+    GB.check(rid)                                                        # (a test runs several rows: each launch its own check)
     out = cd.cpu()
     h = out[:, :M].t() if c_t else out[:, :N]
     assert torch.isnan(out[:, -3:]).all(), rid + ": wrote outside the strided output"
@@ -335,8 +340,8 @@ def test_head(row):
             keep[T:2 * T] = 0                                            # every frame of clip 1
     inv_keep = 1.0 / 0.6
     W, bias = A.randn32(K, C, seed=seed + 3, scale=1.0 / math.sqrt(C)), A.randn32(K, seed=seed + 4)
-    xd, vd, Wd, bd = x.to(DEV), vf.to(DEV), W.to(DEV), bias.to(DEV)
-    kd = keep.to(DEV) if keep is not None else None
+    xd, vd, Wd, bd = GB.frozen(x), GB.frozen(vf), GB.frozen(W), GB.frozen(bias)
+    kd = GB.frozen(keep) if keep is not None else None
     feat, logits = nan_f32(rows, C), nan_f32(clips, K)
     call("adamml_head_fwd", ptr(xd), ptr(vd) if lazy else None, ptr(vd[C:]) if lazy else None, 4 * C, act if lazy else 0, ptr(kd), inv_keep, ptr(Wd),
          ptr(bd), ptr(feat), ptr(logits), clips, T, HW, C, K, G)
@@ -352,7 +357,7 @@ def test_head(row):
         assert torch.equal(hl[1], bias), name + ": an all-dropped clip must give the bias"
     # backward
     g = A.randn32(clips, K, seed=seed + 5)
-    gd, gx = g.to(DEV), nan_bf16(rows, HW, C)
+    gd, gx = GB.frozen(g), nan_bf16(rows, HW, C)
     gr = nan_f32(rows, K) if grows else None
     call("adamml_head_bwd", ptr(gd), ptr(kd), inv_keep, ptr(Wd), ptr(gx), ptr(gr), clips, T, HW, C, K)
     xref, xab, k, rref = A.head_bwd_ref(g, keep, inv_keep, W, T, HW)
@@ -367,8 +372,8 @@ def test_colsum_f32(rows, cols, accumulate):
     seed = seed_of(rid)
     a, o = A.randn32(max(rows, 1), cols, seed=seed)[:rows], A.randn32(cols, seed=seed + 1)
     ref, tol = A.colsum_ref(a, o if accumulate else None)
-    ad = torch.cat([a.reshape(-1), torch.full((SLACK,), NAN)]).to(DEV)
-    out = o.to(DEV) if accumulate else nan_f32(cols)
+    ad = GB.frozen(torch.cat([a.reshape(-1), torch.full((SLACK,), NAN)]))
+    out = GB.inout(o) if accumulate else nan_f32(cols)
     call("adamml_colsum_f32", ptr(ad), ptr(out), rows, cols, accumulate)
     record(rid, passed(rid, A.ratio(out.cpu(), ref, tol)), "colsum_f32_kernel")
 
@@ -383,9 +388,10 @@ def sgd_row(n, mu, nes, first, wd):
     seed, lr = seed_of(rid), 0.05
     p, g, mom = A.randn32(n, seed=seed, scale=0.05), A.randn32(n, seed=seed + 1), A.randn32(n, seed=seed + 2)
     out = A.sgd_ref(p, g, mom, lr, mu, wd, nes, first)
-    pd, gd = p.to(DEV), g.to(DEV)
-    md = (nan_f32(n) if first else mom.to(DEV)) if mu != 0 else None      # first step: the buffer is written, not read
+    pd, gd = GB.inout(p), GB.frozen(g)
+    md = (nan_f32(n) if first else GB.inout(mom)) if mu != 0 else None      # first step: the buffer is written, not read
     call("adamml_sgd_step", ptr(pd), ptr(gd), ptr(md), n, lr, mu, wd, nes, first)
+    GB.check(rid)
     r = passed(rid, A.ratio(A.update_of(pd.cpu(), p), *out["upd"]), "update")
     if mu != 0:
         r = max(r, passed(rid, A.ratio(md.cpu(), *out["mom"]), "mom"))
@@ -410,8 +416,9 @@ ADAM = dict(lr=1e-2, b1=0.9, b2=0.999, eps=1e-8, wd=5e-4)
 def adam_row(rid, p, g, m, v, step):
     """one adamml_adam_step from the float32 state (p, m, v) with gradient g -> the new state (CPU tensors)"""
     out = A.adam_ref(p, g, m, v, ADAM["lr"], ADAM["b1"], ADAM["b2"], ADAM["eps"], ADAM["wd"], step)
-    pd, gd, md, vd = p.to(DEV), g.to(DEV), m.to(DEV), v.to(DEV)
+    pd, gd, md, vd = GB.inout(p), GB.frozen(g), GB.inout(m), GB.inout(v)
     call("adamml_adam_step", ptr(pd), ptr(gd), ptr(md), ptr(vd), p.numel(), ADAM["lr"], ADAM["b1"], ADAM["b2"], ADAM["eps"], ADAM["wd"], step)
+    GB.check(rid)
     pn, mn, vn = pd.cpu(), md.cpu(), vd.cpu()
     ru = A.ratio(A.update_of(pn, p), *out["upd"])
     rm, rv = A.ratio(mn, *out["m"]), A.ratio(vn, *out["v"])
@@ -461,7 +468,7 @@ def test_policy_head(row):
     rid, tau = "policy_head[%s]" % A.policy_id(row), A.POLICY_TAU
     op = A.policy_operands(M, B, S, A.policy_seed(row))
     r64, r32 = A.policy_run(op, tau, torch.float64, dlin), A.policy_run(op, tau, torch.float32, dlin)
-    dv = {k: (v.to(DEV) if torch.is_tensor(v) else [t.to(DEV) for t in v]) for k, v in op.items()}
+    dv = {k: (GB.frozen(v) if torch.is_tensor(v) else [GB.frozen(t) for t in v]) for k, v in op.items()}
     H, ld = A.HID, A.FEAT + 2 * M
     w_prev = dv["w_ih"].data_ptr() + 4 * A.FEAT                          # W_ih[:, F:], row stride ld_ih = F + 2 M
     fcw, fcb = hip.ptr_array(dv["fc_w"]), hip.ptr_array(dv["fc_b"])
@@ -471,6 +478,11 @@ def test_policy_head(row):
     call("adamml_policy_head_fwd", ptr(dv["gates_x"]), w_prev, ld, ptr(dv["w_hh"]), ptr(dv["b_hh"]), fcw, fcb, ptr(dv["expo"]), tau,
          ptr(out["decisions"]), ptr(out["logits"]), ptr(out["h_all"]), ptr(out["c_all"]), ptr(out["gate_act"]), ptr(out["prev_all"]),
          ptr(out["ysoft"]), S, B, M, H)
+    GB.unwritten_ok(out["d_gates"], out["d_logits"])                     # (the backward's outputs: required again below)
+    GB.check(rid + " forward")
+    GB.written_required(out["d_gates"], out["d_logits"])
+    for k in ("c_all", "gate_act", "ysoft"):
+        GB.frozen(out[k])                                                # (read-only operands of the backward)
     call("adamml_policy_head_bwd", ptr(dv["d_dec"]), ptr(dv["d_logits_in"]) if dlin else None, w_prev, ld, ptr(dv["w_hh"]), fcw, tau,
          ptr(out["c_all"]), ptr(out["gate_act"]), ptr(out["ysoft"]), ptr(out["d_gates"]), ptr(out["d_logits"]), S, B, M, H)
     worst, note, bad = e32_rows(rid, out, r64, r32, A.POLICY_TENSORS)
@@ -488,7 +500,7 @@ def test_gumbel_gate(rows):
     lg, ex, dd = lg[:rows].contiguous(), ex[:rows].contiguous(), dd[:rows].contiguous()
     d64_, y64 = A.gate(lg.double(), ex.double(), A.h32(tau))
     _, y32 = A.gate(lg, ex, torch.tensor(tau))
-    ld, ed, dec, ys = lg.to(DEV), ex.to(DEV), nan_f32(rows), nan_f32(rows, 2)
+    ld, ed, dec, ys = GB.frozen(lg), GB.frozen(ex), nan_f32(rows), nan_f32(rows, 2)
     call("adamml_gumbel_gate_fwd", ptr(ld), ptr(ed), tau, ptr(dec), ptr(ys), rows)
     eh = A.rel_max(ys.cpu(), y64)
     worst = eh / (A.E32_FACTOR * e32_all)
@@ -497,7 +509,7 @@ def test_gumbel_gate(rows):
     assert worst <= 1.0, "%s: ysoft HIP %.3g, E32 %.3g" % (rid, eh, e32_all)
     # backward from the float32 ysoft it is given: no transcendental, a counted bound
     ref, tol = A.gate_bwd_ref(dd, y32, tau)
-    yd, ddd, dl = y32.contiguous().to(DEV), dd.to(DEV), nan_f32(rows, 2)
+    yd, ddd, dl = GB.frozen(y32.contiguous()), GB.frozen(dd), nan_f32(rows, 2)
     call("adamml_gumbel_gate_bwd", ptr(ddd), ptr(yd), tau, ptr(dl), rows)
     record("gumbel_gate_bwd[rows%d]" % rows, passed(rid, A.ratio(dl.cpu(), ref, tol), "d_logits"), "gumbel_gate_bwd_kernel")
 
@@ -517,7 +529,8 @@ def test_fusion(row):
     dec = (torch.rand(S, M, B, generator=E.gen(seed + 5)) > 0.4).float() if gated else None
     lf = (torch.rand(M - 1, generator=E.gen(seed + 6)) * 0.4).float() if learn else None
     g = A.randn32(B, C, seed=seed + 7)
-    xd, dd, lfd, gd = [t.to(DEV) for t in xs], dec.to(DEV) if gated else None, torch.cat([lf, torch.full((SLACK,), NAN)]).to(DEV) if learn else None, g.to(DEV)
+    xd, dd, gd = [GB.frozen(t) for t in xs], GB.frozen(dec) if gated else None, GB.frozen(g)
+    lfd = GB.frozen(torch.cat([lf, torch.full((SLACK,), NAN)])) if learn else None
     xp = hip.ptr_array(xd)
     out = nan_f32(B, C)
     call("adamml_fusion_fwd", xp, ptr(dd), ptr(lfd), ptr(out), S, B, C, M)
@@ -557,7 +570,7 @@ def test_clip_to_nhwc(row):
     x = A.randn32(B, S * Fr * C, H, W, seed=seed_of(name))
     assert A.taps_stable(H, OH) and A.taps_stable(W, OW), rid + ": a source index depends on the contraction of the coordinate"
     ref, tol = A.clip_ref(x, B, S, Fr, C, OH, OW, step, c_pad)
-    buf = torch.cat([torch.full((off,), NAN), x.reshape(-1), torch.full((SLACK,), NAN)]).to(DEV)
+    buf = GB.frozen(torch.cat([torch.full((off,), NAN), x.reshape(-1), torch.full((SLACK,), NAN)]))
     px = buf.data_ptr() + 4 * off
     y = nan_bf16(*ref.shape)
     four = hip.load().adamml_clip_to_nhwc_four_pixel(px, ptr(y), H, W, OH, OW, c_pad)
@@ -568,10 +581,11 @@ def test_clip_to_nhwc(row):
 
 def u8_call(x, B, S, Fr, C, H, W, OH, OW, step, c_pad, mean, std, div255, misalign):
     """adamml_clip_u8_to_nhwc on x [B, H, W, S*F*C] uint8 placed `misalign` bytes behind an aligned address"""
-    buf = torch.cat([torch.zeros(misalign, dtype=torch.uint8), x.reshape(-1), torch.zeros(SLACK, dtype=torch.uint8)]).to(DEV)
+    buf = GB.frozen(torch.cat([torch.zeros(misalign, dtype=torch.uint8), x.reshape(-1), torch.zeros(SLACK, dtype=torch.uint8)]))
     Fk = (Fr + step - 1) // step
     y = nan_bf16(S, B * Fk, OH, OW, c_pad)
     call("adamml_clip_u8_to_nhwc", buf.data_ptr() + misalign, ptr(y), B, S, Fr, C, H, W, OH, OW, step, c_pad, floats(mean), floats(std), len(mean), div255)
+    GB.check("clip_u8_to_nhwc")                                          # (a row calls this twice: each launch its own check)
     return y.cpu()
 
 
@@ -634,7 +648,7 @@ def test_clip_u8_rgbdiff(D, resize, step):
     x[0, 0, 1, 1], x[0, 0, 1, 4] = 255, 0
     assert A.taps_stable(H, OH) and A.taps_stable(W, OW)
     ref, tol = A.clip_u8_ref(x, B, S, Fr, C, OH, OW, step, c_pad, RGB_MEAN, RGB_STD, 1, diff=True)
-    buf = torch.cat([x.reshape(-1), torch.zeros(SLACK, dtype=torch.uint8)]).to(DEV)
+    buf = GB.frozen(torch.cat([x.reshape(-1), torch.zeros(SLACK, dtype=torch.uint8)]))
     y = nan_bf16(*ref.shape)
     call("adamml_clip_u8_rgbdiff_to_nhwc", ptr(buf), ptr(y), B, S, Fr, D, H, W, OH, OW, step, c_pad, floats(RGB_MEAN), floats(RGB_STD), 3)
     record(rid, passed(rid, A.ratio(y.cpu(), ref, tol)), "clip_u8_to_nhwc_kernel<true>")
@@ -648,7 +662,7 @@ def test_copy2d(rows, width, spitch, dpitch):
     n = max(rows, 1)
     src = torch.randint(0, 256, (n, spitch), generator=E.gen(seed_of(rid)), dtype=torch.uint8)
     dst0 = torch.full((n, dpitch), 0xA5, dtype=torch.uint8)
-    sd, dd = src.to(DEV), dst0.to(DEV)
+    sd, dd = GB.frozen(src), GB.inout(dst0)
     call("adamml_copy2d", ptr(dd), dpitch, ptr(sd), spitch, width, rows)
     want = dst0.clone()
     want[:rows, :width] = src[:rows, :width]
@@ -670,32 +684,57 @@ def test_alg_chain(name, Cout, Cin, G, H):
     streams = hip.load().adamml_conv_bwd_data_alg_streams(byref(d))
     assert streams == (1 if name.startswith("stream") else 0), rid + ": dispatch probe"
     fw, T, Fa, tol_dx, tol_dw, fig = A.chain_model(op, tile=not streams)
-    wd, ad, gd, vin, vec, gam = (op["w"].to(DEV), op["a_raw"].to(DEV), op["g"].to(DEV), op["vin"].reshape(-1).to(DEV), fw["vec"].to(DEV),
-                                 op["gamma"].to(DEV))
+    wd, ad, gd, vin, vec, gam = (GB.frozen(op["w"]), GB.frozen(op["a_raw"]), GB.frozen(op["g"]), GB.frozen(op["vin"].reshape(-1)), GB.frozen(fw["vec"]),
+                                 GB.frozen(op["gamma"]))
     sc, sh = ptr(vin), ptr(vin[Cin:])
-    ws = hip.wgrad_workspace(d, Cin, DEV)
-    Pm = nan_f32(G, Cout, Cin)
-    call("adamml_conv_bwd_weight_grouped", byref(d), ptr(gd), None, None, 0, 0, ptr(ad), sc, sh, ptr(Pm), Cin, ptr(ws), ws.numel() * 4)
+    lib = hip.load()
+
+    def step(what, *outs):
+        """each launch of the composition gets its own check; what a kernel wrote is the next kernel's read-only operand"""
+        GB.check("%s %s" % (rid, what))
+        for t in outs:
+            GB.frozen(t)
+
+    # the products: the per-group workspace form, exact / dirty / one float short (refused: the per-group form has no atomic path)
+    q = lib.adamml_conv_bwd_weight_workspace(byref(d), Cin)
+    (Pm,), _ = workspace_launches(
+        GB, q, lambda: (nan_f32(G, Cout, Cin),),
+        lambda outs, ws, nbytes: call("adamml_conv_bwd_weight_grouped", byref(d), ptr(gd), None, None, 0, 0, ptr(ad), sc, sh, ptr(outs[0]), Cin, ptr(ws), nbytes),
+        "refuse", rid + " products", sync=torch.cuda.synchronize)
+    step("products", Pm)
     sums = torch.zeros(G, 2 * Cout, dtype=torch.float64)
     sums[:, :Cout] = fw["g"].sum(1)                                     # (the producer of g' leaves sum(g') and a zero second half)
-    sd = E.stats_to_slots(sums, STAT_SLOTS).to(DEV)
+    sd = GB.inout(E.stats_to_slots(sums, STAT_SLOTS))
     call("adamml_alg_sumfix", ptr(wd), ptr(Pm), ptr(vec), ptr(sd), Cout, Cin, G)
-    dgam, dbet, coef, aff = torch.zeros(Cout, device=DEV), torch.zeros(Cout, device=DEV), nan_f32(G, 3, Cout), nan_f32(G, 3, Cout)
+    step("alg_sumfix", sd)
+    dgam, dbet, coef, aff = GB.inout(torch.zeros(Cout)), GB.inout(torch.zeros(Cout)), nan_f32(G, 3, Cout), nan_f32(G, 3, Cout)
     call("adamml_bn_bwd_finalize_affine", ptr(sd), STAT_SLOTS, G, float(Pn), ptr(gam), ptr(vec), ptr(dgam), ptr(dbet), ptr(coef), ptr(aff), Cout, 1.0)
-    w_alg, epi, dx = nan_bf16(G, Cin, Cout + Cin), nan_f32(G, Cin), nan_bf16(G * Pn, Cin)
+    step("bn_bwd_finalize_affine", aff)
+    w_alg, epi = nan_bf16(G, Cin, Cout + Cin), nan_f32(G, Cin)
     call("adamml_alg_pack", ptr(wd), ptr(aff), None, ptr(w_alg), ptr(epi), Cout, Cin, G)
+    step("alg_pack", w_alg, epi)
+    dx = nan_bf16(G * Pn, Cin)
     call("adamml_conv_bwd_data_alg", byref(d), ptr(gd), ptr(ad), sc, sh, ptr(w_alg), ptr(epi), ptr(dx), 0, None, None, 0, None)
+    step("conv_bwd_data_alg")
     dG = ConvDesc(1, H, H, Cin, H, H, Cin, 1, 1, 1, 0, 1, 1, 0, G, 4 * Cin)
-    wsg = hip.wgrad_workspace(dG, Cin, DEV)
-    Gm, sv, dw = nan_f32(G, Cin, Cin), nan_f32(G, Cin), torch.zeros(Cout, Cin, device=DEV)
-    call("adamml_conv_bwd_weight_grouped", byref(dG), ptr(ad), sc, sh, 1, 4 * Cin, ptr(ad), sc, sh, ptr(Gm), Cin, ptr(wsg), wsg.numel() * 4)
+    qg = lib.adamml_conv_bwd_weight_workspace(byref(dG), Cin)
+    (Gm,), _ = workspace_launches(
+        GB, qg, lambda: (nan_f32(G, Cin, Cin),),
+        lambda outs, ws, nbytes: call("adamml_conv_bwd_weight_grouped", byref(dG), ptr(ad), sc, sh, 1, 4 * Cin, ptr(ad), sc, sh, ptr(outs[0]), Cin, ptr(ws), nbytes),
+        "refuse", rid + " Gram", sync=torch.cuda.synchronize)
+    step("Gram", Gm)
+    sv, dw = nan_f32(G, Cin), GB.inout(torch.zeros(Cout, Cin))
     call("adamml_lazy_colsum", ptr(ad), sc, sh, 4 * Cin, 1, ptr(sv), Pn, Cin, G)
+    step("lazy_colsum", sv)
     call("adamml_alg_wgrad_combine", ptr(wd), ptr(aff), ptr(Pm), ptr(Gm), None, ptr(sv), ptr(dw), Cout, Cin, G)
+    step("alg_wgrad_combine")
     hx, hw = dx.cpu().double().reshape(G, Pn, Cin), dw.cpu().double()
     rx, rw = A.ratio(hx, T["dx"], tol_dx), A.ratio(hw, T["dw"], tol_dw)
     note = ("F - T (exact arithmetic, fp32 W against bf16 W): dx %.2e, dW %.2e of max; HIP - T: dx %.2e, dW %.2e of max; model at most dx %.2e, dW %.2e of max"
             % (fig["dx"], fig["dw"], A.rel_max(hx, T["dx"]), A.rel_max(hw, T["dw"]), (tol_dx.max() / T["dx"].abs().max()).item(),
                (tol_dw.max() / T["dw"].abs().max()).item()))
     print("  %s: dx %.3f dW %.3f of the model; %s" % (rid, rx, rw, note))
+    record(rid + "+dirty", 0.0, "products and Gram matrix bit-identical on a workspace of 0x00")
+    record(rid + "+short", 0.0, "workspace_bytes one float short: EINVAL, nothing written")
     record(rid, max(rx, rw), ("alg_stream_kernel" if streams else "conv_gemm tile kernel (CatIn)") + " + the kernels of the composition; " + note)
     assert rx <= 1.0 and rw <= 1.0, "%s: dx %.3g, dW %.3g of the model" % (rid, rx, rw)

@@ -7,7 +7,12 @@ names the instance (conv_gemm_kernel<BC, MODE, ...> rows: BC = output-channel ti
 library exports a probe, the row asserts it, so that a predicate narrowed later fails here by name instead of quietly testing the
 generic kernel.  Operands are generated on the CPU (bf16-representable weights, data that crosses the activation bounds, exact bound
 values planted), outputs are pre-filled with NaN (or a base tensor when accumulating) so an element a kernel never writes fails.
+Every buffer a row hands to a kernel comes from tests/guarded.py: outputs, accumulators and workspaces lie inside sentinel bands, read-only
+operands are compared bit for bit after the launch, and the rows that take a workspace run three times (exactly the size the query
+answers, the same on a workspace that held other bytes, one float short).
 The second part checks that non-finite operands propagate as they do in torch."""
+import time
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -20,10 +25,49 @@ pytestmark = pytest.mark.gpu
 from adamml_amd import hip  # noqa: E402
 from adamml_amd.hip import ConvDesc, call, ptr, STAT_SLOTS  # noqa: E402
 from adamml_amd.runtime import pad8  # noqa: E402
-from tests.test_kernels_gpu import pack, ssum  # noqa: E402
+from tests.guarded import Scope, workspace_launches  # noqa: E402
 
 DEV = "cuda"
+GB = Scope(DEV)     # every device buffer of a row (tests/guarded.py)
 WORST = {}          # row id -> max err / tol (printed at the end of the module: pytest -s)
+T0 = time.time()
+BF16, F32, F64 = torch.bfloat16, torch.float32, torch.float64
+
+
+@pytest.fixture(autouse=True)
+def guard():
+    GB.reset()
+    yield
+    GB.check("at the end of the row")
+    GB.reset()
+
+
+def pack(w, cin_pad, mode):
+    """adamml_pack_conv_weight on a CPU weight -> the packed weight, from then on a read-only operand"""
+    cout, cin, kh, kw = w.shape
+    wd = GB.frozen(w.float())
+    if mode == 2:
+        out = GB.out((kh * kw, cout), F32)
+        call("adamml_pack_conv_weight", ptr(wd), ptr(out), cout, 1, 1, kh, kw, 2)
+    elif mode == 0:
+        out = GB.out((cout, kh * kw * cin_pad), BF16)
+        call("adamml_pack_conv_weight", ptr(wd), ptr(out), cout, cin, cin_pad, kh, kw, 0)
+    else:
+        out = GB.out((cin_pad, kh * kw * cout), BF16)
+        call("adamml_pack_conv_weight", ptr(wd), ptr(out), cout, cin, cin_pad, kh, kw, 1)
+    return GB.frozen(out)               # (its bands and its interior are checked with the row's next check)
+
+
+def zstats(G, C):
+    return GB.zeros((G, STAT_SLOTS, 2 * C), F64)
+
+
+def ssum(t):
+    """per-channel totals of a statistic accumulator [G][STAT_SLOTS][2C] (adamml_stats_collapse) -> [G][2C] float64"""
+    G, _, C2 = t.shape
+    out = GB.out((G, C2), F64)
+    call("adamml_stats_collapse", ptr(t), ptr(out), C2 // 2, G)
+    return out
 
 
 def probe(name, d, *args):
@@ -39,7 +83,7 @@ def report():
     yield
     if WORST:
         k = max(WORST, key=WORST.get)
-        print("\nconv conformance: C_ACC = %g, largest err/tol %.4f (%s) over %d rows" % (R.C_ACC, WORST[k], k, len(WORST)))
+        print("\nconv conformance: C_ACC = %g, largest err/tol %.4f (%s) over %d rows, %.0f s" % (R.C_ACC, WORST[k], k, len(WORST), time.time() - T0))
         for rid in sorted(WORST):
             print("  %-60s %.4f" % (rid, WORST[rid]))
 
@@ -82,7 +126,7 @@ def plant_bounds(x):
 
 
 def nan_fill(*shape):
-    return torch.full(shape, float("nan"), dtype=torch.bfloat16, device=DEV)
+    return GB.out(shape, BF16)
 
 
 # ---------------------------------------------------------------------------------------------------------------------- forward
@@ -165,16 +209,17 @@ def test_conv_fwd(row, monkeypatch):
     w = rand_weight(Cout, Cin, k, seed + 2)
     a = R.lazy_operand(x, scale, shift, act or 0, groups=G, gstride=d.in_gstride, cin_true=Cin)
     ref, ab, n = R.conv_fwd_ref(a, w, s, p)
-    xd, wd = x.to(DEV), w.to(DEV)
-    vd = vflat.to(DEV) if act is not None else None
+    xd, wp = GB.frozen(x), pack(w, cp, 0)
+    vd = GB.frozen(vflat) if act is not None else None
     if acc:
         base = (torch.randn(ref.shape, generator=gen(seed + 3)) * ref.abs().mean()).to(torch.bfloat16)
-        y = base.to(DEV)
+        y = GB.inout(base)
     else:
         y = nan_fill(*ref.shape)
-    stats = None if acc else torch.zeros(G, STAT_SLOTS, 2 * Cout, dtype=torch.float64, device=DEV)
-    call("adamml_conv_fwd", byref(d), ptr(xd), ptr(pack(wd, cp, 0)), ptr(vd) if vd is not None else None,
+    stats = None if acc else zstats(G, Cout)
+    call("adamml_conv_fwd", byref(d), ptr(xd), ptr(wp), ptr(vd) if vd is not None else None,
          ptr(vd[cp:]) if vd is not None else None, ptr(y), ptr(stats) if stats is not None else None)
+    GB.check(rid)
     h = y.cpu()
     if acc:
         r = R.check(h, base.double() + ref, ab + base.double().abs(), n, extra=R.RHO_BF16 * ref.abs(), what=rid)
@@ -184,9 +229,10 @@ def test_conv_fwd(row, monkeypatch):
     record(rid, r)
     if "=gemm" in probes:
         monkeypatch.setenv("ADAMML_WIDE_STREAM", "0")            # (read at every call)
-        y2 = base.to(DEV) if acc else nan_fill(*ref.shape)
-        call("adamml_conv_fwd", byref(d), ptr(xd), ptr(pack(wd, cp, 0)), ptr(vd) if vd is not None else None,
+        y2 = GB.inout(base) if acc else nan_fill(*ref.shape)
+        call("adamml_conv_fwd", byref(d), ptr(xd), ptr(wp), ptr(vd) if vd is not None else None,
              ptr(vd[cp:]) if vd is not None else None, ptr(y2), None)
+        GB.check(rid + " (wide kernel off)")
         assert torch.equal(y2.cpu(), h), rid + ": not the conv_gemm_kernel result"
 
 
@@ -248,15 +294,16 @@ def test_conv_bwd_data(row):
     if cp != Cin:
         z0 = torch.zeros(ref.shape[:-1] + (cp - Cin,), dtype=torch.float64)
         ref, ab = torch.cat([ref, z0], -1), torch.cat([ab, z0], -1)
-    wp = pack(w.to(DEV), cp, 1)
-    dzd = dz.to(DEV)
+    wp = pack(w, cp, 1)
+    dzd = GB.frozen(dz)
     if acc:
         base = (torch.randn(ref.shape, generator=gen(seed + 3)) * ref.abs().mean()).to(torch.bfloat16)
-        dx = base.to(DEV)
+        dx = GB.inout(base)
     else:
         dx = nan_fill(*ref.shape)
     if bn is None:
         call("adamml_conv_bwd_data", byref(d), ptr(dzd), ptr(wp), ptr(dx), acc)
+        GB.check(rid)
         h = dx.cpu()
         if acc:
             r = R.check(h, base.double() + ref, ab + base.double().abs(), n, extra=R.RHO_BF16 * ref.abs(), what=rid)
@@ -265,9 +312,10 @@ def test_conv_bwd_data(row):
     else:
         z = plant_bounds(rand_input(G * N, H, W, cp, cp, seed + 4, scale=3.0, offset=1.0))
         vec = lazy_vectors(G, cp, seed + 5, bn)
-        zd, vd = z.to(DEV), vec.to(DEV)
-        sums = torch.zeros(G, STAT_SLOTS, 2 * cp, dtype=torch.float64, device=DEV)
+        zd, vd = GB.frozen(z), GB.frozen(vec)
+        sums = zstats(G, cp)
         call("adamml_conv_bwd_data_bn", byref(d), ptr(dzd), ptr(wp), ptr(dx), ptr(zd), ptr(vd), bn, ptr(sums))
+        GB.check(rid)
         m = R.bn_mask(z, vec, bn, groups=G)
         assert (m == 0).any() and (m == 1).any()
         h = dx.cpu()
@@ -328,18 +376,25 @@ def test_conv_bwd_weight(row):
     a = R.lazy_operand(x, scale, shift, act or 0, groups=G, gstride=d.in_gstride, cin_true=cin_true)
     ref, ab, n = R.conv_wgrad_ref(a, R.lazy_operand(dz), (Cout, cin_true, k, k), s, p)
     base = torch.randn(ref.shape, generator=gen(seed + 3)) * ref.abs().mean().item()
-    dw = base.to(DEV)
-    vd = vflat.to(DEV) if act is not None else None
-    xd, dzd = x.to(DEV), dz.to(DEV)
-    if use_ws:
-        ws = hip.wgrad_workspace(d, cin_true, DEV)
-        wsa = (ptr(ws), ws.numel() * 4)
-    else:
-        wsa = (None, 0)
-    call("adamml_conv_bwd_weight", byref(d), ptr(dzd), ptr(xd), ptr(vd) if vd is not None else None, ptr(vd[Cin:]) if vd is not None else None,
-         ptr(dw), cin_true, *wsa)
-    r = R.check(dw.cpu(), base.double() + ref, ab, n, rho=R.RHO_F32, what=rid)
-    record(rid, r)
+    vd = GB.frozen(vflat) if act is not None else None
+    xd, dzd = GB.frozen(x), GB.frozen(dz)
+
+    def launch(outs, ws, nbytes):
+        call("adamml_conv_bwd_weight", byref(d), ptr(dzd), ptr(xd), ptr(vd) if vd is not None else None, ptr(vd[Cin:]) if vd is not None else None,
+             ptr(outs[0]), cin_true, ptr(ws), nbytes)
+
+    if not use_ws:                                                      # the atomic path: no workspace at all
+        dw = GB.inout(base)
+        launch((dw,), None, 0)
+        GB.check(rid)
+        record(rid, R.check(dw.cpu(), base.double() + ref, ab, n, rho=R.RHO_F32, what=rid))
+        return
+    # exact, dirty, one float short: an undersized workspace is ignored (atomic accumulation), csrc/conv_wgrad.hip wgrad_launch
+    q = hip.load().adamml_conv_bwd_weight_workspace(byref(d), cin_true)
+    (dw,), (dw_short,) = workspace_launches(GB, q, lambda: (GB.inout(base),), launch, "fallback", rid)
+    record(rid, R.check(dw.cpu(), base.double() + ref, ab, n, rho=R.RHO_F32, what=rid))
+    record(rid + "+dirty", 0.0)
+    record(rid + "+short", R.check(dw_short.cpu(), base.double() + ref, ab, n, rho=R.RHO_F32, what=rid + "+short"))
 
 
 @pytest.mark.parametrize("C", [64, 128])
@@ -354,11 +409,15 @@ def test_conv_bwd_weight_grouped_lazy_dz(C):
     vec = lazy_vectors(G, C, seed + 1, 1)
     vflat = vec.reshape(-1)
     a = R.lazy_operand(x, vflat, vflat[C:], 1, groups=G, gstride=4 * C)
-    xd, vd = x.to(DEV), vflat.to(DEV)
-    ws = hip.wgrad_workspace(d, C, DEV)
-    out = torch.full((G, C, C), float("nan"), device=DEV)
-    call("adamml_conv_bwd_weight_grouped", byref(d), ptr(xd), ptr(vd), ptr(vd[C:]), 1, 4 * C, ptr(xd), ptr(vd), ptr(vd[C:]), ptr(out), C,
-         ptr(ws), ws.numel() * 4)
+    xd, vd = GB.frozen(x), GB.frozen(vflat)
+
+    def launch(outs, ws, nbytes):
+        call("adamml_conv_bwd_weight_grouped", byref(d), ptr(xd), ptr(vd), ptr(vd[C:]), 1, 4 * C, ptr(xd), ptr(vd), ptr(vd[C:]), ptr(outs[0]), C,
+             ptr(ws), nbytes)
+
+    # the per-group form has no atomic path: one float short is refused (EINVAL) before anything is launched
+    q = hip.load().adamml_conv_bwd_weight_workspace(byref(d), C)
+    (out,), _ = workspace_launches(GB, q, lambda: (GB.out((G, C, C), F32),), launch, "refuse", rid, sync=torch.cuda.synchronize)
     h = out.cpu()
     worst = 0.0
     for g in range(G):
@@ -366,21 +425,26 @@ def test_conv_bwd_weight_grouped_lazy_dz(C):
         ref, ab, n = R.conv_wgrad_ref(ag, ag, (C, C, 1, 1), 1, 0)
         worst = max(worst, R.check(h[g], ref.view(C, C), ab.view(C, C), n, rho=R.RHO_F32, what="%s group %d" % (rid, g)))
     record(rid, worst)
+    record(rid + "+dirty", 0.0)
+    record(rid + "+short", 0.0)
 
 
 def test_conv_bwd_weight_grouped_lazy_dz_unsupported_shape():
     """the lazy-dz form has instances for Cout == Cin in {64, >= 128} only: 64 -> 128 channels must be refused, not computed wrongly"""
     G, N, H, W, Cin, Cout = 2, 1, 8, 8, 128, 64
     d = ConvDesc(N, H, W, Cin, H, W, Cout, 1, 1, 1, 0, 1, 0, 0, G, 0)
-    x = torch.zeros(G * N, H, W, Cin, dtype=torch.bfloat16, device=DEV)
-    dz = torch.zeros(G * N, H, W, Cout, dtype=torch.bfloat16, device=DEV)
-    v = torch.ones(2 * Cout, device=DEV)
-    ws = hip.wgrad_workspace(d, Cin, DEV)
-    out = torch.zeros(G, Cout, Cin, device=DEV)
+    x = GB.frozen(torch.zeros(G * N, H, W, Cin, dtype=torch.bfloat16))
+    dz = GB.frozen(torch.zeros(G * N, H, W, Cout, dtype=torch.bfloat16))
+    v = GB.frozen(torch.ones(2 * Cout))
+    q = hip.load().adamml_conv_bwd_weight_workspace(byref(d), Cin)
+    assert q > 0
+    ws = GB.workspace(q)
+    out = GB.inout(torch.zeros(G, Cout, Cin))
     with pytest.raises(RuntimeError):
         call("adamml_conv_bwd_weight_grouped", byref(d), ptr(dz), ptr(v), ptr(v[Cout:]), 1, 0, ptr(x), None, None, ptr(out), Cin,
-             ptr(ws), ws.numel() * 4)
+             ptr(ws), q)
     torch.cuda.synchronize()
+    assert GB.untouched(out) and GB.untouched(ws)
 
 
 # ----------------------------------------------------------------------------------------------------------- non-finite operands
@@ -420,10 +484,12 @@ def test_conv_fwd_propagates_nan(row, where):
     a = R.lazy_operand(x, vflat, vflat[cp:], act, groups=2, gstride=4 * cp, cin_true=Cin)
     w = rand_weight(Cout, Cin, k, 7)
     ref = R.conv_fwd_ref(a, w, s, p)[0]
-    y = nan_fill(*ref.shape) if where == "input" else torch.zeros(ref.shape, dtype=torch.bfloat16, device=DEV)
-    stats = torch.zeros(2, STAT_SLOTS, 2 * Cout, dtype=torch.float64, device=DEV)
-    xd, vd = x.to(DEV), vflat.to(DEV)
-    call("adamml_conv_fwd", byref(d), ptr(xd), ptr(pack(w.to(DEV), cp, 0)), ptr(vd), ptr(vd[cp:]), ptr(y), ptr(stats))
+    # (NaN is what the row expects in y: an unwritten element cannot be told from a propagated one here)
+    y = GB.out(ref.shape, BF16, written=False) if where == "input" else GB.inout(torch.zeros(ref.shape, dtype=torch.bfloat16))
+    stats = zstats(2, Cout)
+    xd, vd = GB.frozen(x), GB.frozen(vflat)
+    call("adamml_conv_fwd", byref(d), ptr(xd), ptr(pack(w, cp, 0)), ptr(vd), ptr(vd[cp:]), ptr(y), ptr(stats))
+    GB.check(rid)
     finite_pattern_matches(y, ref, "%s NaN %s" % (rid, where))
 
 
@@ -436,8 +502,8 @@ def test_bn_act_add_propagates_nan(act):
     z[17, 5] = NAN
     v[0, 1, 9] = NAN                          # shift of channel 9
     idn[400, 33] = NAN
-    zd, idd, vd = z.to(DEV), idn.to(DEV), v.to(DEV)
-    out = nan_fill(P, C)
+    zd, idd, vd = GB.frozen(z), GB.frozen(idn), GB.frozen(v)
+    out = GB.out((P, C), BF16, written=False)
     call("adamml_bn_act_add", ptr(zd), ptr(vd[0, 0]), ptr(vd[0, 1]), 0, act, ptr(idd), ptr(vd[1, 0]), ptr(vd[1, 1]), 0, ptr(out), P, C, 1)
     zz, ii, vv = z.double(), idn.double(), v.double()
     pre = zz * vv[0, 0] + vv[0, 1] + ii * vv[1, 0] + vv[1, 1]
@@ -456,9 +522,9 @@ def test_maxpool_fwd_propagates_nan(H, W, lazy):
     if lazy:
         v[0, 0, 20] = NAN                     # every window of channel 20
     OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-    y = nan_fill(N, OH, OW, C)
-    idx = torch.empty(N, OH, OW, C, dtype=torch.uint8, device=DEV)
-    xd, vd = x.to(DEV), v.to(DEV)
+    y = GB.out((N, OH, OW, C), BF16, written=False)
+    idx = GB.out((N, OH, OW, C), torch.uint8)
+    xd, vd = GB.frozen(x), GB.frozen(v)
     call("adamml_maxpool2d_fwd", ptr(xd), ptr(vd[0, 0]) if lazy else None, ptr(vd[0, 1]) if lazy else None, 0, 1 if lazy else 0, ptr(y),
          ptr(idx), None, N, H, W, C, OH, OW, 1)
     a = R.lazy_operand(x, v[0, 0], v[0, 1], 1) if lazy else x.double()
@@ -476,8 +542,8 @@ def test_temporal_max_pool_propagates_nan(T):
     v = lazy_vectors(1, C, 14, 1)
     v[0, 0, 11] = NAN
     To = (T - 1) // 2 + 1
-    y = nan_fill(NB * To, H, W, C)
-    xd, vd = x.to(DEV), v.to(DEV)
+    y = GB.out((NB * To, H, W, C), BF16, written=False)
+    xd, vd = GB.frozen(x), GB.frozen(v)
     call("adamml_temporal_pool_fwd", ptr(xd), ptr(vd[0, 0]), ptr(vd[0, 1]), 0, 1, ptr(y), NB, T, H * W * C, C, 0, 1)
     a = R.lazy_operand(x, v[0, 0], v[0, 1], 1).view(NB, T, H, W, C)
     ref = F.max_pool3d(a.permute(0, 4, 1, 2, 3), (3, 1, 1), (2, 1, 1), (1, 0, 0)).permute(0, 2, 3, 4, 1).reshape(NB * To, H, W, C)
@@ -515,26 +581,29 @@ def test_fused_temporal_max_pool_propagates_nan(T, clips, H, Cin, Cout, G, lazy,
     from adamml_amd.runtime import ACT_RELU
     monkeypatch.setenv("ADAMML_FADD_TPOOL_SLICE", slice_mode)
     N, Q, To = clips * T, H * H, T // 2
-    x = rand_input(G * N, H, H, Cin, Cin, 21, scale=1.5).to(DEV)
-    xvec = lazy_vectors(G, Cin, 22, 1).to(DEV)
-    w = rand_weight(Cout, Cin, 1, 23).to(DEV)
-    wp = pack(w, Cin, 0)
+    x = GB.frozen(rand_input(G * N, H, H, Cin, Cin, 21, scale=1.5))
+    xvec = GB.frozen(lazy_vectors(G, Cin, 22, 1))
+    wp = pack(rand_weight(Cout, Cin, 1, 23), Cin, 0)
     d = ConvDesc(N, H, H, Cin, H, H, Cout, 1, 1, 1, 0, 1, ACT_RELU if lazy else 0, 0, G, 4 * Cin if lazy else 0)
     assert hip.load().adamml_conv_fwd_bn_add_tpool_supported(byref(d), T, ACT_RELU, 1 if lazy else 0)
-    vec = (torch.rand(G, 4, Cout, generator=gen(24)) * 0.5 + 0.25).to(DEV)
+    vec = GB.frozen(torch.rand(G, 4, Cout, generator=gen(24)) * 0.5 + 0.25)
     idn = torch.relu(torch.randn(G * N, H, H, Cout, generator=gen(25))).to(torch.bfloat16)
     idn[2, 3, 4, 5] = NAN                       # clip 0, frame 2: tap 1 of window 1
     idn[T + 5, H - 1, H - 1, Cout - 1] = NAN     # clip 1, frame 5: tap 2 of window 2 (and tap 0 of window 3)
-    idn = idn.to(DEV)
+    idn = GB.frozen(idn)
     sc, sh = (ptr(xvec[0, 0]), ptr(xvec[0, 1])) if lazy else (None, None)
-    full = torch.empty(G * N, H, H, Cout, dtype=torch.bfloat16, device=DEV)
+    full = GB.out((G * N, H, H, Cout), BF16, written=False)
     call("adamml_conv_fwd_bn_add", byref(d), ptr(x), ptr(wp), sc, sh, ptr(vec), ptr(idn), None, None, 0, ACT_RELU, ptr(full), None)
-    ref = torch.empty(G * clips * To, H, H, Cout, dtype=torch.bfloat16, device=DEV)
+    GB.check("conv_fwd_bn_add")
+    full = GB.frozen(full)                                               # (from here on an operand)
+    ref = GB.out((G * clips * To, H, H, Cout), BF16, written=False)
     call("adamml_temporal_pool_fwd", ptr(full), None, None, 0, 0, ptr(ref), clips, T, Q * Cout, Cout, 0, G)
-    pooled = torch.zeros_like(ref)
-    code = torch.empty((G * clips * To, H, H, Cout // 8), dtype=torch.int16, device=DEV)
+    GB.check("temporal_pool_fwd")
+    pooled = GB.inout(torch.zeros(ref.shape, dtype=torch.bfloat16))
+    code = GB.out((G * clips * To, H, H, Cout // 8), torch.int16)
     call("adamml_conv_fwd_bn_add_tpool", byref(d), ptr(x), ptr(wp), sc, sh, ptr(vec), ptr(idn), None, None, 0, ACT_RELU, T, ptr(pooled),
          ptr(code))
+    GB.check("conv_fwd_bn_add_tpool (slice %s)" % slice_mode)
     r = ref.cpu().double()
     finite_pattern_matches(pooled, r, "fused temporal max-pool (slice %s)" % slice_mode)
     fin = torch.isfinite(r)

@@ -5,8 +5,11 @@ csrc/dwconv_bwd_fused.hip and csrc/conv_stem.hip can launch; the row id names th
 profiles/elementwise_conformance_rows.md lists the kernel instance each row launched.  Operands are generated on the CPU from seeded
 generators (the three large rows generate on the device: 0.3 - 0.6 GB per tensor), outputs are pre-filled with NaN (or a base tensor where
 the entry point accumulates) so that an element a kernel never writes fails, every call goes through the C ABI with hip.call, and where
-the library exports a probe the row asserts it.  Tolerances are those derived in tests/elementwise_ref.py; none is fitted to an observed
-error.  The module prints its WORST table (row id -> largest err / tol) at the end: pytest -s.
+the library exports a probe the row asserts it.  Every buffer handed to a kernel comes from tests/guarded.py: outputs, accumulators and
+workspaces inside sentinel bands, read-only operands compared bit for bit, both checked at the end of every row (and after each launch
+where a row launches the same entry point twice); the weight-gradient rows run on a workspace of exactly the size their query answers,
+again on a workspace that held other bytes, and with workspace_bytes one float short.  Tolerances are those derived in
+tests/elementwise_ref.py; none is fitted to an observed error.  The module prints its WORST table (row id -> largest err / tol) at the end: pytest -s.
 
 Environment switches read once per process: ADAMML_DWB_SEGW (pixels per thread of dwconv_bwd_fused_kernel<1, SEGW>; default 3) and
 ADAMML_DW_S2_QUADS (0: the stride-2 data gradient through the per-pixel dwconv_bwd_data_kernel instead of the quad kernel) -- the rows run
@@ -16,6 +19,7 @@ import math
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 import torch
@@ -28,9 +32,10 @@ pytestmark = pytest.mark.gpu
 
 from adamml_amd import hip  # noqa: E402
 from adamml_amd.hip import ConvDesc, call, ptr, STAT_SLOTS  # noqa: E402
-from tests.test_kernels_gpu import pack, ssum  # noqa: E402
+from tests.guarded import workspace_launches  # noqa: E402
+from tests.test_conv_conformance_gpu import DEV, GB, guard, pack, ssum, zstats  # noqa: E402,F401  (guard: the autouse check of every row)
 
-DEV = "cuda"
+T0 = time.time()
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WORST = {}          # row id -> max err / tol (exact rows record 0)
 NOTES = {}          # row id -> a measured figure worth reporting
@@ -43,7 +48,7 @@ def record(rid, r):
 def print_table():
     if WORST:
         k = max(WORST, key=WORST.get)
-        print("\nelementwise conformance: largest err/tol %.4f (%s) over %d rows" % (WORST[k], k, len(WORST)))
+        print("\nelementwise conformance: largest err/tol %.4f (%s) over %d rows, %.0f s" % (WORST[k], k, len(WORST), time.time() - T0))
         for rid in sorted(WORST):
             print("  %-72s %.4f%s" % (rid, WORST[rid], ("   " + NOTES[rid]) if rid in NOTES else ""))
 
@@ -55,15 +60,15 @@ def report():
 
 
 def nan_bf16(*shape):
-    return torch.full(shape, float("nan"), dtype=torch.bfloat16, device=DEV)
+    return GB.out(shape, torch.bfloat16)
 
 
 def nan_f32(*shape):
-    return torch.full(shape, float("nan"), dtype=torch.float32, device=DEV)
+    return GB.out(shape, torch.float32)
 
 
 def zsums(G, C):
-    return torch.zeros(G, STAT_SLOTS, 2 * C, dtype=torch.float64, device=DEV)
+    return zstats(G, C)
 
 
 def seed_of(rid):
@@ -73,7 +78,7 @@ def seed_of(rid):
 def group_args(vec, pergroup):
     """(device vector, scale ptr, shift ptr, gstride) of a [G or 1][4][C] vector tensor"""
     C = vec.shape[-1]
-    vd = vec.reshape(-1).to(DEV)
+    vd = GB.frozen(vec.reshape(-1))
     return vd, ptr(vd), ptr(vd[C:]), (4 * C if pergroup else 0)
 
 
@@ -110,13 +115,13 @@ def test_bn_act_add(row):
     vif = vi.reshape(-1) if vi is not None else None
     ref, ab, k = E.bn_act_add_ref(z, vzf if zscale else None, vzf[C:] if zscale else None, gs, act, idn,
                                   vif, vif[C:] if vif is not None else None, gs, groups=G)
-    zd, idd = z.to(DEV), idn.to(DEV) if idn is not None else None
+    zd, idd = GB.frozen(z), GB.frozen(idn) if idn is not None else None
     vzd, zs, zt, _ = group_args(vz, pergroup)
     vid, is_, it = None, None, None
     if vi is not None:
         vid, is_, it, _ = group_args(vi, pergroup)
     out = nan_bf16(G * P, C)
-    bits = torch.full((G * P * C // 8,), 0xAA, dtype=torch.uint8, device=DEV)
+    bits = GB.inout(torch.full((G * P * C // 8,), 0xAA, dtype=torch.uint8))
     args = (ptr(zd), zs if zscale else None, zt if zscale else None, gs, act, ptr(idd), is_, it, gs, ptr(out))
     if mask:
         call("adamml_bn_act_add_mask", *args, ptr(bits), P, C, G)
@@ -139,7 +144,7 @@ def test_act_bwd_from_output():
     out = E.rand_bf16(P, C, scale=3.0, offset=1.0, seed=5).float().clamp(0, 6).to(torch.bfloat16)
     g = E.rand_bf16(P, C, seed=6)
     assert (out == 0).any() and (out == 6).any()
-    od, gd, g2 = out.to(DEV), g.to(DEV), nan_bf16(P, C)
+    od, gd, g2 = GB.frozen(out), GB.frozen(g), nan_bf16(P, C)
     call("adamml_act_bwd_from_output", ptr(gd), ptr(od), 2, ptr(g2), P * C)
     assert torch.equal(g2.cpu().double(), E.act_bwd_ref(g, out, 2)), rid
     record(rid, 0.0)
@@ -163,7 +168,7 @@ def test_row_walk_edges(C, kind, G):
     seed = seed_of(tag)
     z, g = E.act_data(G * P, C, act, seed), E.rand_bf16(G * P, C, seed=seed + 1)
     vec = E.bn_vectors(G, C, seed + 2, act)
-    zd, gd, vd = z.to(DEV), g.to(DEV), vec.to(DEV)
+    zd, gd, vd = GB.frozen(z), GB.frozen(g), GB.frozen(vec)
     # bn_bwd_reduce
     gp = g.double() * R.bn_mask(z, vec, act, groups=G)
     sref, sab = R.bn_dgrad_sums_ref(gp, z, vec, groups=G)
@@ -173,19 +178,20 @@ def test_row_walk_edges(C, kind, G):
     # bn_bwd_apply
     coef = torch.stack([vec[:, 3] * 1.3, torch.randn(G, C, generator=E.gen(seed + 3)) * 0.1, torch.randn(G, C, generator=E.gen(seed + 4)) * 0.2], 1)
     ref, ab = E.bn_bwd_apply_ref(gp, z, vec, coef, groups=G)
-    dz, cd = nan_bf16(G * P, C), coef.contiguous().to(DEV)
+    dz, cd = nan_bf16(G * P, C), GB.frozen(coef.contiguous())
     call("adamml_bn_bwd_apply", ptr(gd), ptr(zd), ptr(vd), act, ptr(cd), ptr(dz), P, C, G)
     record("bn_bwd_apply[%s]" % tag, E.point_check(dz.cpu(), ref, ab, E.K_BN_BWD_APPLY, what="bn_bwd_apply " + tag))
     # residual_bwd
     out = E.rand_bf16(G * P, C, scale=3.0, offset=1.0, seed=seed + 5).float().clamp(0, 6).to(torch.bfloat16)
     zb, vecb = E.rand_bf16(G * P, C, seed=seed + 6), E.bn_vectors(G, C, seed + 7)
-    od, zbd, vbd = out.to(DEV), zb.to(DEV), vecb.to(DEV)
+    od, zbd, vbd = GB.frozen(out), GB.frozen(zb), GB.frozen(vecb)
     g2ref = E.act_bwd_ref(g, out, act)
     for mode in ("a", "ab", "none"):
         g2, sa, sb = nan_bf16(G * P, C), zsums(G, C), zsums(G, C)
         call("adamml_residual_bwd", ptr(gd), ptr(od), act, ptr(g2), ptr(zd) if mode != "none" else None, ptr(vd) if mode != "none" else None,
              ptr(sa) if mode != "none" else None, ptr(zbd) if mode == "ab" else None, ptr(vbd) if mode == "ab" else None,
              ptr(sb) if mode == "ab" else None, P, C, G)
+        GB.check("residual_bwd %s %s" % (mode, tag))
         assert torch.equal(g2.cpu().double(), g2ref), "residual_bwd %s %s: g2" % (mode, tag)
         r = 0.0
         if mode != "none":
@@ -196,7 +202,7 @@ def test_row_walk_edges(C, kind, G):
             r = max(r, E.sums_check(ssum(sb).cpu(), rb_, ab_, P, what="residual_bwd b " + tag))
         record("residual_bwd[%s-%s]" % (mode, tag), r)
     # ACT_NONE in place (g2 == g_out: the store is skipped, the sums still come from g_out)
-    gin, sa = g.to(DEV), zsums(G, C)
+    gin, sa = GB.inout(g), zsums(G, C)
     call("adamml_residual_bwd", ptr(gin), ptr(od), 0, ptr(gin), ptr(zd), ptr(vd), ptr(sa), None, None, None, P, C, G)
     assert torch.equal(gin.cpu(), g)
     ra, aa = R.bn_dgrad_sums_ref(g.double(), z, vec, groups=G)
@@ -225,8 +231,8 @@ def test_bn_finalize(G, nslots, with_running):
     gamma, beta = torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g) * 0.2
     rm, rv = torch.randn(C, generator=g) * 0.1, torch.rand(C, generator=g) + 0.5
     ref = E.bn_finalize_ref(s, count, gamma, beta, rm if with_running else None, rv, 0.1, 1e-5)
-    sd = E.stats_to_slots(s, nslots).to(DEV)
-    gd, bd, rmd, rvd, vec = gamma.to(DEV), beta.to(DEV), rm.to(DEV), rv.to(DEV), nan_f32(G, 4, C)
+    sd = GB.frozen(E.stats_to_slots(s, nslots))
+    gd, bd, rmd, rvd, vec = GB.frozen(gamma), GB.frozen(beta), GB.inout(rm), GB.inout(rv), nan_f32(G, 4, C)
     call("adamml_bn_finalize", ptr(sd), nslots, G, count, ptr(gd), ptr(bd), ptr(rmd) if with_running else None,
          ptr(rvd) if with_running else None, 0.1, 1e-5, ptr(vec), C)
     r = E.vec_ratio(vec.cpu(), *ref["vec"])
@@ -237,8 +243,7 @@ def test_bn_finalize(G, nslots, with_running):
     assert r <= 1.0, "%s: max err/tol %.3g" % (rid, r)
     record(rid, r)
     if nslots == STAT_SLOTS and with_running:
-        out = torch.empty(G, 2 * C, dtype=torch.float64, device=DEV)
-        call("adamml_stats_collapse", ptr(sd), ptr(out), C, G)
+        out = ssum(sd)
         val, ab = E.det_decode_host(sd.cpu().permute(0, 2, 1).contiguous())
         rc = E.vec_ratio(out.cpu(), val, 32 * E.U64 * ab)
         assert rc <= 1.0, "stats_collapse G%d: %.3g" % (G, rc)
@@ -258,8 +263,8 @@ def test_bn_bwd_finalize(G, nslots):
     vec = E.bn_vectors(G, C, seed_of(rid) + 1)
     dg0, db0 = torch.randn(C, generator=g), torch.randn(C, generator=g)
     ref = E.bn_bwd_finalize_ref(sums, count, gamma, vec, dg0, db0, gs)
-    sd, gd, vd = E.stats_to_slots(sums, nslots).to(DEV), gamma.to(DEV), vec.to(DEV)
-    dg, db, coef = dg0.to(DEV), db0.to(DEV), nan_f32(G, 3, C)
+    sd, gd, vd = GB.frozen(E.stats_to_slots(sums, nslots)), GB.frozen(gamma), GB.frozen(vec)
+    dg, db, coef = GB.inout(dg0), GB.inout(db0), nan_f32(G, 3, C)
     call("adamml_bn_bwd_finalize", ptr(sd), nslots, G, count, ptr(gd), ptr(vd), ptr(dg), ptr(db), ptr(coef), C, gs)
     r = max(E.vec_ratio(coef.cpu(), *ref["coef"]), E.vec_ratio(dg.cpu(), *ref["dgamma"]), E.vec_ratio(db.cpu(), *ref["dbeta"]))
     assert r <= 1.0, "%s: max err/tol %.3g" % (rid, r)
@@ -271,7 +276,7 @@ def test_bn_bwd_finalize(G, nslots):
     ra = E.vec_ratio(aff.cpu(), aref, atol)
     assert ra <= 1.0, "bn_bwd_affine G%d: %.3g" % (G, ra)
     record("bn_bwd_affine[G%d-C20]" % G, ra)
-    dg2, db2, coef2, aff2 = dg0.to(DEV), db0.to(DEV), nan_f32(G, 3, C), nan_f32(G, 3, C)
+    dg2, db2, coef2, aff2 = GB.inout(dg0), GB.inout(db0), nan_f32(G, 3, C), nan_f32(G, 3, C)
     call("adamml_bn_bwd_finalize_affine", ptr(sd), nslots, G, count, ptr(gd), ptr(vd), ptr(dg2), ptr(db2), ptr(coef2), ptr(aff2), C, gs)
     assert torch.equal(coef2, coef) and torch.equal(aff2, aff) and torch.equal(dg2, dg) and torch.equal(db2, db), rid + ": finalize_affine"
     rf = E.vec_ratio(aff2.cpu(), *ref["aff"])
@@ -290,7 +295,7 @@ def test_bn_eval_affine():
     rm, rv = torch.randn(C, generator=g), torch.rand(C, generator=g) * 2 + 0.01
     (sref, stol), (href, htol) = E.bn_eval_affine_ref(gamma, beta, rm, rv, 1e-5)
     sc, sh = nan_f32(C), nan_f32(C)
-    dv = [t.to(DEV) for t in (gamma, beta, rm, rv)]
+    dv = [GB.frozen(t) for t in (gamma, beta, rm, rv)]
     call("adamml_bn_eval_affine", ptr(dv[0]), ptr(dv[1]), ptr(dv[2]), ptr(dv[3]), 1e-5, ptr(sc), ptr(sh), C)
     r = max(E.vec_ratio(sc.cpu(), sref, stol), E.vec_ratio(sh.cpu(), href, htol))
     assert r <= 1.0, "bn_eval_affine: %.3g" % r
@@ -332,12 +337,14 @@ def test_maxpool2d(row):
         taps = E._taps2d(E.lazy_f32(x, vf, vf[C:], act, G, 4 * C), OH, OW, -math.inf)
         tied = ((taps == taps.max(0).values) | torch.isinf(taps)).all(0)
         assert tied.double().mean().item() >= 0.01, name + ": fewer than 1 % of the windows fully tied"
-    xd = x.to(DEV)
-    vd = vec.to(DEV).reshape(-1) if vec is not None else None
-    y, idx = nan_bf16(G * N, OH, OW, C), torch.full((G * N, OH, OW, C), 0xEE, dtype=torch.uint8, device=DEV)
+    xd = GB.frozen(x)
+    vd = GB.frozen(vec).reshape(-1) if vec is not None else None
+    y, idx = nan_bf16(G * N, OH, OW, C), GB.inout(torch.full((G * N, OH, OW, C), 0xEE, dtype=torch.uint8))
     zs = nan_bf16(G * N, OH, OW, C) if zsel else None
     call("adamml_maxpool2d_fwd", ptr(xd), ptr(vd), ptr(vd[C:]) if vd is not None else None, 4 * C, act or 0, ptr(y), ptr(idx), ptr(zs),
          N, H, W, C, OH, OW, G)
+    GB.check("maxpool2d_fwd " + name)
+    idx = GB.frozen(idx)                                                 # (read-only from here on)
     assert torch.equal(y.cpu().double(), yref), name + ": y"
     assert torch.equal(idx.cpu().long(), iref), name + ": idx (first arg-max in torch's window order)"
     if zsel:
@@ -345,11 +352,12 @@ def test_maxpool2d(row):
     record("maxpool2d_fwd[%s]" % name, 0.0)
     # backward from the recorded indices, plain and accumulating
     g = E.rand_bf16(G * N, OH, OW, C, seed=seed + 2)
-    gd = g.to(DEV)
+    gd = GB.frozen(g)
     for acc in (0, 1):
         base = E.rand_bf16(G * N, H, W, C, seed=seed + 3) if acc else None
-        gx = base.to(DEV) if acc else nan_bf16(G * N, H, W, C)
+        gx = GB.inout(base) if acc else nan_bf16(G * N, H, W, C)
         call("adamml_maxpool2d_bwd", ptr(gd), ptr(idx), ptr(gx), G * N, H, W, C, OH, OW, acc)
+        GB.check("maxpool2d_bwd acc%d %s" % (acc, name))
         ref, ab = E.maxpool2d_route(g, iref, H, W, base)
         record("maxpool2d_bwd[acc%d-%s]" % (acc, name), E.point_check(gx.cpu(), ref, ab, E.K_MAXPOOL_BWD + acc, what="maxpool2d_bwd " + name))
     if act is None:
@@ -359,11 +367,11 @@ def test_maxpool2d(row):
     gp = R.bf16(routed) * R.bn_mask(x, vec, act, groups=G)
     sref, sab = R.bn_dgrad_sums_ref(gp, x, vec, groups=G)
     sums = zsums(G, C)
-    v4 = vec.to(DEV)
+    v4 = GB.frozen(vec)
     call("adamml_maxpool2d_bwd_bn_reduce", ptr(gd), ptr(idx), ptr(xd), ptr(v4), act, ptr(sums), N, H, W, C, OH, OW, G)
     record("maxpool2d_bwd_bn_reduce[%s]" % name, E.sums_check(ssum(sums).cpu(), sref, sab, N * H * W, what="maxpool2d_bwd_bn_reduce " + name))
     coef = torch.stack([vec[:, 3] * 1.3, torch.randn(G, C, generator=E.gen(seed + 4)) * 0.1, torch.randn(G, C, generator=E.gen(seed + 5)) * 0.2], 1)
-    cd, dz = coef.contiguous().to(DEV), nan_bf16(G * N, H, W, C)
+    cd, dz = GB.frozen(coef.contiguous()), nan_bf16(G * N, H, W, C)
     call("adamml_maxpool2d_bwd_bn_apply", ptr(gd), ptr(idx), ptr(xd), ptr(v4), act, ptr(cd), ptr(dz), N, H, W, C, OH, OW, G)
     ref, ab = E.bn_bwd_apply_ref(gp.reshape(-1, C), x.reshape(-1, C), vec, coef, groups=G)
     record("maxpool2d_bwd_bn_apply[%s-%s]" % ("even" if H % 2 == 0 and W % 2 == 0 else "odd", name),
@@ -393,8 +401,8 @@ def test_temporal_pool(T, mode, act):
     vec = tied_vectors(G, C, seed + 1, act) if act is not None else None
     vf = vec.reshape(-1) if vec is not None else None
     sc, sh = (vf, vf[C:]) if vf is not None else (None, None)
-    xd = x.to(DEV)
-    vd = vf.to(DEV) if vf is not None else None
+    xd = GB.frozen(x)
+    vd = GB.frozen(vf) if vf is not None else None
     y = nan_bf16(G * NB * To, HW, C)
     call("adamml_temporal_pool_fwd", ptr(xd), ptr(vd), ptr(vd[C:]) if vd is not None else None, 4 * C, act or 0, ptr(y), NB, T, HW * C, C, mode, G)
     kern = "walk<%d>" % T if T in (8, 4, 2) else "generic"
@@ -411,16 +419,19 @@ def test_temporal_pool(T, mode, act):
         record("temporal_pool_fwd[%s-%s]" % (kern, name), E.point_check(h, ref, ab, E.K_TPOOL_AVG_FWD, what="temporal_pool_fwd " + name))
         gref, gab = E.temporal_pool_bwd_ref(g, None, T, 1)
         k = E.K_TPOOL_AVG_BWD
-    gd, gx = g.to(DEV), nan_bf16(G * NB * T, HW, C)
+    gd, gx = GB.frozen(g), nan_bf16(G * NB * T, HW, C)
     call("adamml_temporal_pool_bwd", ptr(gd), ptr(xd), ptr(vd), ptr(vd[C:]) if vd is not None else None, 4 * C, act or 0, ptr(gx), NB, T, HW * C, C, mode, G)
     record("temporal_pool_bwd[%s]" % name, E.point_check(gx.cpu().reshape(G * NB, T, HW * C), gref, gab, k, what="temporal_pool_bwd " + name))
 
 
 @pytest.mark.parametrize("T", [1, 2])
 def test_temporal_avg_short_T_is_refused(T):
-    x, y = torch.zeros(T, 4, 8, dtype=torch.bfloat16, device=DEV), nan_bf16(1, 4, 8)
+    x, y = GB.frozen(torch.zeros(T, 4, 8, dtype=torch.bfloat16)), nan_bf16(1, 4, 8)
     with pytest.raises(RuntimeError):
         call("adamml_temporal_pool_fwd", ptr(x), None, None, 0, 0, ptr(y), 1, T, 32, 8, 1, 1)
+    torch.cuda.synchronize()
+    assert GB.untouched(y)
+    GB.unwritten_ok(y)
 
 
 @pytest.mark.parametrize("with_z", [True, False])
@@ -437,7 +448,7 @@ def test_temporal_pool_bwd_res(T, with_z):
     _, arg = E.temporal_pool_fwd_ref(out, None, None, 0, 0, T, 0)
     routed, rab = E.temporal_pool_bwd_ref(g, arg, T, 0)
     m = E.act_mask(out.double(), act).reshape(routed.shape)
-    od, gd, zd, vd = out.to(DEV), g.to(DEV), z.to(DEV), vec.to(DEV)
+    od, gd, zd, vd = GB.frozen(out), GB.frozen(g), GB.frozen(z), GB.frozen(vec)
     g2, sums = nan_bf16(G * NB * T, HW, C), zsums(G, C)
     call("adamml_temporal_pool_bwd_res", ptr(gd), ptr(od), act, ptr(g2), ptr(zd) if with_z else None, ptr(vd) if with_z else None, ptr(sums),
          NB, T, HW, C, G)
@@ -463,8 +474,8 @@ def test_temporal_pool_bwd_code(T):
     first = code[:, 0]
     first[first == 0] = 1                                            # tap 0 of window 0 is the padding frame: never recorded
     ref, ab = E.temporal_code_route(g, code.reshape(G * NB * To, HW, C), T)
-    cd = E.pack_codes(code).to(DEV)
-    gd, g2, sums = g.to(DEV), nan_bf16(G * NB * T, HW, C), zsums(G, C)
+    cd = GB.frozen(E.pack_codes(code))
+    gd, g2, sums = GB.frozen(g), nan_bf16(G * NB * T, HW, C), zsums(G, C)
     call("adamml_temporal_pool_bwd_code", ptr(gd), ptr(cd), ptr(g2), ptr(sums), NB, T, HW, C, G)
     h = g2.cpu()
     r = E.point_check(h.reshape(ref.shape), ref, ab, E.K_TPOOL_MAX_BWD, what="temporal_pool_bwd_code " + name)
@@ -484,15 +495,15 @@ def test_gap(N, HW, C, G, act):
     vec = E.bn_vectors(G, C, seed + 1, act) if act is not None else None
     vf = vec.reshape(-1) if vec is not None else None
     ref, ab, n = E.gap_fwd_ref(x, vf, vf[C:] if vf is not None else None, 4 * C, act or 0, N, HW, groups=G)
-    xd = x.to(DEV)
-    vd = vf.to(DEV) if vf is not None else None
+    xd = GB.frozen(x)
+    vd = GB.frozen(vf) if vf is not None else None
     out = nan_f32(G * N, C)
     call("adamml_gap_fwd", ptr(xd), ptr(vd), ptr(vd[C:]) if vd is not None else None, 4 * C, act or 0, ptr(out), N, HW, C, G)
     r = R.err_ratio(out.cpu(), ref, ab, n, R.RHO_F32)
     assert r <= 1.0, "gap_fwd %s: %.3g" % (name, r)
     record("gap_fwd[%s]" % name, r)
     g = torch.randn(G * N, C, generator=E.gen(seed + 2))
-    gd, gx = g.to(DEV), nan_bf16(G * N, HW, C)
+    gd, gx = GB.frozen(g), nan_bf16(G * N, HW, C)
     call("adamml_gap_bwd", ptr(gd), ptr(gx), G * N, HW, C)
     gref = (g.double() / HW).view(G * N, 1, C).expand(G * N, HW, C)
     record("gap_bwd[%s]" % name, E.point_check(gx.cpu(), gref, gref.abs(), E.K_GAP_BWD, what="gap_bwd " + name))
@@ -534,8 +545,8 @@ def test_dwconv(row):
     d = ConvDesc(N, H, W, C, OH, OW, C, 3, 3, s, 1, 1, 2, 0, G, 4 * C)
     vf = vec.reshape(-1)
     a = E.lazy_f32(x, vf, vf[C:], 2, G, 4 * C)
-    xd, vd, wd = x.to(DEV), vf.to(DEV), w.to(DEV)
-    wp = pack(wd, C, 2)
+    xd, vd = GB.frozen(x), GB.frozen(vf)
+    wp = pack(w, C, 2)
     # forward
     ref, ab, nt = E.dwconv_fwd_ref(a, w, s)
     y, stats = nan_bf16(G * N, OH, OW, C), zsums(G, C)
@@ -547,12 +558,13 @@ def test_dwconv(row):
     record("dwconv_fwd[%s]" % name, r)
     # data gradient, plain and accumulating
     g = E.rand_bf16(G * N, OH, OW, C, seed=seed + 3)
-    gd = g.to(DEV)
+    gd = GB.frozen(g)
     dref, dab, dnt = E.dwconv_dgrad_ref(g.double(), w, (H, W), s)
     for acc in (0, 1):
         base = E.rand_bf16(G * N, H, W, C, seed=seed + 4) if acc else None
-        dx = base.to(DEV) if acc else nan_bf16(G * N, H, W, C)
+        dx = GB.inout(base) if acc else nan_bf16(G * N, H, W, C)
         call("adamml_dwconv_bwd_data", byref(d), ptr(gd), ptr(wp), ptr(dx), acc)
+        GB.check("dwconv_bwd_data acc%d %s" % (acc, name))
         if acc:
             r = R.check(dx.cpu(), dref + base.double(), dab + base.double().abs(), 10, acc=E.dw_acc(dnt, 1), extra=R.RHO_BF16 * dref.abs(),
                         what="dwconv_bwd_data accumulate " + name)
@@ -563,7 +575,7 @@ def test_dwconv(row):
     assert hip.load().adamml_dwconv_bwd_data_bn_supported(byref(d)) == 1
     m = R.bn_mask(x, vec, 2, groups=G)
     gpd, sums = nan_bf16(G * N, H, W, C), zsums(G, C)
-    v4 = vec.to(DEV)
+    v4 = GB.frozen(vec)
     call("adamml_dwconv_bwd_data_bn", byref(d), ptr(gd), ptr(wp), ptr(gpd), ptr(xd), ptr(v4), 2, ptr(sums))
     hp = gpd.cpu()
     r = R.check(hp, dref * m, dab * m, 9, acc=E.dw_acc(dnt), what="dwconv_bwd_data_bn " + name)
@@ -577,12 +589,22 @@ def test_dwconv(row):
         r1, a1, _ = E.dwconv_wgrad_ref(a[gi * N:(gi + 1) * N], g.double()[gi * N:(gi + 1) * N], s)
         wref, wab = wref + r1, wab + a1
     base = torch.randn(C, 1, 3, 3, generator=E.gen(seed + 5))
-    for path in ("atomic", "workspace"):
-        dw = base.to(DEV)
-        ws = hip.wgrad_workspace(d, 0, xd.device, depthwise=True) if path == "workspace" else None
-        call("adamml_dwconv_bwd_weight", byref(d), ptr(gd), ptr(xd), ptr(vd), ptr(vd[C:]), ptr(dw), ptr(ws), ws.numel() * 4 if ws is not None else 0)
-        r = E.wgrad_check(dw.cpu(), wref + base.double(), wab + base.double().abs(), G * N * OH * OW, what="dwconv_bwd_weight %s %s" % (path, name))
-        record("dwconv_bwd_weight[%s-%s]" % (path, name), r)
+    def launch(outs, ws, nbytes):
+        call("adamml_dwconv_bwd_weight", byref(d), ptr(gd), ptr(xd), ptr(vd), ptr(vd[C:]), ptr(outs[0]), ptr(ws), nbytes)
+
+    def checked(dw, path):
+        return E.wgrad_check(dw.cpu(), wref + base.double(), wab + base.double().abs(), G * N * OH * OW, what="dwconv_bwd_weight %s %s" % (path, name))
+
+    dw = GB.inout(base)
+    launch((dw,), None, 0)
+    GB.check("dwconv_bwd_weight atomic " + name)
+    record("dwconv_bwd_weight[atomic-%s]" % name, checked(dw, "atomic"))
+    # exact, dirty, one float short: an undersized workspace is ignored (p.ws = nullptr in csrc/dwconv_gemm32.hip: atomic accumulation)
+    q = hip.load().adamml_dwconv_bwd_weight_workspace(byref(d))
+    (dw,), (dw_short,) = workspace_launches(GB, q, lambda: (GB.inout(base),), launch, "fallback", "dwconv_bwd_weight workspace " + name)
+    record("dwconv_bwd_weight[workspace-%s]" % name, checked(dw, "workspace"))
+    record("dwconv_bwd_weight[workspace-%s]+dirty" % name, 0.0)
+    record("dwconv_bwd_weight[workspace-%s]+short" % name, checked(dw_short, "workspace one float short"))
 
 
 def test_bn_finalize_on_a_channel_with_mean_30_std():
@@ -596,13 +618,13 @@ def test_bn_finalize_on_a_channel_with_mean_30_std():
     w = torch.zeros(C, 1, 3, 3)
     w[:, 0, 1, 1] = 1.0
     d = ConvDesc(N, H, W, C, H, W, C, 3, 3, 1, 1, 1, 0, 0, 1, 0)
-    xd, wd = x.to(DEV), w.to(DEV)
+    xd = GB.frozen(x)
     y, stats = nan_bf16(N, H, W, C), zsums(1, C)
-    call("adamml_dwconv_fwd", byref(d), ptr(xd), ptr(pack(wd, C, 2)), None, None, ptr(y), ptr(stats))
+    call("adamml_dwconv_fwd", byref(d), ptr(xd), ptr(pack(w, C, 2)), None, None, ptr(y), ptr(stats))
     assert torch.equal(y.cpu(), x)
     R.stats_check(ssum(stats), y.cpu(), what=rid, groups=1)
     n = float(N * H * W)
-    gamma, beta, vec = torch.ones(C, device=DEV), torch.zeros(C, device=DEV), nan_f32(1, 4, C)
+    gamma, beta, vec = GB.frozen(torch.ones(C)), GB.frozen(torch.zeros(C)), nan_f32(1, 4, C)
     call("adamml_bn_finalize", ptr(stats), STAT_SLOTS, 1, n, ptr(gamma), ptr(beta), None, None, 0.1, 1e-5, ptr(vec), C)
     sref, sab = R.stats_ref(x.double())
     tol = R.tolerance(sref, sab, int(n), 2.0 ** -23)
@@ -662,11 +684,19 @@ def run_fused(row, segw):
         e1, _, _ = E.dwconv_wgrad_ref(a[sl].abs(), Ez[sl], s)
         wref, wab, wextra = wref + r1, wab + a1, wextra + e1
     base = torch.randn(C, 1, 3, 3, generator=E.gen(seed + 7))
-    gd, zd, ad, xd, vd, wd = g.to(DEV), z.to(DEV), aff.to(DEV), x.to(DEV), xvec.to(DEV), w.to(DEV)
-    dx, sums, dw = nan_bf16(G * N, H, W, C), zsums(G, C), base.to(DEV)
-    ws = hip.scratch(hip.load().adamml_dwconv_bwd_fused_workspace(byref(d)), DEV)
-    call("adamml_dwconv_bwd_fused", byref(d), ptr(gd), ptr(zd), ptr(ad), ptr(pack(wd, C, 2)), ptr(xd), ptr(vd), 2, ptr(dx), ptr(sums), ptr(dw),
-         ptr(ws), ws.numel() * 4)
+    gd, zd, ad, xd, vd, wp = GB.frozen(g), GB.frozen(z), GB.frozen(aff), GB.frozen(x), GB.frozen(xvec), pack(w, C, 2)
+    rid = "dwconv_bwd_fused[segw%d-%s]" % (segw, name)
+
+    def launch(outs, ws, nbytes):
+        call("adamml_dwconv_bwd_fused", byref(d), ptr(gd), ptr(zd), ptr(ad), ptr(wp), ptr(xd), ptr(vd), 2, ptr(outs[0]), ptr(outs[1]), ptr(outs[2]),
+             ptr(ws), nbytes)
+
+    # exact, dirty, one float short: refused with EINVAL before the launch (csrc/dwconv_bwd_fused.hip)
+    q = hip.load().adamml_dwconv_bwd_fused_workspace(byref(d))
+    (dx, sums, dw), _ = workspace_launches(GB, q, lambda: (nan_bf16(G * N, H, W, C), zsums(G, C), GB.inout(base)), launch, "refuse", rid,
+                                           sync=torch.cuda.synchronize)
+    record(rid + "+dirty", 0.0)
+    record(rid + "+short", 0.0)
     h = dx.cpu()
     r_dx = R.check(h, dref * m, dab * m, 9, acc=E.dw_acc(dnt), extra=dextra * m, what="dwconv_bwd_fused dx " + name)
     sref, sab = R.bn_dgrad_sums_ref(h.double(), x, xvec, groups=G)
@@ -678,7 +708,6 @@ def run_fused(row, segw):
     dzk = R.bf16(E.f32(A * gg + E.f32(B * zz + Cc))).view(G * N, OH, OW, C)
     kref, kab, _ = E.dwconv_dgrad_ref(dzk, w, (H, W), s)
     r_k = R.err_ratio(h, kref * m, kab * m, 9, R.RHO_BF16, acc=E.dw_acc(dnt))
-    rid = "dwconv_bwd_fused[segw%d-%s]" % (segw, name)
     record(rid, max(r_dx, r_s, r_w))
     NOTES[rid] = "dx %.3f sums %.3f dW %.3f; dx against the kernel's own bf16 dz, no extra term: %.3f" % (r_dx, r_s, r_w, r_k)
     assert r_k <= 1.0, rid + ": dx against the emulated bf16 dz"
@@ -696,10 +725,14 @@ def fused_child_main():
     for row in FUSED:
         if row[5] == 1:
             run_fused(row, 2)
+            GB.check(row[0])                                             # (no fixture in the child: the check of the row by hand)
+            GB.reset()
     before = set(WORST)
     for row in DWCONV:
         if row[5] == 2:
             test_dwconv(row)
+            GB.check(row[0])
+            GB.reset()
     for k in set(WORST) - before:
         v = WORST.pop(k)
         if k.startswith("dwconv_bwd_data["):                         # (the other entry points of the row do not read the switch)
@@ -723,7 +756,8 @@ def test_switch_only_instances_child():
                 if len(p) > 2:
                     NOTES[p[0]] = " ".join(p[2:])
                 n[i] += 1
-    assert n == [sum(1 for r in FUSED if r[5] == 1), 2 * sum(1 for r in DWCONV if r[5] == 2)], n
+    # (every dwconv_bwd_fused row three times: exact, +dirty, +short)
+    assert n == [3 * sum(1 for r in FUSED if r[5] == 1), 2 * sum(1 for r in DWCONV if r[5] == 2)], n
 
 
 # ------------------------------------------------------------------------------------------------------------------------------- stems
@@ -739,9 +773,11 @@ def test_conv_stem(N, H, W, Cin, G, xc):
     x[..., Cin:] = 0
     w = R.bf16(torch.randn(64, Cin, 7, 7, generator=E.gen(seed + 1), dtype=torch.float64) * (2.0 / (Cin * 49)) ** 0.5).float()
     ref, ab, _ = R.conv_fwd_ref(x.double(), w, 2, 3)
-    xd, wd = x.to(DEV), w.to(DEV)
-    wsp = torch.empty(64, 224, dtype=torch.bfloat16, device=DEV)
+    xd, wd = GB.frozen(x), GB.frozen(w)
+    wsp = GB.out((64, 224), torch.bfloat16)
     call("adamml_pack_stem_weight", ptr(wd), ptr(wsp), 64, Cin)
+    GB.check("pack_stem_weight " + name)
+    wsp = GB.frozen(wsp)
     y, st = nan_bf16(G * N, OH, OW, 64), zsums(G, 64)
     call("adamml_conv_stem_fwd", byref(d), ptr(xd), ptr(wsp), ptr(y), ptr(st))
     h = y.cpu()
@@ -751,9 +787,16 @@ def test_conv_stem(N, H, W, Cin, G, xc):
     g = E.rand_bf16(G * N, OH, OW, 64, seed=seed + 2)
     wref, wab, n = R.conv_wgrad_ref(x.double(), g.double(), (64, Cin, 7, 7), 2, 3)
     base = torch.randn(64, Cin, 7, 7, generator=E.gen(seed + 3))
-    gd, dw = g.to(DEV), base.to(DEV)
-    wsb = hip.wgrad_workspace(d, Cin, xd.device, stem=True)
-    call("adamml_conv_stem_bwd_weight", byref(d), ptr(gd), ptr(xd), ptr(dw), Cin, ptr(wsb), wsb.numel() * 4)
+    gd = GB.frozen(g)
+
+    def launch(outs, ws, nbytes):
+        call("adamml_conv_stem_bwd_weight", byref(d), ptr(gd), ptr(xd), ptr(outs[0]), Cin, ptr(ws), nbytes)
+
+    # exact, dirty, one float short: refused with EINVAL before the launch (csrc/conv_stem.hip)
+    q = hip.load().adamml_conv_stem_bwd_weight_workspace(byref(d))
+    (dw,), _ = workspace_launches(GB, q, lambda: (GB.inout(base),), launch, "refuse", "conv_stem_bwd_weight " + name, sync=torch.cuda.synchronize)
+    record("conv_stem_bwd_weight[%s]+dirty" % name, 0.0)
+    record("conv_stem_bwd_weight[%s]+short" % name, 0.0)
     record("conv_stem_bwd_weight[%s]" % name, E.wgrad_check(dw.cpu(), wref + base.double(), wab + base.double().abs(), n,
                                                             what="conv_stem_bwd_weight " + name, products_round=False))
 
@@ -770,8 +813,8 @@ def test_conv_stem1(B, G, H, W, C):
     w = torch.randn(C, 1, 3, 3, generator=E.gen(seed + 1)) * 0.4
     a = x.transpose(0, 1).reshape(G * B, H, W, 1).double().expand(G * B, H, W, C).contiguous()        # group-major, broadcast over the channels
     ref, ab, nt = E.dwconv_fwd_ref(a, w, 2)
-    xd, wd = x.to(DEV), w.to(DEV)
-    wp = pack(wd, 1, 2)
+    xd = GB.frozen(x)
+    wp = pack(w, 1, 2)
     y, st = nan_bf16(G * B, OH, OW, C), zsums(G, C)
     call("adamml_conv_stem1_fwd", byref(d), ptr(xd), G * H * W, H * W, ptr(wp), ptr(y), ptr(st))
     h = y.cpu()
@@ -781,13 +824,24 @@ def test_conv_stem1(B, G, H, W, C):
     g = E.rand_bf16(G * B, OH, OW, C, scale=0.1, seed=seed + 2)
     wref, wab, n = E.dwconv_wgrad_ref(a, g.double(), 2)
     base = torch.randn(C, 1, 3, 3, generator=E.gen(seed + 3))
-    for path in ("atomic", "workspace"):
-        gd, dw = g.to(DEV), base.to(DEV)
-        need = hip.load().adamml_conv_stem1_bwd_weight_workspace(byref(d))
-        ws = torch.empty(need // 4 + 1, device=DEV) if path == "workspace" else None
-        call("adamml_conv_stem1_bwd_weight", byref(d), ptr(gd), ptr(xd), G * H * W, H * W, ptr(dw), ptr(ws), ws.numel() * 4 if ws is not None else 0)
-        record("conv_stem1_bwd_weight[%s-%s]" % (path, name),
-               E.wgrad_check(dw.cpu(), wref + base.double(), wab + base.double().abs(), n, what="conv_stem1_bwd_weight %s %s" % (path, name)))
+    gd = GB.frozen(g)
+
+    def launch(outs, ws, nbytes):
+        call("adamml_conv_stem1_bwd_weight", byref(d), ptr(gd), ptr(xd), G * H * W, H * W, ptr(outs[0]), ptr(ws), nbytes)
+
+    def checked(dw, path):
+        return E.wgrad_check(dw.cpu(), wref + base.double(), wab + base.double().abs(), n, what="conv_stem1_bwd_weight %s %s" % (path, name))
+
+    dw = GB.inout(base)
+    launch((dw,), None, 0)
+    GB.check("conv_stem1_bwd_weight atomic " + name)
+    record("conv_stem1_bwd_weight[atomic-%s]" % name, checked(dw, "atomic"))
+    # exact, dirty, one float short: an undersized workspace is ignored (p.ws = nullptr in csrc/dwconv_gemm32.hip: atomic accumulation)
+    q = hip.load().adamml_conv_stem1_bwd_weight_workspace(byref(d))
+    (dw,), (dw_short,) = workspace_launches(GB, q, lambda: (GB.inout(base),), launch, "fallback", "conv_stem1_bwd_weight workspace " + name)
+    record("conv_stem1_bwd_weight[workspace-%s]" % name, checked(dw, "workspace"))
+    record("conv_stem1_bwd_weight[workspace-%s]+dirty" % name, 0.0)
+    record("conv_stem1_bwd_weight[workspace-%s]+short" % name, checked(dw_short, "workspace one float short"))
 
 
 # -------------------------------------------------------------------------------------------------------------------------- large rows
@@ -796,9 +850,11 @@ def large_P(mb):
     return ((mb << 20) // (5 * 256 * 2) // 64 + 1) * 64
 
 
-def dev_bf16(rows, C, seed, scale=1.0, offset=0.0):
+def dev_bf16(rows, C, seed, scale=1.0, offset=0.0, relu=False):
+    """a read-only operand generated on the device (0.3 - 0.6 GB: not through the host)"""
     g = torch.Generator(device=DEV).manual_seed(seed)
-    return (torch.randn(rows, C, generator=g, device=DEV) * scale + offset).to(torch.bfloat16)
+    t = (torch.randn(rows, C, generator=g, device=DEV) * scale + offset).to(torch.bfloat16)
+    return GB.frozen(t.clamp_(min=0) if relu else t)
 
 
 def sums_ref_gpu(gp, z, vec, G, P, C):
@@ -827,15 +883,15 @@ def test_large_rows(kernel, mb):
     P = large_P(mb)
     assert G * P * C * 2 > (mb << 20) and P * C * 2 < (256 << 20)
     rid = "%s[large-%dMB-G5-C256-P%d]" % (kernel, mb, P)
-    vec = E.bn_vectors(G, C, 3, act).to(DEV)
+    vec = GB.frozen(E.bn_vectors(G, C, 3, act))
     z = dev_bf16(G * P, C, 1)
     r = 0.0
     if kernel == "bn_act_add_mask":
-        idn, vi = dev_bf16(G * P, C, 2), E.bn_vectors(G, C, 4, act).to(DEV)
-        out, bits = nan_bf16(G * P, C), torch.full((G * P * C // 8,), 0xAA, dtype=torch.uint8, device=DEV)
+        idn, vi = dev_bf16(G * P, C, 2), GB.frozen(E.bn_vectors(G, C, 4, act))
+        out, bits = nan_bf16(G * P, C), GB.out((G * P * C // 8,), torch.uint8)
         call("adamml_bn_act_add_mask", ptr(z), ptr(vec), ptr(vec.reshape(-1)[C:]), 4 * C, act, ptr(idn), ptr(vi), ptr(vi.reshape(-1)[C:]), 4 * C,
              ptr(out), ptr(bits), P, C, G)
-        o1, b1 = nan_bf16(P, C), torch.empty(P * C // 8, dtype=torch.uint8, device=DEV)
+        o1, b1 = nan_bf16(P, C), GB.out((P * C // 8,), torch.uint8)
         for g in range(G):
             sl = slice(g * P, (g + 1) * P)
             call("adamml_bn_act_add_mask", ptr(z[sl]), ptr(vec[g, 0]), ptr(vec[g, 1]), 0, act, ptr(idn[sl]), ptr(vi[g, 0]), ptr(vi[g, 1]), 0,
@@ -844,7 +900,7 @@ def test_large_rows(kernel, mb):
         del idn, out, bits, o1, b1
     elif kernel == "bn_bwd_apply":
         gq = dev_bf16(G * P, C, 2)
-        coef = torch.stack([vec[:, 3] * 1.3, vec[:, 2] * 0.3, vec[:, 1] * 0.4], 1).contiguous()
+        coef = GB.frozen(torch.stack([vec[:, 3] * 1.3, vec[:, 2] * 0.3, vec[:, 1] * 0.4], 1).contiguous())
         dz, d1 = nan_bf16(G * P, C), nan_bf16(P, C)
         call("adamml_bn_bwd_apply", ptr(gq), ptr(z), ptr(vec), act, ptr(coef), ptr(dz), P, C, G)
         for g in range(G):
@@ -853,8 +909,8 @@ def test_large_rows(kernel, mb):
             assert torch.equal(dz[sl], d1), "%s: group %d" % (rid, g)
         del gq, dz, d1
     else:
-        gq, out = dev_bf16(G * P, C, 2), dev_bf16(G * P, C, 5).clamp_(min=0)
-        zb, vb = dev_bf16(G * P, C, 6), E.bn_vectors(G, C, 7, act).to(DEV)
+        gq, out = dev_bf16(G * P, C, 2), dev_bf16(G * P, C, 5, relu=True)
+        zb, vb = dev_bf16(G * P, C, 6), GB.frozen(E.bn_vectors(G, C, 7, act))
         g2, sa, sb = nan_bf16(G * P, C), zsums(G, C), zsums(G, C)
         call("adamml_residual_bwd", ptr(gq), ptr(out), act, ptr(g2), ptr(z), ptr(vec), ptr(sa), ptr(zb), ptr(vb), ptr(sb), P, C, G)
         g1 = nan_bf16(P, C)
@@ -870,5 +926,7 @@ def test_large_rows(kernel, mb):
             r = max(r, E.sums_check(ssum(ss).cpu(), sref, sab, P, what="%s sums %s" % (rid, nm)))
         del gq, out, zb, g2, g1
     record(rid, r)
+    GB.check(rid)
+    GB.reset()
     del z
     torch.cuda.empty_cache()

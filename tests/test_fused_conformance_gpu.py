@@ -4,9 +4,11 @@ One row per kernel instance that adamml_conv_fwd_bn_add / _next / _tpool, adamml
 adamml_gram_stats, adamml_temporal_pool_bwd_code_prod and the weight packs can select (profiles/fused_conformance_rows.md lists what each
 row launched); the row id names the instance in brackets (conv_gemm_kernel rows: cout tile, then FADD / RES / DUAL, EID = identity-side
 operands requested at the start of the tile, LZF = fragment-side lazy input, PF = with the product, TPn = pooled over n frames).  Every
-row asserts the dispatch probe that selects its kernel, allocates every output inside a guard band of BAND pixels in front and behind
-(NaN / a byte pattern, asserted untouched), pre-fills the output itself with NaN (an element a kernel never writes fails) and compares
-per element with the counted error model of its reference.
+row asserts the dispatch probe that selects its kernel, takes every buffer it hands to a kernel from tests/guarded.py (outputs, statistic
+accumulators and workspaces inside sentinel bands, asserted untouched; read-only operands compared bit for bit after the launch),
+pre-fills the output itself with NaN (an element a kernel never writes fails) and compares per element with the counted error model of
+its reference.  The rows that take a workspace run three times: exactly the size the query answers, the same on a workspace that held
+other bytes (bit-identical outputs), and one float short (refused, nothing written).
 
 The forward rows (FADD_ROWS, NEXT_ROWS, TPOOL_ROWS) and their operand generators live in tests/fused_ref.py, not here, so that
 tests/test_fused_ref_cpu.py can bound their undecided share without a GPU; the backward, Gram and pack rows are defined below."""
@@ -24,12 +26,10 @@ from tests import fused_ref as F
 pytestmark = pytest.mark.gpu
 
 from adamml_amd import hip  # noqa: E402
-from adamml_amd.hip import ConvDesc, call, ptr, STAT_SLOTS  # noqa: E402
-from tests.test_kernels_gpu import pack, ssum  # noqa: E402
-from tests.test_conv_conformance_gpu import finite_pattern_matches  # noqa: E402
+from adamml_amd.hip import ConvDesc, call, ptr  # noqa: E402
+from tests.guarded import workspace_launches  # noqa: E402
+from tests.test_conv_conformance_gpu import GB, guard, pack, ssum, zstats, finite_pattern_matches  # noqa: E402,F401  (guard: the autouse check)
 
-DEV = "cuda"
-BAND = 128            # guard band in pixels: one pixel tile of conv_gemm_kernel (BP), four of the streaming kernels
 WORST = {}            # row id -> max err / tol (printed at the end of the module: pytest -s)
 T0 = time.time()
 NAN = float("nan")
@@ -54,32 +54,22 @@ def lib():
 
 
 class Guarded:
-    """an output of `rows` pixels x `c` elements inside a sentinel band of BAND pixels on either side"""
+    """[rows, c] view of tests/guarded.py: an output (NaN / byte pattern inside its bands), or an in/out buffer initialised from `fill`"""
 
     def __init__(self, rows, c, dtype, fill=None):
-        self.n, self.b = rows * c, BAND * c
-        if dtype in (torch.bfloat16, torch.float32):
-            self.full = torch.full((self.n + 2 * self.b,), NAN, dtype=dtype, device=DEV)
-            self.sentinel = None
-        else:
-            self.sentinel = 0xA5 if dtype == torch.uint8 else 0x5AA5
-            self.full = torch.full((self.n + 2 * self.b,), self.sentinel, dtype=dtype, device=DEV)
-        self.t = self.full[self.b:self.b + self.n].view(rows, c)
-        if fill is not None:
-            self.t.copy_(fill.reshape(rows, c))
+        self.t = GB.inout(fill.reshape(rows, c)) if fill is not None else GB.out((rows, c), dtype)
 
     def check(self, what, written=True):
-        for side in (self.full[:self.b], self.full[self.b + self.n:]):
-            ok = torch.isnan(side).all() if self.sentinel is None else (side == self.sentinel).all()
-            assert bool(ok), what + ": guard band written"
-        if written and self.sentinel is None:
-            assert not torch.isnan(self.t).any(), what + ": %d elements never written" % int(torch.isnan(self.t).sum())
+        if not written:
+            GB.unwritten_ok(self.t)
+        GB.check(what)
         return self.t
 
 
 def untouched(g):
-    """the whole allocation still holds its sentinel (an unsupported call must not write)"""
-    return bool(torch.isnan(g.full).all() if g.sentinel is None else (g.full == g.sentinel).all())
+    """the whole allocation is as it was handed out (an unsupported call must not write)"""
+    GB.unwritten_ok(g.t)
+    return GB.untouched(g.t)
 
 
 def setenv(monkeypatch, env, *names):
@@ -90,17 +80,35 @@ def setenv(monkeypatch, env, *names):
 
 
 def w4(w):
-    return w.reshape(w.shape[0], w.shape[1], 1, 1).to(DEV)
+    return w.reshape(w.shape[0], w.shape[1], 1, 1)
 
 
-def collapse(s, C, G):
-    out = torch.empty(G, 2 * C, dtype=torch.float64, device=DEV)
-    call("adamml_stats_collapse", ptr(s), ptr(out), C, G)
+def collapse(s, C, G, written=True):
+    out = ssum(s)
+    if not written:
+        GB.unwritten_ok(out)
     return out.cpu()
 
 
 def stat_acc(G, C):
-    return torch.zeros(G, STAT_SLOTS, 2 * C, dtype=torch.float64, device=DEV)
+    return zstats(G, C)
+
+
+def three(q, outputs, launch, rid):
+    """exact / dirty / short launches of a workspace row whose entry point refuses an undersized workspace (tests/guarded.py); outputs()
+    -> Guarded objects and accumulators.  The table gets the two extra launches as rows of their own."""
+    def raw(o):
+        return o.t if isinstance(o, Guarded) else o
+    made = []
+
+    def make():
+        made.append(outputs())
+        return tuple(raw(o) for o in made[-1])
+
+    workspace_launches(GB, q, make, lambda outs, ws, nbytes: launch(made[-1], ws, nbytes), "refuse", rid, sync=torch.cuda.synchronize)
+    record(rid + "+dirty", 0.0)
+    record(rid + "+short", 0.0)
+    return made[0], None
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ forward
@@ -109,12 +117,12 @@ class FwdArgs:
         Cin, Cout, G = row["Cin"], row["Cout"], row["G"]
         lazy = op["xvec"] is not None
         self.d = ConvDesc(N, H, W, Cin, H, W, Cout, 1, 1, 1, 0, 1, (op["in_act"] or 0) if lazy else 0, 0, G, 4 * Cin if lazy else 0)
-        self.x = op["x"].to(DEV)
-        self.xv = op["xvec"].reshape(-1).to(DEV) if lazy else None
+        self.x = GB.frozen(op["x"])
+        self.xv = GB.frozen(op["xvec"].reshape(-1)) if lazy else None
         self.wp = pack(w4(op["w"]), Cin, 0)
-        self.vec = op["vec"].to(DEV)
-        self.idn = op["idn"].to(DEV) if op["idn"] is not None else None
-        self.iv = op["ivec"].reshape(-1).to(DEV) if op["ivec"] is not None else None
+        self.vec = GB.frozen(op["vec"])
+        self.idn = GB.frozen(op["idn"])
+        self.iv = GB.frozen(op["ivec"].reshape(-1)) if op["ivec"] is not None else None
         self.head = (byref(self.d), ptr(self.x), ptr(self.wp), ptr(self.xv), ptr(self.xv[Cin:]) if lazy else None, ptr(self.vec), ptr(self.idn),
                      ptr(self.iv), ptr(self.iv[Cout:]) if self.iv is not None else None, op["id_gstride"], row["act"])
 
@@ -233,23 +241,24 @@ def res_operands(row):
     return op
 
 
-def run_res(row, op):
+def run_res(row, op, finite=True):
+    """finite=False: the row plants NaN, which the sums then hold as well"""
     G, P, C, K = row["G"], row["P"], row["C"], row["K"]
     d = ConvDesc(1, P, 1, C, P, 1, K, 1, 1, 1, 0, 1, 0, 0, G, 0)
     assert lib().adamml_conv_bwd_data_res_supported(byref(d)) == 1
     assert lib().adamml_conv_bwd_data_res_streams(byref(d)) == row["stream"], "dispatch probe"
     streams = bool(row["stream"] and row["acc"] and row["form"] == "bits" and not row["za"])        # the launcher's own condition
     assert streams == row["id"].startswith("stream-"), "the row id names the other kernel family"
-    keep = {k: (v.to(DEV) if torch.is_tensor(v) else v) for k, v in op.items()}
+    keep = {k: (GB.frozen(v) if torch.is_tensor(v) and k != "dx_in" else v) for k, v in op.items()}
     wp = pack(w4(op["w"]), C, 1)
-    dx = Guarded(G * P, C, torch.bfloat16, fill=keep["dx_in"] if row["acc"] else None)
+    dx = Guarded(G * P, C, torch.bfloat16, fill=op["dx_in"] if row["acc"] else None)
     sa, sb = stat_acc(G, C), stat_acc(G, C)
     bits = row["form"] == "bits"
     res_out = dx.t if (bits and row["acc"]) else keep["res_out"]          # (the mask form never reads res_out: the runtime passes dx)
     call("adamml_conv_bwd_data_res", byref(d), ptr(keep["dz"]), ptr(wp), ptr(dx.t), row["acc"], ptr(res_out), ptr(keep["bits"]) if bits else None,
          row["res_act"], ptr(keep["za"]) if row["za"] else None, ptr(keep["va"]), ptr(sa), ptr(keep["zb"]) if row["zb"] else None,
          ptr(keep["vb"]) if row["zb"] else None, ptr(sb) if row["zb"] else None)
-    return dx, collapse(sa, C, G), collapse(sb, C, G)
+    return dx, collapse(sa, C, G, finite), collapse(sb, C, G, finite)
 
 
 @pytest.mark.parametrize("row", RES_ROWS, ids=[r["id"] for r in RES_ROWS])
@@ -306,17 +315,21 @@ def test_conv_bwd_data_res_prod(row, monkeypatch):
     assert lib().adamml_conv_bwd_data_res_prod_supported(byref(d), 64) == 1
     assert lib().adamml_conv_bwd_data_res_prod_streams(byref(d), 64) == streams, "dispatch probe"
     op = prod_operands(rid, G, P, C, K, lazy, a_act)
-    dv = {k: (v.to(DEV) if torch.is_tensor(v) else v) for k, v in op.items()}
+    dv = {k: (GB.frozen(v) if torch.is_tensor(v) and k != "dx_in" else v) for k, v in op.items()}
     wp = pack(w4(op["w"]), C, 1)
     avf = dv["av"].reshape(-1) if lazy else None
-    need = lib().adamml_conv_bwd_data_res_prod_workspace(byref(d))
-    ws = torch.full((need // 4 + 1,), NAN, device=DEV)
-    for rep in range(2):            # twice on the same workspace: the partials are overwritten, not accumulated
-        dx = Guarded(G * P, C, torch.bfloat16, fill=dv["dx_in"])
-        prod = Guarded(G * C, 64, torch.float32)
-        sa = stat_acc(G, C)
+
+    def launch(outs, ws, nbytes):
+        dx, prod, sa = outs
         call("adamml_conv_bwd_data_res_prod", byref(d), ptr(dv["dz"]), ptr(wp), ptr(dx.t), ptr(dv["bits"]), 1, ptr(sa), ptr(dv["a"]), ptr(avf),
-             ptr(avf[64:]) if lazy else None, a_act if lazy else 0, 4 * 64 if lazy else 0, 64, ptr(prod.t), ptr(ws), ws.numel() * 4)
+             ptr(avf[64:]) if lazy else None, a_act if lazy else 0, 4 * 64 if lazy else 0, 64, ptr(prod.t), ptr(ws), nbytes)
+
+    def outputs():
+        return Guarded(G * P, C, torch.bfloat16, fill=op["dx_in"]), Guarded(G * C, 64, torch.float32), stat_acc(G, C)
+
+    # exact, dirty (the partials are overwritten, never read first), one float short: refused by both launchers before anything runs
+    need = lib().adamml_conv_bwd_data_res_prod_workspace(byref(d))
+    (dx, prod, sa), _ = three(need, outputs, launch, rid)
     h = dx.check(rid).cpu().reshape(G, P, C)
     ph = prod.check(rid + " prod").cpu().reshape(G, C, 64)
     s = collapse(sa, C, G)
@@ -343,17 +356,17 @@ def test_conv_bwd_data_res_prod_below_the_workgroup_term_is_refused(monkeypatch)
     assert lib().adamml_conv_bwd_data_res_prod_supported(byref(d), 64) == 0
     assert lib().adamml_conv_bwd_data_res_prod_supported(byref(ConvDesc(1, P + 128, 1, C, P + 128, 1, K, 1, 1, 1, 0, 1, 0, 0, G, 0)), 64) == 1
     dx, prod = Guarded(G * P, C, torch.bfloat16), Guarded(G * C, 64, torch.float32)
-    dz = torch.zeros(G * P, K, dtype=torch.bfloat16, device=DEV)
-    wp = torch.zeros(C, K, dtype=torch.bfloat16, device=DEV)
-    bits = torch.zeros(G * P * C // 8, dtype=torch.uint8, device=DEV)
-    a = torch.zeros(G * P, 64, dtype=torch.bfloat16, device=DEV)
+    dz = GB.frozen(torch.zeros(G * P, K, dtype=torch.bfloat16))
+    wp = GB.frozen(torch.zeros(C, K, dtype=torch.bfloat16))
+    bits = GB.frozen(torch.zeros(G * P * C // 8, dtype=torch.uint8))
+    a = GB.frozen(torch.zeros(G * P, 64, dtype=torch.bfloat16))
     sa = stat_acc(G, C)
-    ws = torch.empty(1 << 20, device=DEV)
+    ws = GB.workspace(4 << 20)
     with pytest.raises(RuntimeError, match=r"\(-2\)"):
         call("adamml_conv_bwd_data_res_prod", byref(d), ptr(dz), ptr(wp), ptr(dx.t), ptr(bits), 1, ptr(sa), ptr(a), None, None, 0, 0, 64, ptr(prod.t),
-             ptr(ws), ws.numel() * 4)
+             ptr(ws), ws.numel())
     torch.cuda.synchronize()
-    assert untouched(dx) and untouched(prod) and not sa.any()
+    assert untouched(dx) and untouched(prod) and GB.untouched(sa) and GB.untouched(ws)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------- dual
@@ -386,11 +399,11 @@ def test_conv_bwd_data_dual(row):
     zin = E.act_data(G * P, Cin, bn, s + 4) if bn else None
     vin = E.bn_vectors(G, Cin, s + 5, bn) if bn else None
     base = E.rand_bf16(G * P, Cin, seed=s + 6) if mode == "acc" else None
-    gd, zd, ad, wp = g.to(DEV), z.to(DEV), aff.to(DEV), pack(w4(w), Cin, 1)
-    zind, vind = (zin.to(DEV), vin.to(DEV)) if bn else (None, None)
+    gd, zd, ad, wp = GB.frozen(g), GB.frozen(z), GB.frozen(aff), pack(w4(w), Cin, 1)
+    zind, vind = (GB.frozen(zin), GB.frozen(vin)) if bn else (None, None)
     res = []
     for with_side in (True, False):
-        dx = Guarded(G * P, Cin, torch.bfloat16, fill=base.to(DEV) if base is not None else None)
+        dx = Guarded(G * P, Cin, torch.bfloat16, fill=base)
         side = Guarded(G * P, Cout, torch.bfloat16) if with_side else None
         sums = stat_acc(G, Cin) if bn else None
         call("adamml_conv_bwd_data_dual", byref(d), ptr(gd), ptr(zd), ptr(ad), ptr(side.t) if side else None, ptr(wp), ptr(dx.t),
@@ -415,9 +428,9 @@ def test_conv_bwd_data_dual_cout_limit():
     P, Cin, Cout = 64, 128, 520
     d = ConvDesc(1, P, 1, Cin, P, 1, Cout, 1, 1, 1, 0, 1, 0, 0, 1, 0)
     assert lib().adamml_conv_bwd_data_dual_supported(byref(d)) == 0
-    g = torch.zeros(P, Cout, dtype=torch.bfloat16, device=DEV)
-    aff = torch.zeros(3, Cout, device=DEV)
-    wp = torch.zeros(Cin, Cout, dtype=torch.bfloat16, device=DEV)
+    g = GB.frozen(torch.zeros(P, Cout, dtype=torch.bfloat16))
+    aff = GB.frozen(torch.zeros(3, Cout))
+    wp = GB.frozen(torch.zeros(Cin, Cout, dtype=torch.bfloat16))
     dx, side = Guarded(P, Cin, torch.bfloat16), Guarded(P, Cout, torch.bfloat16)
     with pytest.raises(RuntimeError, match=r"\(-2\)"):
         call("adamml_conv_bwd_data_dual", byref(d), ptr(g), ptr(g), ptr(aff), ptr(side.t), ptr(wp), ptr(dx.t), 0, None, None, 0, None)
@@ -437,13 +450,16 @@ def gram_id(row):
     return "gram-C%d-P%d-g%d-%s-act%d[gram_colsum_kernel<%d,%d>]" % (C, P, G, "lazy" if lazy else "plain", act, C, {64: 8, 128: 4, 256: 2}[C])
 
 
-def run_gram(x, vec, act, P, C, G):
-    xd = x.to(DEV)
-    vd = vec.reshape(-1).to(DEV) if vec is not None else None
-    Gm, sv = Guarded(G * C, C, torch.float32), Guarded(G, C, torch.float32)
+def run_gram(x, vec, act, P, C, G, rid):
+    xd = GB.frozen(x)
+    vd = GB.frozen(vec.reshape(-1)) if vec is not None else None
+
+    def launch(outs, ws, nbytes):
+        call("adamml_gram_colsum", ptr(xd), ptr(vd), ptr(vd[C:]) if vd is not None else None, 4 * C, act, ptr(outs[0].t), ptr(outs[1].t), P, C, G,
+             ptr(ws), nbytes)
+
     need = lib().adamml_gram_colsum_workspace(P, C, G)
-    ws = torch.full((need // 4 + 1,), NAN, device=DEV)
-    call("adamml_gram_colsum", ptr(xd), ptr(vd), ptr(vd[C:]) if vd is not None else None, 4 * C, act, ptr(Gm.t), ptr(sv.t), P, C, G, ptr(ws), ws.numel() * 4)
+    (Gm, sv), _ = three(need, lambda: (Guarded(G * C, C, torch.float32), Guarded(G, C, torch.float32)), launch, rid)
     return Gm, sv
 
 
@@ -455,7 +471,7 @@ def test_gram_colsum(row):
     s = F.seed_of(rid)
     x = E.plant_bounds(E.rand_bf16(G * P, C, scale=3.0 if act == 2 else 1.5, offset=1.0 if act == 2 else 0.0, seed=s))
     vec = E.bn_vectors(G, C, s + 1, act) if lazy else None
-    Gm, sv = run_gram(x, vec, act, P, C, G)
+    Gm, sv = run_gram(x, vec, act, P, C, G, rid)
     vf = vec.reshape(-1) if lazy else None
     a = F.operand(x, vf, vf[C:] if lazy else None, act if lazy else 0, G, 4 * C if lazy else 0)
     q = F.gram_check(Gm.check(rid).cpu().reshape(G, C, C), sv.check(rid + " s").cpu(), a, rid)
@@ -478,11 +494,10 @@ def test_gram_stats(Cin, Cout):
     G1 = a.double().t() @ a.double()
     Gm = torch.stack([G0, ((G1 + G1.t()) * 0.5).float()]).float()          # (exactly symmetric: the kernel reads G by columns)
     sv = torch.stack([torch.randn(Cin, generator=g) * 50, a.sum(0)]).float()
-    buf = torch.full((2 * 2 * Cout + 2 * BAND,), NAN, dtype=torch.float64, device=DEV)
-    out = buf[BAND:BAND + 4 * Cout]
-    wp, Gd, sd = pack(w4(w), Cin, 0), Gm.to(DEV), sv.to(DEV)
+    out = GB.out((4 * Cout,), torch.float64)
+    wp, Gd, sd = pack(w4(w), Cin, 0), GB.frozen(Gm), GB.frozen(sv)
     call("adamml_gram_stats", ptr(wp), ptr(Gd), ptr(sd), ptr(out), Cout, Cin, 2)
-    assert torch.isnan(buf[:BAND]).all() and torch.isnan(buf[BAND + 4 * Cout:]).all() and not torch.isnan(out).any()
+    GB.check(rid)
     ref, tol = F.gram_stats_ref(w, Gm, sv)
     q = F.ratio(out.cpu().reshape(2, 2 * Cout), ref, tol)
     assert q <= 1.0, "%s: max err/tol %.3g" % (rid, q)
@@ -513,14 +528,15 @@ def test_temporal_pool_bwd_code_prod(row):
     assert all((code == k).any() for k in range(4))
     a = E.plant_bounds(E.rand_bf16(G * P, Cin, scale=1.5, seed=s + 2))
     av = E.bn_vectors(G, Cin, s + 3) if lazy else None
-    avd = av.reshape(-1).to(DEV) if lazy else None
-    g2, prod = Guarded(G * P, C, torch.bfloat16), Guarded(G * C, Cin, torch.float32)
-    sa = stat_acc(G, C)
+    avd = GB.frozen(av.reshape(-1)) if lazy else None
+    gyd, cd, ad = GB.frozen(gy), GB.frozen(E.pack_codes(code)), GB.frozen(a)
+
+    def launch(outs, ws, nbytes):
+        call("adamml_temporal_pool_bwd_code_prod", ptr(gyd), ptr(cd), ptr(outs[0].t), ptr(outs[2]), ptr(ad), ptr(avd),
+             ptr(avd[Cin:]) if lazy else None, 4 * Cin if lazy else 0, 1 if lazy else 0, ptr(outs[1].t), ptr(ws), nbytes, clips, T, Q, C, Cin, G)
+
     need = lib().adamml_temporal_pool_bwd_code_prod_workspace(clips, T, Q, C, Cin, G)
-    ws = torch.full((need // 4 + 1,), NAN, device=DEV)
-    gyd, cd, ad = gy.to(DEV), E.pack_codes(code).to(DEV), a.to(DEV)
-    call("adamml_temporal_pool_bwd_code_prod", ptr(gyd), ptr(cd), ptr(g2.t), ptr(sa), ptr(ad), ptr(avd),
-         ptr(avd[Cin:]) if lazy else None, 4 * Cin if lazy else 0, 1 if lazy else 0, ptr(prod.t), ptr(ws), ws.numel() * 4, clips, T, Q, C, Cin, G)
+    (g2, prod, sa), _ = three(need, lambda: (Guarded(G * P, C, torch.bfloat16), Guarded(G * C, Cin, torch.float32), stat_acc(G, C)), launch, rid)
     avf = av.reshape(-1) if lazy else None
     ao = F.operand(a, avf, avf[Cin:] if lazy else None, 1 if lazy else 0, G, 4 * Cin if lazy else 0)
     g2r, pr, pa, n = F.tpool_bwd_code_prod_ref(gy.reshape(G * clips * To, Q, C), code.reshape(G * clips * To, Q, C), ao, T, G)
@@ -550,12 +566,12 @@ def test_weight_packs_follow_the_index_map():
         n = ref.numel()
         s = Guarded(n, 1, ref.dtype)
         b = Guarded(n, 1, ref.dtype)
-        wd = w.to(DEV)
+        wd = GB.frozen(w)
         call("adamml_pack_conv_weight", ptr(wd), ptr(s.t), cout, 1 if mode == 2 else cin, 1 if mode == 2 else cp, kh, kw, mode)
         ws.append(wd); singles.append(s); batched.append(b); refs.append(ref); specs.append((cout, cin, kh, kw, mode, cp))
     assert any(r.numel() % epb for r in refs)
     rows, blk = F.pack_table(specs, [(w.data_ptr(), b.t.data_ptr()) for w, b in zip(ws, batched)], epb)
-    table = torch.tensor(rows, dtype=torch.int64).to(DEV)
+    table = GB.frozen(torch.tensor(rows, dtype=torch.int64))
     call("adamml_pack_conv_weights_batched", ptr(table), len(rows), blk)
     for spec, s, b, ref in zip(PACK_SPECS, singles, batched, refs):
         hs, hb = s.check("pack %s" % (spec,)).cpu().reshape(ref.shape), b.check("batched pack %s" % (spec,)).cpu().reshape(ref.shape)
@@ -598,6 +614,7 @@ def test_conv_fwd_bn_add_next_propagates_nan():
     out, y = Guarded(G * P, Cout, torch.bfloat16), Guarded(G * P, Cn, torch.bfloat16)
     wnp = pack(w4(wn), Cout, 0)
     call("adamml_conv_fwd_bn_add_next", *a.head, ptr(out.t), None, ptr(wnp), ptr(y.t), None)
+    GB.unwritten_ok(y.t)                                                 # (NaN is what the row expects, in y_next too)
     finite_pattern_matches(out.check(row["id"], written=False).cpu().reshape(r["ref"].shape), r["ref"], row["id"] + " NaN")
     yr = r["ref"] @ wn.double().t()                      # (a NaN of the block output reaches every next-conv channel of its pixel)
     finite_pattern_matches(y.check(row["id"], written=False).cpu().reshape(yr.shape), yr, row["id"] + " NaN y_next")
@@ -615,7 +632,7 @@ def test_conv_bwd_data_res_propagates_nan(row, monkeypatch):
     op["m"][0, P // 3, 17] = 1.0
     op["res_out"][P // 3, 17] = 1.0
     op["bits"] = F.pack_bits(op["m"].bool())
-    dx, _, _ = run_res(row, op)
+    dx, _, _ = run_res(row, op, finite=False)
     ref = F.res_ref(F.gview(op["dz"].double(), G), op["w"], torch.ones_like(op["m"]), F.gview(op["dx_in"], G))[0]
     ref = torch.where(op["m"] > 0, ref, torch.zeros_like(ref))
     finite_pattern_matches(dx.check(row["id"], written=False).cpu().reshape(ref.shape), ref, row["id"] + " NaN")
@@ -637,14 +654,21 @@ def test_bottleneck_tail_chain_gram_stats_finalize_fused_conv():
     beta = (torch.randn(Cout, generator=F.gen(s + 9)) * 0.3).float()
     a = FwdArgs(row, op, 1, P, 1)
     need = lib().adamml_gram_colsum_workspace(P, Cin, G)
-    ws = torch.empty(need // 4 + 1, device=DEV)
-    Gm, sv = torch.empty(G, Cin, Cin, device=DEV), torch.empty(G, Cin, device=DEV)
-    call("adamml_gram_colsum", ptr(a.x), ptr(a.xv), ptr(a.xv[Cin:]), 4 * Cin, 1, ptr(Gm), ptr(sv), P, Cin, G, ptr(ws), ws.numel() * 4)
-    sums = torch.empty(G, 2 * Cout, dtype=torch.float64, device=DEV)
+    assert need > 0
+    ws = GB.workspace(need)
+    Gm, sv = GB.out((G, Cin, Cin), torch.float32), GB.out((G, Cin), torch.float32)
+    call("adamml_gram_colsum", ptr(a.x), ptr(a.xv), ptr(a.xv[Cin:]), 4 * Cin, 1, ptr(Gm), ptr(sv), P, Cin, G, ptr(ws), need)
+    GB.check(rid + " gram_colsum")
+    Gm, sv = GB.frozen(Gm), GB.frozen(sv)                                # (each kernel's output is the next one's read-only operand)
+    sums = GB.out((G, 2 * Cout), torch.float64)
     call("adamml_gram_stats", ptr(a.wp), ptr(Gm), ptr(sv), ptr(sums), Cout, Cin, G)
-    vec = torch.empty(G, 4, Cout, device=DEV)
-    gd, bd = gamma.to(DEV), beta.to(DEV)
+    GB.check(rid + " gram_stats")
+    sums = GB.frozen(sums)
+    vec = GB.out((G, 4, Cout), torch.float32)
+    gd, bd = GB.frozen(gamma), GB.frozen(beta)
     call("adamml_bn_finalize", ptr(sums), 1, G, float(P), ptr(gd), ptr(bd), None, None, 0.1, eps, ptr(vec), Cout)
+    GB.check(rid + " bn_finalize")
+    vec = GB.frozen(vec)
     out = Guarded(G * P, Cout, torch.bfloat16)
     head = list(a.head)
     head[5] = ptr(vec)

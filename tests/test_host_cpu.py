@@ -47,9 +47,6 @@ def test_library_exports_every_declared_symbol(built):
 # entry points no test module has to name, with the reason (everything else declared in the header must appear in a tests/test_*.py)
 ABI_TEST_EXEMPT = {
     "adamml_last_error_string": "query: hip.call reads it on every failing launch",
-    "adamml_conv_bwd_weight_workspace": "query: workspace size, reached through hip.wgrad_workspace in every weight-gradient row",
-    "adamml_conv_stem_bwd_weight_workspace": "query: workspace size, reached through hip.wgrad_workspace(stem=True)",
-    "adamml_dwconv_bwd_weight_workspace": "query: workspace size, reached through hip.wgrad_workspace(depthwise=True)",
     "adamml_plan_run": "plan plumbing: driven through adamml_amd/plan.py (tests/test_launch_plan_gpu.py)",
     "adamml_plan_events_create": "plan plumbing: driven through adamml_amd/plan.py",
     "adamml_plan_events_destroy": "plan plumbing: driven through adamml_amd/plan.py",
@@ -58,7 +55,7 @@ ABI_TEST_EXEMPT = {
 
 def test_every_declared_entry_point_is_named_by_a_test_module():
     """A kernel entry point the suite never calls by name is a gap: every function of include/adamml_hip.h is called in some tests/test_*.py,
-    or is in ABI_TEST_EXEMPT with its reason (size queries, the error string, plan plumbing); the exemption list holds nothing stale.
+    or is in ABI_TEST_EXEMPT with its reason (the error string, plan plumbing); the exemption list holds nothing stale.
     Dispatch probes are not exempt: a row asserts them (test_dispatch_probes_answer_as_documented for those no GPU row reads)."""
     import glob
     hdr = open(os.path.join(ROOT, "include", "adamml_hip.h")).read()
@@ -92,6 +89,61 @@ CONFORMANCE_EXEMPT = {
     "plan_events_destroy": "plan plumbing: driven through adamml_amd/plan.py",
     "plan_num_entry_points": "plan plumbing: the length of the thunk table (test_launch_plan_thunks_are_in_sync_with_the_c_abi)",
 }
+
+
+# the conformance modules whose rows take every device buffer from tests/guarded.py
+GUARDED_MODULES = CONFORMANCE_MODULES[:4]
+# (module, line) -> why this line may create a device tensor outside tests/guarded.py
+DEVICE_ALLOC_EXEMPT = {
+    ("test_conv_conformance_gpu.py", "model.to(DEV).train()"): "the whole-network NaN row: the model owns its parameters, no buffer is handed to a kernel by the row",
+    ("test_conv_conformance_gpu.py", "y = model(x.to(DEV))"): "the whole-network NaN row: the network input, consumed by the executor",
+    ("test_elementwise_conformance_gpu.py", "g = torch.Generator(device=DEV).manual_seed(seed)"): "large rows: the generator of operands made on the device (0.3 - 0.6 GB)",
+    ("test_elementwise_conformance_gpu.py", "t = (torch.randn(rows, C, generator=g, device=DEV) * scale + offset).to(torch.bfloat16)"):
+        "large rows: the operand is made on the device and handed to guarded.frozen on the next line",
+    ("test_elementwise_conformance_gpu.py",
+     "out, ab = torch.zeros(G, 2 * C, dtype=torch.float64, device=DEV), torch.zeros(G, 2 * C, dtype=torch.float64, device=DEV)"):
+        "large rows: accumulators of the float64 reference computed by torch on the device, no kernel of the library sees them",
+}
+DEVICE_ALLOC = re.compile(r"device\s*=\s*DEV|\.to\(DEV\)|\.cuda\(\)")
+
+
+def test_guarded_modules_create_no_device_tensor_of_their_own():
+    """In the four float64 conformance modules every buffer a kernel sees comes from tests/guarded.py (guard bands, frozen operands): no
+    `device=DEV`, `.to(DEV)` or `.cuda()` in the module text but the lines of DEVICE_ALLOC_EXEMPT, which holds nothing stale"""
+    assert len(GUARDED_MODULES) == 4 and all(m.endswith("_conformance_gpu.py") for m in GUARDED_MODULES)
+    seen = set()
+    for m in GUARDED_MODULES:
+        text = open(os.path.join(ROOT, "tests", m)).read()
+        assert re.search(r"^from tests\.guarded import |^from tests\.test_conv_conformance_gpu import .*\bGB\b", text, re.M), m + ": does not use tests/guarded.py"
+        for no, line in enumerate(text.splitlines(), 1):
+            if DEVICE_ALLOC.search(line):
+                key = (m, line.strip())
+                assert key in DEVICE_ALLOC_EXEMPT, "%s:%d creates a device tensor outside tests/guarded.py: %s" % (m, no, line.strip())
+                seen.add(key)
+    assert seen == set(DEVICE_ALLOC_EXEMPT), "stale exemptions: %s" % sorted(set(DEVICE_ALLOC_EXEMPT) - seen)
+    assert all(len(r) > 10 for r in DEVICE_ALLOC_EXEMPT.values())
+
+
+# workspace queries no guarded conformance module has to call, with the reason (keys without the adamml_ prefix, as CONFORMANCE_EXEMPT)
+WORKSPACE_QUERY_EXEMPT = {
+    "jpeg_decode_workspace": "the decoder clamps every workspace address by construction and tests/test_jpeg_gpu.py is byte-exact",
+}
+
+
+def test_every_workspace_query_is_called_by_a_guarded_conformance_module():
+    """A workspace-size query nobody checks against what the kernel touches is a gap: every adamml_*_workspace of the header is called by
+    name in one of the GUARDED_MODULES (whose rows allocate exactly the answer inside guard bands), or is in WORKSPACE_QUERY_EXEMPT"""
+    hdr = open(os.path.join(ROOT, "include", "adamml_hip.h")).read()
+    queries = set(re.findall(r"\b(adamml_[a-z0-9_]+_workspace)\s*\(", hdr))
+    assert len(queries) >= 9
+    text = "".join(open(os.path.join(ROOT, "tests", m)).read() for m in GUARDED_MODULES)
+    called = {q for q in queries if re.search(r"\.%s\(" % q, text)}
+    exempt = {"adamml_" + k for k in WORKSPACE_QUERY_EXEMPT}
+    assert exempt <= queries and not (exempt & called), sorted(exempt)
+    assert not (queries - called - exempt), "workspace queries no guarded conformance module calls: %s" % sorted(queries - called - exempt)
+    # and every call passes its answer on: no module sizes a workspace through the grow-only scratch of adamml_amd/hip.py
+    assert not re.search(r"hip\.(wgrad_workspace|scratch)\(", text)
+    assert all(len(r) > 10 for r in WORKSPACE_QUERY_EXEMPT.values())
 
 
 def test_every_computing_entry_point_is_named_by_a_float64_conformance_module():
