@@ -71,6 +71,9 @@ struct C3P {
     const bf16_t* bn_z;      // data gradient fused with the BatchNorm backward of the tensor it flows into, or null
     const float* bn_vec;     // [G][4][64]
     int bn_act, act;
+    const bf16_t* res_out;   // residual form (RES instance): block output of the add whose backward the epilogue finishes ..
+    const uint8_t* res_mask; // .. or its 1-bit act' != 0 mask; y then holds the identity-path gradient when `accumulate`
+    int res_act, accumulate;
     int N, H, W, R, tiles_per_img, tiles_per_group, total_tiles, tpb;
     int PW, PR, npt;         // patch width / rows (pixels); pixel tiles per tile
     int in_gstride;
@@ -140,7 +143,10 @@ __device__ __forceinline__ void fold16_to_cs(const f32x8& esum, const f32x8& esq
 // 16-byte units cannot be conflict-free for the gfx950 ds_read_b128 service groups (rows {0-3, 12-15} at chunk c with rows {4-11} at
 // chunk c + 1: for ANY pixel order one of the two complementary groups collides -- the groups cover all 16 residues and one half is
 // shifted by one).  160 (10 units) is conflict-free for every pixel offset; it costs one output row per strip (7 instead of 8 at W = 56).
-template <bool BNZ, int PP>
+// RES: the residual form of the data gradient (adamml_conv_bwd_data_res: conv1 of a BasicBlock without a downsample branch at 64 channels).
+// Same main loop; the epilogue adds the identity-path gradient already in y (p.accumulate), SELECTS by act'(block output) -- p.res_out or the
+// 1-bit p.res_mask -- and accumulates sum(g') and, with p.bn_z, sum(g' * zhat) of the add's BatchNorm operand.  Its own instantiation, as BNZ.
+template <bool BNZ, int PP, bool RES = false>
 __global__ __launch_bounds__(NT3, 1) void conv3x3_c64_kernel(C3P p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* s_w = smem;                                              // [64][WROW3]
@@ -268,9 +274,11 @@ __global__ __launch_bounds__(NT3, 1) void conv3x3_c64_kernel(C3P p) {
         // one 8-wave workgroup per CU, every register and all of the LDS taken.  One dword per line requested HERE, ahead of the ~14 us
         // of MFMA work, pulls the strip into L2: the epilogue's two batches of row loads then cost an L2 round trip instead of an HBM one.
         unsigned ztouch = 0;
-        if constexpr (BNZ) {
+        if constexpr (BNZ || RES) {
             const size_t zb = (size_t)g * p.gxy + ((size_t)n * p.H + oh0) * p.W * C64;
-            ztouch = *reinterpret_cast<const unsigned*>(p.bn_z + zb + (size_t)min(tid, npx - 1) * C64);
+            // (RES: the identity-path gradient when there is one -- the rows every form of the epilogue reads and writes)
+            const bf16_t* tp = !RES ? p.bn_z : p.accumulate ? p.y : p.bn_z ? p.bn_z : p.res_out;
+            ztouch = *reinterpret_cast<const unsigned*>(tp + zb + (size_t)min(tid, npx - 1) * C64);
         }
 
         // ---- MFMA: wave w owns pixel tiles w, w+8, w+16, w+24 (16 consecutive output pixels, row-major over the strip) ---
@@ -315,7 +323,7 @@ __global__ __launch_bounds__(NT3, 1) void conv3x3_c64_kernel(C3P p) {
         };
         if (__builtin_amdgcn_readfirstlane(last_live ? 1 : 0)) mfma_loop(std::integral_constant<int, 4>{});
         else mfma_loop(std::integral_constant<int, 3>{});
-        if constexpr (BNZ) asm volatile("" ::"v"(ztouch));   // (keeps the touch load's destination allocated until it has landed)
+        if constexpr (BNZ || RES) asm volatile("" ::"v"(ztouch));   // (keeps the touch load's destination allocated until it has landed)
         C64_TS(4);
         __syncthreads();                                     // patch consumed: its LDS becomes the staging tile
         C64_TS(5);
@@ -338,7 +346,75 @@ __global__ __launch_bounds__(NT3, 1) void conv3x3_c64_kernel(C3P p) {
         __syncthreads();
         C64_TS(7);
         const size_t obase = (size_t)g * p.gxy + ((size_t)n * p.H + oh0) * p.W * C64;
-        if constexpr (!BNZ) {
+        if constexpr (RES) {
+            // g' = (W^T dz [+ identity-path gradient in y]) selected by act'(block output): written once; sum(g') and sum(g' * zhat_a) from the
+            // STORED values (conv_gemm.hip RES epilogue semantics: a closed mask gives +0 whatever the gradient holds).  All loads of a batch of
+            // 4 rows (z, identity-path gradient, block output or mask byte) are requested before the batch's first store, as below.
+            f32x8 mu, is;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) mu[i] = is[i] = 0.f;
+            if (p.bn_z) {
+                const float* vec = p.bn_vec + (size_t)g * 4 * C64;
+                mu = load_f32x8(vec + 2 * C64 + ech * 8);
+                is = load_f32x8(vec + 3 * C64 + ech * 8);
+            }
+            const float rlo = act_lo(p.res_act), rhi = act_hi(p.res_act);
+            const uint8_t* mb = p.res_mask ? p.res_mask + (obase >> 3) : nullptr;       // (obase is a multiple of 64 elements)
+            f32x8 esum, esq;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) esum[i] = esq[i] = 0.f;
+            constexpr int MAXE = MAXPX3 * 8 / NT3, EBR = 4;
+#pragma unroll 1
+            for (int b0 = 0; b0 < MAXE; b0 += EBR) {
+                if ((b0 * NT3) >= npx * 8) break;                  // (uniform)
+                bf16x8 zr[EBR], dr[EBR], orr[EBR];
+                unsigned mbits[EBR];
+#pragma unroll
+                for (int k = 0; k < EBR; ++k) {
+                    const int q = min((tid + (b0 + k) * NT3) >> 3, npx - 1);          // clamped: rows past the strip re-read its last row, never stored
+                    const size_t off = obase + (size_t)q * C64 + ech * 8;
+                    zr[k] = dr[k] = orr[k] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+                    mbits[k] = 0;
+                    if (p.bn_z) zr[k] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(p.bn_z + off));
+                    if (p.accumulate) dr[k] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(p.y + off));
+                    if (mb) mbits[k] = mb[q * 8 + ech];
+                    else orr[k] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(p.res_out + off));
+                }
+#pragma unroll
+                for (int k = 0; k < EBR; ++k) {
+                    const int e = tid + (b0 + k) * NT3;
+                    if (e < npx * 8) {
+                        const int q = e >> 3;
+                        const s16x4 lo = *reinterpret_cast<const s16x4*>(s_patch + q * SROW3 + ech * 16);
+                        const s16x4 hi = *reinterpret_cast<const s16x4*>(s_patch + q * SROW3 + ech * 16 + 8);
+                        union { struct { s16x4 a, b; } s; bf16x8 v; } u;
+                        u.s.a = lo; u.s.b = hi;
+                        f32x8 f = bf8_to_f32(u.v);
+                        if (p.accumulate) f += bf8_to_f32(dr[k]);
+                        if (mb) {
+#pragma unroll
+                            for (int i = 0; i < 8; ++i) f[i] = (mbits[k] >> i) & 1u ? f[i] : 0.f;
+                        } else {
+                            const f32x8 ov = bf8_to_f32(orr[k]);
+#pragma unroll
+                            for (int i = 0; i < 8; ++i) f[i] = (ov[i] > rlo && ov[i] < rhi) ? f[i] : 0.f;
+                        }
+                        union { bf16x8 v; unsigned w[4]; } o;
+                        o.v = f32_to_bf8(f);
+                        *reinterpret_cast<bf16x8*>(p.y + obase + (size_t)q * C64 + ech * 8) = o.v;
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) { f[2 * i] = __uint_as_float(o.w[i] << 16); f[2 * i + 1] = __uint_as_float(o.w[i] & 0xffff0000u); }
+                        esum += f;
+                        if (p.bn_z) {
+                            const f32x8 zv = bf8_to_f32(zr[k]);
+#pragma unroll
+                            for (int i = 0; i < 8; ++i) esq[i] += f[i] * (zv[i] - mu[i]) * is[i];
+                        }
+                    }
+                }
+            }
+            if (p.stats) fold16_to_cs(esum, esq, csw, lane, ech);
+        } else if constexpr (!BNZ) {
             for (int e = tid; e < npx * 8; e += NT3) {
                 const int q = e >> 3;
                 const s16x4 lo = *reinterpret_cast<const s16x4*>(s_patch + q * SROW3 + ech * 16);
@@ -670,12 +746,8 @@ bool adamml_conv3x3_c64_supported(const adamml_conv_desc_t* d) {
     return c3_rows(d, PITCH3) >= 2;
 }
 
-int adamml_conv3x3_c64_launch(const adamml_conv_desc_t* d, const void* x, const void* w_packed, const float* in_scale,
-                              const float* in_shift, void* y, double* stats, const void* bn_z, const float* bn_vec, int bn_act,
-                              hipStream_t stream) {
-    C3P p;
-    p.x = (const bf16_t*)x; p.w = (const bf16_t*)w_packed; p.in_scale = in_scale; p.in_shift = in_shift; p.y = (bf16_t*)y;
-    p.stats = stats; p.bn_z = (const bf16_t*)bn_z; p.bn_vec = bn_vec; p.bn_act = bn_act; p.act = d->act;
+// geometry of d into p (pointers and epilogue fields already set) and the launch; res: the residual instance
+static int c3_launch(const adamml_conv_desc_t* d, C3P& p, bool res, hipStream_t stream) {
     p.N = d->N; p.H = d->H; p.W = d->W;
     const int R = c3_rows(d, PITCH3);
     p.R = R; p.PR = R + 2; p.PW = d->W + 2;
@@ -695,13 +767,44 @@ int adamml_conv3x3_c64_launch(const adamml_conv_desc_t* d, const void* x, const 
     if (!attr_once.test(attr_dev)) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_c64_kernel<false, PITCH3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_c64_kernel<true, PITCH3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_c64_kernel<false, PITCH3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return adamml_set_error(ADAMML_ELAUNCH, "conv3x3_c64: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
         attr_once.set(attr_dev);
     }
     const dim3 grid(ceil_div(p.total_tiles, p.tpb));
-    if (p.bn_z) hipLaunchKernelGGL((conv3x3_c64_kernel<true, PITCH3>), grid, dim3(NT3), C64_LDS(lds), stream, p);
+    if (res) hipLaunchKernelGGL((conv3x3_c64_kernel<false, PITCH3, true>), grid, dim3(NT3), C64_LDS(lds), stream, p);
+    else if (p.bn_z) hipLaunchKernelGGL((conv3x3_c64_kernel<true, PITCH3>), grid, dim3(NT3), C64_LDS(lds), stream, p);
     else hipLaunchKernelGGL((conv3x3_c64_kernel<false, PITCH3>), grid, dim3(NT3), C64_LDS(lds), stream, p);
     return adamml_check_launch("conv3x3_c64");
+}
+
+int adamml_conv3x3_c64_launch(const adamml_conv_desc_t* d, const void* x, const void* w_packed, const float* in_scale,
+                              const float* in_shift, void* y, double* stats, const void* bn_z, const float* bn_vec, int bn_act,
+                              hipStream_t stream) {
+    C3P p;
+    p.x = (const bf16_t*)x; p.w = (const bf16_t*)w_packed; p.in_scale = in_scale; p.in_shift = in_shift; p.y = (bf16_t*)y;
+    p.stats = stats; p.bn_z = (const bf16_t*)bn_z; p.bn_vec = bn_vec; p.bn_act = bn_act; p.act = d->act;
+    p.res_out = nullptr; p.res_mask = nullptr; p.res_act = 0; p.accumulate = 0;
+    return c3_launch(d, p, false, stream);
+}
+
+// d: the stride-1 descriptor of the data gradient as adamml_conv_bwd_data_res forms it (d->accumulate says whether dx holds the
+// identity-path gradient: the epilogue reads it, the main loop never does, so the strips and the LDS budget are those of the plain form)
+bool adamml_conv3x3_c64_res_supported(const adamml_conv_desc_t* d) {
+    adamml_conv_desc_t f = *d;
+    f.accumulate = 0;
+    return adamml_conv3x3_c64_supported(&f);
+}
+
+int adamml_conv3x3_c64_res_launch(const adamml_conv_desc_t* d, const void* dz, const void* w_dgrad_packed, void* dx, const void* res_out,
+                                  const uint8_t* res_mask, int res_act, const void* z_a, const float* vec_a, double* sums_a, hipStream_t stream) {
+    C3P p;
+    p.x = (const bf16_t*)dz; p.w = (const bf16_t*)w_dgrad_packed; p.in_scale = nullptr; p.in_shift = nullptr; p.y = (bf16_t*)dx;
+    p.stats = sums_a; p.bn_z = (const bf16_t*)z_a; p.bn_vec = vec_a; p.bn_act = ACT_NONE; p.act = ACT_NONE;
+    p.res_out = (const bf16_t*)res_out; p.res_mask = res_mask; p.res_act = res_act; p.accumulate = d->accumulate;
+    adamml_conv_desc_t f = *d;
+    f.accumulate = 0;
+    return c3_launch(&f, p, true, stream);
 }
 
 static int c3_geometry(const adamml_conv_desc_t* d, int* R_out) {

@@ -107,7 +107,7 @@ __device__ __forceinline__ int lds_off(int row, int chunk) {
 // PD = register prefetch depth (K steps of global loads in flight).  PD 1 keeps 3-4 workgroups per CU (latency hidden by
 // occupancy: best for the big, short-K layers); PD 3 is for small grids with long K loops (layer3/4), where a CU holds a
 // single workgroup and only explicit look-ahead hides the HBM round trip.
-// RES: residual form of the BatchNorm-fused data-gradient epilogue (MODE 0 only).  Its epilogue keeps four 16-byte streams
+// RES: residual form of the BatchNorm-fused data-gradient epilogue (MODE 0, and MODE 1 for dense 3x3 / stride-1 data gradients).  Its epilogue keeps four 16-byte streams
 // per row in flight and two sets of per-channel vectors, so it is compiled for 2 workgroups per CU (256 VGPRs) as its own
 // instantiation -- inside the shared kernel it pushed every MODE 0 instance into scratch spills.
 // DUAL: the BatchNorm-backward affine of two source tensors is applied by the MODE 0 loader (own instantiation as well:
@@ -1142,6 +1142,10 @@ template <int BC, int EID>                              // RES: residual form of
 static void launch_res(const ConvGrid& g, const ConvP& p) {
     hipLaunchKernelGGL((conv_gemm_kernel<BC, 0, 1, true, false, false, false, true, EID>), g.grid, dim3(NTHREADS), 0, g.stream, p);
 }
+template <int BC>                                       // RES behind the KxK (MODE 1) LDS-DMA loaders: 3x3 / stride-1 data gradients
+static void launch_res_kxk(const ConvGrid& g, const ConvP& p) {
+    hipLaunchKernelGGL((conv_gemm_kernel<BC, 1, 1, true, false, false, false, true, 0>), g.grid, dim3(NTHREADS), 0, g.stream, p);
+}
 static void launch_res_prod(const ConvGrid& g, const ConvP& p) {      // RES + EID with the product of the gradient tile (PF)
     hipLaunchKernelGGL((conv_gemm_kernel<128, 0, 1, true, false, false, false, true, 1, false, -1, true>), g.grid, dim3(NTHREADS), 0, g.stream, p);
 }
@@ -1181,7 +1185,7 @@ static int conv_launch(const adamml_conv_desc_t* d, const void* x, const void* w
                        const CatIn* cat = nullptr, const FaddEpi* fadd = nullptr, const PfIn* pf = nullptr) {
     if (!d || !x || !w_packed || !y) return adamml_set_error(ADAMML_EINVAL, "conv_fwd: null argument");
     if (d->Cin % 8 || d->Cout % 8) return adamml_set_error(ADAMML_EINVAL, "conv_fwd: channels must be multiples of 8 (Cin=%d Cout=%d)", d->Cin, d->Cout);
-    if (!cls && !fadd && adamml_conv3x3_c64_supported(d))
+    if (!cls && !fadd && !res && adamml_conv3x3_c64_supported(d))       // (the residual form of the 64-channel kernel: adamml_conv_bwd_data_res)
         return adamml_conv3x3_c64_launch(d, x, w_packed, in_scale, in_shift, y, stats, bn_z, bn_vec, bn_act, stream);
     // narrow 1x1 convs of the MobileNetV2s (plain forward / plain data gradient): the barrier-free streaming kernel (conv1x1_narrow.hip)
     if (!cls && !fadd && !res && !dual && !cat && !pf && !bn_z && adamml_conv1x1_narrow_fwd_supported(d))
@@ -1300,7 +1304,9 @@ static int conv_launch(const adamml_conv_desc_t* d, const void* x, const void* w
         return adamml_check_launch("conv_fwd_bn_add");
     }
     if (res) {
-        if (mode != 0) return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_data_res: only 1x1 / stride-1 convs");
+        // MODE 1 (3x3 / pad 1 / stride 1, dense dz): the epilogue only needs tile row r to be output pixel p0 + r, as in MODE 0
+        if (mode != 0 && !(mode == 1 && !pf && p.up == 1 && p.stride == 1))
+            return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_data_res: only 1x1 / stride-1 and 3x3 / pad-1 / stride-1 convs");
         if (pf) {
             if (BC != 128 || d->Cout % 128 || pf->C != 64 || in_scale || !p.res_mask || !p.accumulate || p.bn_z || p.bn_z2 || !stats)
                 return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_data_res_prod: needs Cout %% 128 == 0, a 64-channel product operand, "
@@ -1318,6 +1324,10 @@ static int conv_launch(const adamml_conv_desc_t* d, const void* x, const void* w
             return adamml_check_launch("conv_bwd_data_res_prod (reduce)");
         }
         if (in_scale) return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_data_res: the gradient operand is never lazy");
+        if (mode == 1) {
+            with_bc(BC, [&](auto bc) { launch_res_kxk<bc()>(cg, p); });
+            return adamml_check_launch("conv_bwd_data_res (3x3)");
+        }
         // the algebraic backward's form (identity gradient + 1-bit mask, sum(g') only): identity-side loads at the start of each tile (EID)
         const bool eid = p.res_mask && p.accumulate && !p.bn_z && !p.bn_z2;
         with_bc(BC, [&](auto bc) { if (eid) launch_res<bc(), 1>(cg, p); else launch_res<bc(), 0>(cg, p); });
@@ -1549,12 +1559,31 @@ extern "C" int adamml_conv_bwd_data_alg(const adamml_conv_desc_t* d, const void*
     return conv_launch(&gd, g, w_alg, a_scale, a_shift, dx, sums, z_in, bn_vec, act, stream, nullptr, nullptr, nullptr, &c);
 }
 
+static bool res_1x1(const adamml_conv_desc_t* d) {
+    return d && d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && d->Cin % 8 == 0 && d->Cout % 8 == 0;
+}
+
+// 3x3 / pad 1 / stride 1 with as many output as input channels (conv1 of a BasicBlock without a downsample branch): the tile kernel's
+// KxK loaders need a power-of-two channel count
+static bool res_3x3(const adamml_conv_desc_t* d) {
+    return d && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1 && d->up <= 1 && d->Cin == d->Cout && d->Cin >= 64 &&
+           ilog2_exact(d->Cin) >= 0 && d->OH == d->H && d->OW == d->W;
+}
+
 extern "C" int adamml_conv_bwd_data_res_supported(const adamml_conv_desc_t* d) {
-    return d && d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && d->Cin % 8 == 0 && d->Cout % 8 == 0 ? 1 : 0;
+    return res_1x1(d) || res_3x3(d) ? 1 : 0;
+}
+
+// 64 channels (layer 1 of the BasicBlock nets): the resident-weight kernel of conv3x3_c64.hip, which has no second BatchNorm operand
+static bool res_3x3_c64(const adamml_conv_desc_t* d) {
+    if (!res_3x3(d)) return false;
+    const adamml_conv_desc_t g = dgrad_desc(d, 0, true);
+    return adamml_conv3x3_c64_res_supported(&g);
 }
 
 extern "C" int adamml_conv_bwd_data_res_streams(const adamml_conv_desc_t* d) {
-    return d && adamml_conv_bwd_data_res_supported(d) && adamml_res_stream_supported(d) ? 1 : 0;
+    if (res_3x3_c64(d)) return 2;
+    return res_1x1(d) && adamml_res_stream_supported(d) ? 1 : 0;
 }
 
 extern "C" int adamml_conv_bwd_data_res(const adamml_conv_desc_t* d, const void* dz, const void* w_dgrad_packed, void* dx,
@@ -1564,10 +1593,13 @@ extern "C" int adamml_conv_bwd_data_res(const adamml_conv_desc_t* d, const void*
     if (!d || !res_out || !sums_a || (z_a && !vec_a)) return adamml_set_error(ADAMML_EINVAL, "conv_bwd_data_res: null argument");
     if ((z_b != nullptr) != (vec_b != nullptr) || (z_b != nullptr) != (sums_b != nullptr))
         return adamml_set_error(ADAMML_EINVAL, "conv_bwd_data_res: incomplete second BatchNorm operand");
-    if (!adamml_conv_bwd_data_res_supported(d)) return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_data_res: only 1x1 / stride-1 convs");
-    if (accumulate && res_mask && !z_a && adamml_res_stream_supported(d))       // (the algebraic backward's form at the layer-2 shape)
+    if (!adamml_conv_bwd_data_res_supported(d))
+        return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_data_res: only 1x1 / stride-1 convs and 3x3 / pad-1 / stride-1 convs with Cin == Cout (a power of two >= 64)");
+    if (accumulate && res_mask && !z_a && res_1x1(d) && adamml_res_stream_supported(d))       // (the algebraic backward's form at the layer-2 shape)
         return adamml_res_stream_launch(d, dz, w_dgrad_packed, dx, res_mask, sums_a, z_b, vec_b, sums_b, stream);
-    const adamml_conv_desc_t g = dgrad_desc(d, accumulate);
+    const adamml_conv_desc_t g = dgrad_desc(d, accumulate, d->KH > 1);       // (3x3: pad KH - 1 - pad for the flipped taps, as adamml_conv_bwd_data)
+    if (!z_b && res_3x3_c64(d))
+        return adamml_conv3x3_c64_res_launch(&g, dz, w_dgrad_packed, dx, res_out, res_mask, res_act, z_a, vec_a, sums_a, stream);
     ResEpi r{res_out, res_mask, res_act, z_b, vec_b, sums_b};
     return conv_launch(&g, dz, w_dgrad_packed, nullptr, nullptr, dx, sums_a, z_a, vec_a, ACT_NONE, stream, nullptr, &r);
 }
@@ -1584,13 +1616,13 @@ extern "C" size_t adamml_conv_bwd_data_res_prod_workspace(const adamml_conv_desc
 }
 
 extern "C" int adamml_conv_bwd_data_res_prod_supported(const adamml_conv_desc_t* d, int a_channels) {
-    if (d && adamml_conv_bwd_data_res_supported(d) && adamml_res_prod_stream_supported(d, a_channels)) return 1;
-    return d && adamml_conv_bwd_data_res_supported(d) && d->Cin % 128 == 0 && a_channels == 64 &&
+    if (res_1x1(d) && adamml_res_prod_stream_supported(d, a_channels)) return 1;
+    return res_1x1(d) && d->Cin % 128 == 0 && a_channels == 64 &&
            (long)ceil_div(d->N * d->OH * d->OW, BP) * (d->Cin / 128) * (d->groups < 1 ? 1 : d->groups) >= 4096 ? 1 : 0;
 }
 
 extern "C" int adamml_conv_bwd_data_res_prod_streams(const adamml_conv_desc_t* d, int a_channels) {
-    return d && adamml_conv_bwd_data_res_supported(d) && adamml_res_prod_stream_supported(d, a_channels) ? 1 : 0;
+    return res_1x1(d) && adamml_res_prod_stream_supported(d, a_channels) ? 1 : 0;
 }
 
 extern "C" int adamml_conv_bwd_data_res_prod(const adamml_conv_desc_t* d, const void* dz, const void* w_dgrad_packed, void* dx,

@@ -23,6 +23,11 @@ bool adamml_conv3x3_c64_supported(const adamml_conv_desc_t* d);
 int adamml_conv3x3_c64_launch(const adamml_conv_desc_t* d, const void* x, const void* w_packed, const float* in_scale,
                               const float* in_shift, void* y, double* stats, const void* bn_z, const float* bn_vec, int bn_act,
                               hipStream_t stream);
+// the residual form of the data gradient (adamml_conv_bwd_data_res without a second BatchNorm operand); d->accumulate: dx holds the
+// identity-path gradient
+bool adamml_conv3x3_c64_res_supported(const adamml_conv_desc_t* d);
+int adamml_conv3x3_c64_res_launch(const adamml_conv_desc_t* d, const void* dz, const void* w_dgrad_packed, void* dx, const void* res_out,
+                                  const uint8_t* res_mask, int res_act, const void* z_a, const float* vec_a, double* sums_a, hipStream_t stream);
 bool adamml_conv3x3_c64_wgrad_supported(const adamml_conv_desc_t* d, int cin_true);
 int adamml_conv3x3_c64_wgrad_blocks(const adamml_conv_desc_t* d, int* tpb_out);
 int adamml_conv3x3_c64_wgrad_launch(const adamml_conv_desc_t* d, const void* dz, const void* x, const float* in_scale,

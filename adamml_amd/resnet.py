@@ -1,4 +1,4 @@
-"""TSN-style 2-D ResNet-50/101/152 over N*T frames with temporal pooling between stages, executed by
+"""TSN-style 2-D ResNet-18/34/50/101/152 over N*T frames with temporal pooling between stages, executed by
 libadamml_hip (bf16 MFMA implicit-GEMM convs with fused BatchNorm statistics).
 
 Mirrors the interface and state_dict of models/resnet.py:116-259 (class ResNet, factory resnet()).
@@ -14,7 +14,21 @@ from .runtime import (Lazy, conv_bn, conv_bn_add, conv_bn_add_supported, conv_bn
 
 __all__ = ['ResNet', 'resnet']
 
-_BLOCKS = {50: [3, 4, 6, 3], 101: [3, 4, 23, 3], 152: [3, 8, 36, 3]}
+_BLOCKS = {18: [2, 2, 2, 2], 34: [3, 4, 6, 3], 50: [3, 4, 6, 3], 101: [3, 4, 23, 3], 152: [3, 8, 36, 3]}     # models/resnet.py:124-129
+
+
+class _BasicBlock(nn.Module):
+    """Parameter container with the names of models/resnet.py:46-57."""
+    expansion = 1
+
+    def __init__(self, inplanes, planes, stride, downsample):
+        super().__init__()
+        self.conv1 = nn.Conv2d(inplanes, planes, 3, stride, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(planes)
+        self.conv2 = nn.Conv2d(planes, planes, 3, 1, 1, bias=False)
+        self.bn2 = nn.BatchNorm2d(planes)
+        self.downsample = downsample
+        self.stride = stride
 
 
 class _Bottleneck(nn.Module):
@@ -40,9 +54,10 @@ class ResNet(HipBackbone, MeanStdMixin, StockDDPAware):
         super().__init__()
         self._install_ddp_probe()
         if depth not in _BLOCKS:
-            raise ValueError("adamml_amd.ResNet: the HIP path implements the Bottleneck depths 50/101/152 "
-                             "(the AdaMML hot path uses 50); got depth=%r" % (depth,))
+            raise ValueError("adamml_amd.ResNet: depth is one of 18/34 (BasicBlock) and 50/101/152 (Bottleneck), as in the "
+                             "reference (the AdaMML hot path uses 50); got depth=%r" % (depth,))
         layers = _BLOCKS[depth]
+        block = self.block = _BasicBlock if depth < 50 else _Bottleneck       # models/resnet.py:123
         self.pooling_method = pooling_method.lower()
         self.depth = depth
         self.num_frames = num_frames
@@ -54,31 +69,31 @@ class ResNet(HipBackbone, MeanStdMixin, StockDDPAware):
         self.inplanes = 64
         self.conv1 = nn.Conv2d(input_channels, 64, kernel_size=7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
-        self.layer1 = self._make_layer(64, layers[0])
-        self.layer2 = self._make_layer(128, layers[1], stride=2)
-        self.layer3 = self._make_layer(256, layers[2], stride=2)
-        self.layer4 = self._make_layer(512, layers[3], stride=2)
+        self.layer1 = self._make_layer(block, 64, layers[0])
+        self.layer2 = self._make_layer(block, 128, layers[1], stride=2)
+        self.layer3 = self._make_layer(block, 256, layers[2], stride=2)
+        self.layer4 = self._make_layer(block, 512, layers[3], stride=2)
         self.dropout_p = dropout
-        self.fc = nn.Linear(2048, num_classes)
+        self.fc = nn.Linear(512 * block.expansion, num_classes)
 
         self._stem = self._register_conv(self.conv1)
         for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
             for b in layer:
                 b._cs1 = self._register_conv(b.conv1)
                 b._cs2 = self._register_conv(b.conv2)
-                b._cs3 = self._register_conv(b.conv3)
+                b._cs3 = self._register_conv(b.conv3) if block is _Bottleneck else None
                 b._csd = self._register_conv(b.downsample[0]) if b.downsample is not None else None
         self.flat_owner = FlatBuffers(self)
 
-    def _make_layer(self, planes, blocks, stride=1):
+    def _make_layer(self, block, planes, blocks, stride=1):
         downsample = None
-        if stride != 1 or self.inplanes != planes * 4:
-            downsample = nn.Sequential(nn.Conv2d(self.inplanes, planes * 4, 1, stride, bias=False),
-                                       nn.BatchNorm2d(planes * 4))
-        layers = [_Bottleneck(self.inplanes, planes, stride, downsample)]
-        self.inplanes = planes * 4
+        if stride != 1 or self.inplanes != planes * block.expansion:
+            downsample = nn.Sequential(nn.Conv2d(self.inplanes, planes * block.expansion, 1, stride, bias=False),
+                                       nn.BatchNorm2d(planes * block.expansion))
+        layers = [block(self.inplanes, planes, stride, downsample)]
+        self.inplanes = planes * block.expansion
         for _ in range(1, blocks):
-            layers.append(_Bottleneck(self.inplanes, planes, 1, None))
+            layers.append(block(self.inplanes, planes, 1, None))
         return nn.Sequential(*layers)
 
     # ------------------------------------------------------------------------------------------
@@ -105,6 +120,18 @@ class ResNet(HipBackbone, MeanStdMixin, StockDDPAware):
                 # the downsample branch is issued FIRST so that its data gradient runs LAST in the reversed tape: it then
                 # accumulates into the gradient conv1 already wrote, and a stride-2 1x1 only touches a quarter of the pixels
                 idn = conv_bn(rt, h, b._csd, b.downsample[1], ACT_NONE) if b._csd is not None else h
+                if self.block is _BasicBlock:
+                    # models/resnet.py:59-74.  Consumers of h: [downsample], conv1 and -- without a downsample -- the add's identity operand.
+                    # The add is recorded last, so it is reversed first and has put its gradient into h.grad before conv1's data gradient
+                    # runs: conv1 is then the last consumer of h (it accumulates, and where h is the previous block's add output its epilogue
+                    # may finish that add's backward).  With a downsample the add's identity operand is the downsample output, conv1's data
+                    # gradient is the first into h.grad and the downsample's accumulates after it: no promise for conv1.
+                    o = conv_bn(rt, h, b._cs1, b.bn1, ACT_RELU, last_consumer=b._csd is None)
+                    # conv1's output feeds conv2 alone; conv2's output (linear BatchNorm) feeds the add alone, and so does the downsample's
+                    o = conv_bn(rt, o, b._cs2, b.bn2, ACT_NONE, sole_consumer=True)
+                    h = add_act(rt, o, idn, ACT_RELU, idn_sole=b._csd is not None)
+                    pooled = False
+                    continue
                 # without a downsample branch conv1 is the last consumer of h in the reversed tape (the identity path of
                 # the add is reversed first): its data-gradient epilogue finishes the previous block's residual backward
                 o = conv_bn(rt, h, b._cs1, b.bn1, ACT_RELU, last_consumer=b._csd is None)

@@ -48,8 +48,8 @@ INERT_FLAGS = ("frames_per_group", "workers", "threed_data", "disable_scaleup", 
 
 def arg_parser():
     """Every flag of the reference's parser (opts.py:5-149), same spelling, type and default -- except `--backbone_net` (the
-    reference's default 's3d' is not among its own choices, opts.py:9-10: 'adamml' here), `-d` (18 there; the HIP path implements
-    the Bottleneck depths, 50 here) and `--dataset` (the reference's default 'activitynet' is absent from its own table:
+    reference's default 's3d' is not among its own choices, opts.py:9-10: 'adamml' here), `-d` (18 there; 50 here, the depth of
+    the AdaMML recipes -- 18 / 34 / 101 / 152 run as well) and `--dataset` (the reference's default 'activitynet' is absent from its own table:
     'kinetics-sounds' here).  Three flags are additions: --synthetic, --loader_factory, --num_classes."""
     p = argparse.ArgumentParser(description="AdaMML training on MI355X (restated reference launcher)")
     # model definition (opts.py:8-35)

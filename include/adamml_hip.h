@@ -190,8 +190,13 @@ ADAMML_API int adamml_conv_bwd_data_alg(const adamml_conv_desc_t* d, const void*
                              const void* w_alg, const float* epi_add, void* dx, int accumulate, const void* z_in, const float* bn_vec,
                              int act, double* sums, hipStream_t stream);
 
-/* Data gradient of a 1x1 / stride-1 conv whose INPUT is the output of a residual add  out = act(bn_a(z_a) + idn)
- * (models/resnet.py:110-111; sound_mobilenet_v2.py:67), finishing that add's backward in the epilogue:
+/* Data gradient of a conv whose INPUT is the output of a residual add  out = act(bn_a(z_a) + idn)
+ * (models/resnet.py:110-111 / :71-72; sound_mobilenet_v2.py:67), finishing that add's backward in the epilogue.  Shapes
+ * (adamml_conv_bwd_data_res_supported): 1x1 / stride 1 / pad 0 (conv1 of a Bottleneck, the MobileNetV2 expansions), and 3x3 / stride 1 /
+ * pad 1 with Cin == Cout a power of two >= 64 (conv1 of a BasicBlock without a downsample branch: 64 @ 56^2, 128 @ 28^2, 256 @ 14^2, 512 @
+ * 7^2 in ResNet-18 / -34), which the tile kernel serves behind its KxK loaders (csrc/conv_gemm.hip) -- except 64 channels with W >= 8 and
+ * no second BatchNorm operand (z_b == NULL: the only form a BasicBlock net launches), which the resident-weight kernel of
+ * csrc/conv3x3_c64.hip serves with the same epilogue (adamml_conv_bwd_data_res_streams == 2).  Stride-2 convs are not supported.
  *   g' = (W^T dz [+ dx, when accumulate: the identity-path gradient already stored there]) * act'(res_out)
  * is written to dx, and sum(g'), sum(g' * zhat_a) go to sums_a ([groups][SLOTS][2*Cin], caller zeroes); when the add's
  * other operand is BatchNorm'd too (downsample branch) z_b / vec_b / sums_b receive the same for it (else all NULL).
@@ -201,11 +206,18 @@ ADAMML_API int adamml_conv_bwd_data_alg(const adamml_conv_desc_t* d, const void*
  * holds (a NaN or inf under a closed mask does not propagate, as in autograd's threshold backward).  The unfused
  * adamml_residual_bwd and the BatchNorm-fused data-gradient epilogues multiply by act' instead: equal in value for finite gradients
  * (the zero carries the gradient's sign there), NaN where a non-finite gradient meets a closed mask.
- * Replaces adamml_conv_bwd_data(accumulate) + adamml_residual_bwd: the block-output gradient is written once. */
+ * Replaces adamml_conv_bwd_data(accumulate) + adamml_residual_bwd: the block-output gradient is written once.
+ * The 3x3 form against that pair at ResNet-34's training geometry (72 x 8 frames per segment call, profiles/basicblock_dgrad_res.json,
+ * tools/bench_basicblock_dgrad_res.py): 0.322 vs 0.483 ms at 64 @ 56^2 (the 64-channel kernel; the tile kernel, timed with a second
+ * BatchNorm operand, 0.523), 0.128 vs 0.145 at 128 @ 28^2, 0.075 vs 0.090 at 256 @ 14^2, 0.057 vs 0.076 at 512 @ 7^2 -- each beyond the
+ * larger spread (90th percentile - min) of the two, so the probe accepts all four shapes and the 64-channel kernel keeps its shape. */
 ADAMML_API int adamml_conv_bwd_data_res_supported(const adamml_conv_desc_t* d);
-/* 1 when an adamml_conv_bwd_data_res launch in the algebraic backward's form (accumulate, res_mask, z_a == z_b == NULL) is served by
- * the barrier-free streaming kernel of csrc/res_prod_stream.hip (the ResNet-50 layer-2 shape: d->Cin == 512, d->Cout == 128, >= 4096
- * pixels per group; dx bit-identical) rather than the tile kernel -- a label for profilers.  ADAMML_RES_PROD_STREAM=0 disables it. */
+/* Which kernel serves an adamml_conv_bwd_data_res launch -- a label for profilers and tests.  0: the tile kernel (csrc/conv_gemm.hip).
+ * 1: a launch in the algebraic backward's form (accumulate, res_mask, z_a == z_b == NULL) is served by the barrier-free streaming kernel of
+ * csrc/res_prod_stream.hip (the ResNet-50 layer-2 shape: d->Cin == 512, d->Cout == 128, >= 4096 pixels per group; dx bit-identical);
+ * ADAMML_RES_PROD_STREAM=0 disables it.  2: a 3x3 launch without a second BatchNorm operand (z_b == NULL) is served by the residual
+ * instance of the 64-channel kernel of csrc/conv3x3_c64.hip (3x3 / pad 1 / stride 1, 64 -> 64 channels, 8 <= W <= 256, any accumulate,
+ * either mask form, z_a given or NULL); with z_b the tile kernel serves it.  Launches of other forms go to the tile kernel. */
 ADAMML_API int adamml_conv_bwd_data_res_streams(const adamml_conv_desc_t* d);
 ADAMML_API int adamml_conv_bwd_data_res(const adamml_conv_desc_t* d, const void* dz, const void* w_dgrad_packed, void* dx,
                              int accumulate, const void* res_out, const uint8_t* res_mask, int res_act, const void* z_a, const float* vec_a,
