@@ -8,7 +8,8 @@ Every row drives one forward and one backward of a real model through its own `_
   * asserts a written expectation of the entry points that ran (hip.LaunchProfiler).
 Shapes are the smallest that reach the branch (the host-side *_supported / *_streams probes answer without a GPU).
 Partial freezes run in two variants (the frozen parameters' gradient buffers kept, or none at all); the forward-only rows (train mode
-under no_grad, eval mode) replay the forward alone; the op-level rows drive the graphs of tools/executor_ops.py through the same run_row."""
+under no_grad, eval mode) replay the forward alone; the op-level rows drive the graphs of tools/executor_ops.py through the same run_row.
+The BasicBlock arm (ResNet-18 / -34: the fused 3x3 residual data gradient and the host decisions around it) has its rows at the end."""
 import collections
 import time
 
@@ -168,10 +169,10 @@ def run_row(net, x, groups, out_cols, monkeypatch, frozen=(), label="", frozen_b
     return dict(names=counts, log=log, rep=rep, res=res, pnames=names, net=net, ref=ref, got=got, out=out.detach().cpu().clone())
 
 
-def resnet(frames, **kw):
+def resnet(frames, depth=50, **kw):
     from adamml_amd.resnet import ResNet
     torch.manual_seed(0)
-    net = ResNet(50, num_frames=frames, num_classes=11, dropout=0.0, **kw)
+    net = ResNet(depth, num_frames=frames, num_classes=11, dropout=0.0, **kw)
     randomize(net, 1)
     return net
 
@@ -233,6 +234,22 @@ def test_resnet50_avg_pooling(monkeypatch):
     assert n["adamml_residual_bwd"] >= 1
 
 
+def exact_zeros(r):
+    """the reference's exact zeros are exact zeros in the result, element by element (a small non-zero value there would pass a rel-L2
+    bound) -> the keys of the tensors that are zero as a whole"""
+    nz, whole = 0, []
+    for k, v in r["ref"].items():
+        z = v == 0
+        nz += int(z.sum())
+        bad = int((r["got"][k][z] != 0).sum())
+        assert bad == 0, "%s: %d elements are exact zeros of the reference but not of the result" % (r["pnames"][k], bad)
+        if bool(z.all()):
+            whole.append(k)
+    print("  exact zeros of the reference: %d elements, %d whole tensors" % (nz, len(whole)))
+    assert nz > 0
+    return whole
+
+
 def _zero_bn3(net):
     net.layer1[1].bn3.weight.data.zero_()
 
@@ -256,18 +273,7 @@ def test_resnet50_edge_parameters(monkeypatch, case):
     net = resnet(4)
     r = resnet_row(net, 44, 2, 3, monkeypatch, "resnet50-edge-" + case,
                    prepare={"bn3-gamma-zero": _zero_bn3, "conv3-zero-row": _zero_row, "conv3-cancelling-row": _cancelling_row}[case])
-    # the reference's exact zeros are exact zeros in the result, element by element (a small non-zero value there would pass a rel-L2 bound)
-    nz, whole = 0, []
-    for k, v in r["ref"].items():
-        z = v == 0
-        nz += int(z.sum())
-        bad = int((r["got"][k][z] != 0).sum())
-        assert bad == 0, "%s: %d elements are exact zeros of the reference but not of the result" % (r["pnames"][k], bad)
-        if bool(z.all()):
-            whole.append(k)
-    print("  exact zeros of the reference: %d elements, %d whole tensors" % (nz, len(whole)))
-    assert nz > 0
-    zeros = whole
+    zeros = exact_zeros(r)
     bn3 = net.layer1[1].bn3
     vec = [c for c in r["rep"].calls if c.op == "conv_bn_add" and c.args["bn"] is bn3][0].aux[2].detach().cpu().double()
     if case == "conv3-zero-row":
@@ -654,3 +660,214 @@ def test_ops_accumulating_add(monkeypatch):
     accum = [a for a in launches(r, "adamml_bn_act_add") if a[1] is None and a[2] is None and a[5] is not None]
     assert len(accum) >= 1 and all(a[0] == a[9] for a in accum)          # in place: t.grad += g
     assert r["names"]["adamml_residual_bwd"] == 2
+
+
+# ------------------------------------------------------------------------------------- the BasicBlock arm of ResNet._run (ResNet-18 / -34)
+# The host decisions around adamml_conv_bwd_data_res on 3x3 convs: which conv is the last consumer of an add output, when _residual_fusable
+# hands the add's backward to conv1's epilogue, how the stride-2 conv1 and the stride-2 1x1 downsample share h.grad, the max-pool output as
+# layer1.0's identity operand, the temporal pool finishing the last add of a stage.  Same run_row / forward_only, same K, nothing tuned;
+# the weights are randomize(net, 1) on the default initialisation, as for ResNet-50.
+ABSENT_BASIC = ("adamml_conv_fwd_bn_add", "adamml_alg_", "adamml_gram_", "adamml_conv_bwd_data_dual", "adamml_conv_bwd_data_res_prod")
+
+
+def residual_dgrads(r):
+    """-> [(Cin, H, what adamml_conv_bwd_data_res_streams answers for the logged descriptor)] of the adamml_conv_bwd_data_res launches,
+    in forward order (the tape runs them last layer first)"""
+    from ctypes import byref
+    out = []
+    for a in launches(r, "adamml_conv_bwd_data_res"):
+        d = a[0]._obj
+        assert (d.KH, d.KW, d.stride, d.pad, d.Cin, d.H) == (3, 3, 1, 1, d.Cout, d.W)
+        out.append((d.Cin, d.H, hip.load().adamml_conv_bwd_data_res_streams(byref(d))))
+    return out[::-1]
+
+
+def basic_common(r, convs=19):
+    """what every grad-mode BasicBlock row launches: one plain forward conv per conv, no Bottleneck-only form"""
+    n = r["names"]
+    assert not [k for k in n if k.startswith(ABSENT_BASIC)], sorted(n)
+    assert n["adamml_conv_fwd"] == convs and n["adamml_conv_stem_fwd"] == 1 and n["adamml_bn_finalize"] == convs + 1
+    assert n["adamml_bn_act_add_mask"] == (convs - 3) // 2 and n["adamml_maxpool2d_fwd"] == 1
+
+
+def bn_vec(r, bn):
+    """the recorded [G, 4, C] vectors (scale, shift, mean, invstd) of the conv_bn call that applied the BatchNorm `bn`"""
+    return [c for c in r["rep"].calls if c.op == "conv_bn" and c.args["bn"] is bn][0].snap.vec.detach().cpu().double()
+
+
+def test_resnet18_c64_g3(monkeypatch):
+    """44 x 44, 2 clips of 4 frames per group, 3 groups: spatial sizes 11, 6, 3, 2.  The 64-channel 3x3 residual data gradient (layer1.1.conv1
+    finishing layer1.0's add) is the resident-weight kernel of conv3x3_c64.hip; layers 1 and 2 end in a temporal pool that finishes their
+    last add, layer 3 is left with one frame (an identity pool) and layer 4 has none: their last adds run adamml_residual_bwd."""
+    r = resnet_row(resnet(4, depth=18), 44, 2, 3, monkeypatch, "resnet18-c64-g3")
+    n = r["names"]
+    basic_common(r)
+    assert residual_dgrads(r) == [(64, 11, 2), (128, 6, 0), (256, 3, 0), (512, 2, 0)]
+    assert residual_bwd_channels(r) == [512, 256]
+    assert n["adamml_temporal_pool_fwd"] == 3 and n["adamml_temporal_pool_bwd_res"] == 2 and n["adamml_temporal_pool_bwd"] == 1
+    assert n["adamml_conv_bwd_data"] == 7 and n["adamml_conv_bwd_data_bn"] == 8 and n["adamml_conv_bwd_weight"] == 19
+    assert n["adamml_maxpool2d_bwd_bn_apply"] == 1 and n["adamml_conv_stem_bwd_weight"] == 1
+
+
+def test_resnet18_tile_7x7_without_t_stride(monkeypatch):
+    """28 x 28, 2 clips of 4 frames per group, 2 groups, no temporal pool: spatial sizes 7, 4, 2, 1 (8 values per channel and group in layer 4).
+    64 channels at W = 7 stay with the tile kernel.  Layer 4's stride-1 3x3 convs see 1 x 1 images: eight of their nine taps only ever
+    read padding (layer4.0.conv1, stride 2 on 2 x 2: five of nine), and the weight gradient there is an exact zero."""
+    r = resnet_row(resnet(4, depth=18, without_t_stride=True), 28, 2, 2, monkeypatch, "resnet18-tile-7x7-no-t-stride")
+    basic_common(r)
+    assert residual_dgrads(r) == [(64, 7, 0), (128, 4, 0), (256, 2, 0), (512, 1, 0)]
+    assert residual_bwd_channels(r) == [512, 256, 128, 64]
+    assert not [k for k in r["names"] if "temporal_pool" in k]
+    exact_zeros(r)
+    by_name = {v: k for k, v in r["pnames"].items()}
+    centre = torch.zeros(3, 3, dtype=torch.bool)
+    centre[1, 1] = True
+    for name in ("layer4.0.conv2.weight", "layer4.1.conv1.weight", "layer4.1.conv2.weight"):
+        ref, got = r["ref"][by_name[name]], r["got"][by_name[name]]
+        assert bool((ref[:, :, ~centre] == 0).all()) and bool((got[:, :, ~centre] == 0).all()), name
+        assert float(ref[:, :, 1, 1].norm()) > 0 and float(got[:, :, 1, 1].norm()) > 0, name
+    ref, got = r["ref"][by_name["layer4.0.conv1.weight"]], r["got"][by_name["layer4.0.conv1.weight"]]
+    assert bool((ref[:, :, 0] == 0).all() and (ref[:, :, :, 0] == 0).all() and (got[:, :, 0] == 0).all() and (got[:, :, :, 0] == 0).all())
+
+
+def test_resnet18_avg_pooling(monkeypatch):
+    """12 frames (12, 6, 3), one clip: the average pool refuses the fused backward, every stage's last add runs adamml_residual_bwd"""
+    r = resnet_row(resnet(12, depth=18, pooling_method="avg"), 44, 1, 1, monkeypatch, "resnet18-avg", rows=2)
+    n = r["names"]
+    basic_common(r)
+    assert n["adamml_temporal_pool_fwd"] == 3 and n["adamml_temporal_pool_bwd"] == 3 and n["adamml_temporal_pool_bwd_res"] == 0
+    assert n["adamml_residual_bwd"] == 4 and n["adamml_conv_bwd_data_res"] == 4
+    assert [a[7] for a in launches(r, "adamml_temporal_pool_fwd")] == [12, 6, 3]
+
+
+def test_resnet18_t8_23x23(monkeypatch):
+    """8 frames of 92 x 92, 2 clips: layer 1 is 23 x 23 -- the 64-channel kernel takes a 20-row strip and a ragged 3-row strip per image, at an
+    odd width -- and every stage pools (8, 4, 2 frames), so three of the four last adds are finished by the pool's backward."""
+    r = resnet_row(resnet(8, depth=18), 92, 2, 1, monkeypatch, "resnet18-t8-23x23")
+    n = r["names"]
+    basic_common(r)
+    assert [a[7] for a in launches(r, "adamml_temporal_pool_fwd")] == [8, 4, 2]
+    assert residual_dgrads(r) == [(64, 23, 2), (128, 12, 0), (256, 6, 0), (512, 3, 0)]
+    assert n["adamml_temporal_pool_bwd_res"] == 3 and n["adamml_temporal_pool_bwd"] == 0 and residual_bwd_channels(r) == [512]
+
+
+def test_resnet34_g1(monkeypatch):
+    """ResNet-34, 44 x 44, 2 clips of 4 frames.  13 blocks have no downsample branch; layer1.0 is one of them, and its conv1 reads the stem's
+    max-pool output, which is no residual add: 12 fused residual data gradients, not 13."""
+    net = resnet(4, depth=34)
+    r = resnet_row(net, 44, 2, 1, monkeypatch, "resnet34-g1")
+    n = r["names"]
+    basic_common(r, convs=35)
+    assert sum(1 for layer in (net.layer1, net.layer2, net.layer3, net.layer4) for b in layer if b.downsample is None) == 13
+    assert [(c, h) for c, h, _ in residual_dgrads(r)] == [(64, 11)] * 2 + [(128, 6)] * 3 + [(256, 3)] * 5 + [(512, 2)] * 2
+    assert [s for _, _, s in residual_dgrads(r)] == [2] * 2 + [0] * 10
+    assert residual_bwd_channels(r) == [512, 256] and n["adamml_bn_finalize"] == 36 and n["adamml_conv_bwd_weight"] == 35
+    assert n["adamml_conv_bwd_data_res"] + n["adamml_temporal_pool_bwd_res"] + n["adamml_residual_bwd"] == 16          # every add finished once
+
+
+def _zero_bn2(net):
+    net.layer1[1].bn2.weight.data.zero_()
+
+
+def _zero_row_conv2(net):
+    net.layer1[1].conv2.weight.data[5].zero_()
+
+
+@pytest.mark.parametrize("case", ["bn2-gamma-zero", "conv2-zero-row"])
+def test_resnet18_edge_parameters(monkeypatch, case):
+    """bn2-gamma-zero: the zero_init_residual configuration on layer1.1 -- the BatchNorm'd operand of its add has scale 0, nothing flows into
+    its residual branch.  conv2-zero-row: channel 5 of layer1.1.conv2 sees no input (z = 0, variance 0)."""
+    net = resnet(4, depth=18)
+    r = resnet_row(net, 44, 2, 3, monkeypatch, "resnet18-edge-" + case, prepare={"bn2-gamma-zero": _zero_bn2, "conv2-zero-row": _zero_row_conv2}[case])
+    basic_common(r)
+    assert residual_dgrads(r) == [(64, 11, 2), (128, 6, 0), (256, 3, 0), (512, 2, 0)]
+    zeros = exact_zeros(r)
+    by_name = {v: k for k, v in r["pnames"].items()}
+    if case == "bn2-gamma-zero":
+        assert {r["pnames"][k] for k in zeros} >= {"layer1.1.conv1.weight", "layer1.1.conv2.weight", "layer1.1.bn1.weight", "layer1.1.bn1.bias"}
+        assert float(r["ref"][by_name["layer1.1.bn2.weight"]].abs().min()) > 0
+    else:
+        vec = bn_vec(r, net.layer1[1].bn2)
+        k = by_name["layer1.1.bn2.weight"]
+        assert float(r["ref"][k][5]) == 0.0 and float(r["got"][k][5]) == 0.0
+        assert bool((vec[:, 2, 5] == 0).all())
+        assert float((vec[:, 3, 5] - 1e-5 ** -0.5).abs().max()) <= 3 * 2.0 ** -23 * 1e-5 ** -0.5, vec[:, 3, 5]
+
+
+def batchnorm_params(net):
+    return [p for m in net.modules() if isinstance(m, torch.nn.BatchNorm2d) for p in m.parameters()]
+
+
+@pytest.mark.parametrize("buffers", BUFFERS)
+def test_resnet18_partly_frozen(monkeypatch, buffers):
+    """requires_grad = False on the stem and layer 1 (3 groups): no gradient for them, no stem or layer-1 weight gradient, no stem BatchNorm
+    backward behind the max-pool.  (Layer 1's data gradients and BatchNorm backwards still run -- add_act's output always asks for a
+    gradient; that is work nobody reads, not a wrong gradient, and the row does not assert it either way.)"""
+    r = resnet_row(resnet(4, depth=18), 44, 2, 3, monkeypatch, "resnet18-frozen-stem-layer1-" + buffers, frozen=lambda n: [n.conv1, n.bn1, n.layer1],
+                   frozen_buffers=buffers == BUFFERS[0])
+    assert not [k for k in r["res"] if r["pnames"][k].startswith(("conv1.", "bn1.", "layer1."))]
+    assert any(r["pnames"][k].startswith("layer2.0.") for k in r["res"]) and len(r["res"]) == 62 - 15
+    n = r["names"]
+    assert not [k for k in n if k.startswith(ABSENT_BASIC)], sorted(n)
+    assert n["adamml_conv_stem_bwd_weight"] == 0 and n["adamml_conv_bwd_weight"] == 15 and n["adamml_maxpool2d_bwd_bn_apply"] == 0
+
+
+@pytest.mark.parametrize("buffers", BUFFERS)
+def test_resnet18_frozen_batchnorm(monkeypatch, buffers):
+    """Every gamma / beta frozen: every BatchNorm-backward finalize gets null dgamma / dbeta; the fused 3x3 residual data gradients still run,
+    and the sums their epilogue accumulates are still needed for dz (the mean and variance terms of the BatchNorm backward)."""
+    r = resnet_row(resnet(4, depth=18), 44, 2, 3, monkeypatch, "resnet18-frozen-batchnorm-" + buffers, frozen=lambda n: [Params(batchnorm_params(n))],
+                   frozen_buffers=buffers == BUFFERS[0])
+    basic_common(r)
+    fin = [a for name, a in r["log"] if name in ("adamml_bn_bwd_finalize", "adamml_bn_bwd_finalize_affine")]
+    assert len(fin) == 20 and all(a[6] is None and a[7] is None for a in fin)
+    assert residual_dgrads(r) == [(64, 11, 2), (128, 6, 0), (256, 3, 0), (512, 2, 0)] and r["names"]["adamml_conv_bwd_weight"] == 19
+    assert {r["got"][k].dim() for k in r["res"]} == {1, 2, 4} and len(r["res"]) == 20 + 2         # the convs, fc.weight and fc.bias
+
+
+@pytest.mark.parametrize("buffers", BUFFERS)
+def test_resnet18_frozen_conv_weights(monkeypatch, buffers):
+    """Every 4-D parameter frozen, the BatchNorms and fc train: no weight gradient of any kind, the same data gradients"""
+    r = resnet_row(resnet(4, depth=18), 44, 2, 3, monkeypatch, "resnet18-frozen-conv-weights-" + buffers,
+                   frozen=lambda n: [Params([p for p in n.parameters() if p.dim() == 4])], frozen_buffers=buffers == BUFFERS[0])
+    basic_common(r)
+    n = r["names"]
+    assert not no_frozen_weight_gradient(r), no_frozen_weight_gradient(r)
+    assert not [k for k in n if "_bwd_weight" in k]
+    assert residual_dgrads(r) == [(64, 11, 2), (128, 6, 0), (256, 3, 0), (512, 2, 0)]
+    assert not [k for k in r["res"] if r["got"][k].dim() == 4] and len(r["res"]) == 2 * 20 + 2
+
+
+def test_resnet18_train_nograd(monkeypatch):
+    """net.train() under torch.no_grad() at the c64-g3 shape: 20 BatchNorms finalized, no mask handed to any add, no backward entry point.
+    The grad-mode step straight after meets its bound: nothing of the tape state was left behind."""
+    net = resnet(4, depth=18)
+    x = frames_input(3 * 2 * 4, 44, 3, net.input_cpad(44, 44), 5)
+    out, n, rep = forward_only(net, x, 3, monkeypatch, "resnet18-train-nograd", True, 20)
+    assert n["adamml_bn_finalize"] == 20 and n["adamml_conv_fwd"] == 19 and n["adamml_bn_act_add_mask"] == 8 and n["adamml_temporal_pool_fwd"] == 3
+    assert not [k for k in n if k.startswith(ABSENT_BASIC)], sorted(n)
+    r = resnet_row(net, 44, 2, 3, monkeypatch, "resnet18-grad-step-after-train-nograd")
+    basic_common(r)
+    assert residual_dgrads(r) == [(64, 11, 2), (128, 6, 0), (256, 3, 0), (512, 2, 0)] and net.rt.pre_pending == 0
+    print("  no-grad logits == grad-mode logits bit for bit: %s" % torch.equal(out, r["out"]))
+
+
+def test_resnet18_eval(monkeypatch):
+    """eval mode after one train-mode forward (non-trivial running statistics): 20 eval affines, no finalize, the running statistics and
+    num_batches_tracked bit for bit what they were"""
+    net = resnet(4, depth=18)
+    x = frames_input(3 * 2 * 4, 44, 3, net.input_cpad(44, 44), 5)
+    net.to(DEV)
+    net.flat_owner.ensure(torch.device(DEV, torch.cuda.current_device()))
+    net.train()
+    with torch.no_grad():
+        net._run(x.to(DEV), 3, False)
+    torch.cuda.synchronize()
+    bns = [m for m in net.modules() if isinstance(m, torch.nn.BatchNorm2d)]
+    assert len(bns) == 20 and all(float(m.running_mean.abs().max()) > 0 for m in bns)
+    before = [(m.running_mean.detach().cpu().clone(), m.running_var.detach().cpu().clone(), int(m.num_batches_tracked)) for m in bns]
+    out, n, rep = forward_only(net, x, 3, monkeypatch, "resnet18-eval", False, 20)
+    assert tuple(out.shape) == (6, 11)
+    assert n["adamml_bn_eval_affine"] == 20 and n["adamml_bn_finalize"] == 0 and n["adamml_conv_fwd"] == 19
+    for m, (rm, rv, nb) in zip(bns, before):
+        assert torch.equal(m.running_mean.cpu(), rm) and torch.equal(m.running_var.cpu(), rv) and int(m.num_batches_tracked) == nb == 3

@@ -1,7 +1,9 @@
 """tests/executor_ref.py can fail: its replay is anchored to torch, and a torch emulation of the host executor (bf16 storage at the
 runtime's storage points, Gram-matrix statistics for conv_bn_add, the algebraic dW = A.(g'^T a) + B.(W G) + C (x) s and dx forms in
 float32) passes the shared bound at K while each of seven planted executor defects misses it by at least a factor 2.  The op-level
-graphs of tools/executor_ops.py (the arms no model reaches) get the same three anchors at the end of the file, with six more defects.  No GPU."""
+graphs of tools/executor_ops.py (the arms no model reaches) get the same three anchors at the end of the file, with six more defects.
+The BasicBlock graph of ResNet-18 / -34 (MiniBasicNet) gets them too, in two placements of the residual backward -- every add masks its own
+gradient, or the next block's conv1 finishes it in its data-gradient epilogue -- with six defects of the host decisions around it.  No GPU."""
 import math
 import types
 
@@ -34,6 +36,7 @@ class ELazy:
         self.shift = None if vec is None else vec[0, 1]
         self.gs = 0 if vec is None else 4 * data.shape[-1]
         self.res, self.alg, self.val, self.requires_grad = None, False, val, requires_grad
+        self.hold = None          # an add output: what its backward shares with the conv whose data-gradient epilogue may finish it (Emu.add_act)
 
     @property
     def shape(self):
@@ -54,17 +57,58 @@ class Branch(torch.autograd.Function):
 
 class AddAct(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, a, b, act, drop_idn, no_mask):
+    def forward(ctx, a, b, act, drop_idn, no_mask, hold=None):
         out = bf(E.clamp(a + b, act))
         lo, hi = X.R.ACT_BOUNDS[act]
         ctx.m = torch.ones_like(out) if no_mask else ((out > lo) & (out < hi)).to(out.dtype)
-        ctx.drop = drop_idn
+        ctx.drop, ctx.hold = drop_idn, hold
+        if hold is not None:
+            hold.m = ctx.m
         return out
 
     @staticmethod
     def backward(ctx, g):
+        if ctx.hold is not None and ctx.hold.done:
+            # the last consumer's data-gradient epilogue already masked g (runtime._add_backward, res_done): both operands take it as it is.
+            # planted (e): the epilogue summed the gradient BEFORE the mask for the BatchNorm'd operand's backward
+            gz = ctx.hold.unmasked if ctx.hold.sum_unmasked else g
+            return gz, (torch.zeros_like(g) if ctx.drop else g), None, None, None, None
         g2 = bf(g * ctx.m)
-        return g2, (torch.zeros_like(g2) if ctx.drop else g2), None, None, None
+        return g2, (torch.zeros_like(g2) if ctx.drop else g2), None, None, None, None
+
+
+class IdnCapture(torch.autograd.Function):
+    """the identity operand of the NEXT block's add, where the next block's conv1 finishes this add's backward: its gradient is what sits in
+    x.grad (bf16, already masked by the next add) when conv1's data gradient runs -- kept for ResEpilogue, not passed on a second time"""
+    @staticmethod
+    def forward(ctx, v, hold):
+        ctx.hold = hold
+        return v.view_as(v)
+
+    @staticmethod
+    def backward(ctx, g):
+        ctx.hold.idn_grad = g
+        return torch.zeros_like(g), None
+
+
+class ResEpilogue(torch.autograd.Function):
+    """conv1's view of an add output x whose backward its data gradient finishes (runtime._dgrad_finish_residual, adamml_conv_bwd_data_res):
+    g' = bf16(act'(x) (float32 data gradient + the identity-path gradient stored in x.grad)), written once.  hold.staged: the data gradient
+    passes through the kernels' bf16 staging tile in LDS before the identity-path gradient is added (conv_gemm.hip / conv3x3_c64.hip: the
+    epilogue reads the GEMM tile back as bf16) -- no storage point, one of the roundings K = 4 is there for"""
+    @staticmethod
+    def forward(ctx, v, hold):
+        ctx.hold = hold
+        return v.view_as(v)
+
+    @staticmethod
+    def backward(ctx, g):
+        hold = ctx.hold
+        assert hold.idn_grad is not None, "the add recorded after conv1 has not run its backward: conv1 is not the last consumer"
+        total = (bf(g) if hold.staged else g) + hold.idn_grad
+        hold.unmasked = bf(total)
+        hold.done = True
+        return bf(total * hold.m), None
 
 
 class TPool(torch.autograd.Function):
@@ -176,6 +220,8 @@ class Emu:
         self.count = {}
         self.state = {}
         self.logits = None
+        # True / "staged": a last_consumer conv of an add output finishes that add's backward in its data-gradient epilogue (ResEpilogue)
+        self.fused_residual = False
         self.direct_sums = False      # True: no producer of g' leaves partial sums (the op-level graphs): sum(g' zhat) from the stored z, no sumfix
 
     def _hit(self, kind):
@@ -183,18 +229,26 @@ class Emu:
         self.count[kind] = i + 1
         return self.defects.get(kind) == i
 
-    def use(self, x):
+    def use(self, x, finish=False):
         st = self.state.setdefault(id(x), [getattr(x, "val", None), 0, x, len(self.state)])
         if st[0] is None:
             st[0] = x.data.float()
         k = st[1]
         st[1] += 1
+        v = st[0]
+        hold = getattr(x, "hold", None)
+        if finish:                          # this consumer's data gradient finishes the add that produced x
+            hold.claimed = True
+            hold.sum_unmasked, hold.staged = self._hit("sum_unmasked"), self.fused_residual == "staged"
+            v = ResEpilogue.apply(v, hold)
+        elif hold is not None and hold.claimed:
+            v = IdnCapture.apply(v, hold)
         # planted (d): the second consumer in tape order (conv1; reversed first) loses its gradient to the downsample's write
         drop = k == 1 and self._hit("two_consumers")
         # planted (1), (2): (t, k) -- the k-th consumer (forward order) of the t-th tensor that got a consumer loses its gradient: the consumer
         # recorded BEFORE it runs its backward AFTER it and overwrote the gradient it had to add to (acc dropped)
         drop = drop or self.defects.get("drop_use") == (st[3], k)
-        return Branch.apply(st[0], drop)
+        return Branch.apply(v, drop)
 
     def _running(self, bn, mean, var, n):
         run = self.running[id(bn)]
@@ -235,7 +289,7 @@ class Emu:
 
     def conv_bn(self, rt, x, cs, bn, act, sole_consumer=False, last_consumer=False):
         G = rt.groups
-        a = self.use(x)
+        a = self.use(x, finish=self._residual_fusable(x, cs, last_consumer))
         if self._alg_ok(cs, act, x):
             o, y, vec = self._alg(q(a), cs, bn, False)
             out = ELazy(y.detach().to(torch.bfloat16), vec, act, o.register_hook(bf) and o)
@@ -247,6 +301,14 @@ class Emu:
         else:
             y = F.conv2d(q(a)[..., :w.shape[1]].permute(0, 3, 1, 2), q(w), stride=cs.stride, padding=cs.pad)
         return self._bn_out(G, q(y.permute(0, 2, 3, 1)), bn, act)
+
+    def _residual_fusable(self, x, cs, last_consumer):
+        """runtime._conv_backward_plain's `c.last_consumer and _residual_fusable(x, d)`: x is the output of an add nobody has finished, the
+        add's first operand is a BatchNorm'd conv output, the conv is one adamml_conv_bwd_data_res_supported admits (1x1, or 3x3 / pad 1, stride 1)"""
+        hold = getattr(x, "hold", None)
+        if not (self.fused_residual and last_consumer and hold is not None and not hold.claimed and x.res[0].vec is not None):
+            return False
+        return not cs.depthwise and cs.stride == 1 and (cs.kh, cs.pad) in ((1, 0), (3, 1))
 
     def _bn_out(self, G, y, bn, act):
         """train-mode BatchNorm of the stored raw output y (statistics from the stored values), as one lazy tensor"""
@@ -283,9 +345,11 @@ class Emu:
         return self.logits.detach(), None
 
     def add_act(self, rt, z, idn, act, idn_sole=False):
-        out = AddAct.apply(self.use(z), self.use(idn), act, self._hit("drop_identity"), self._hit("no_mask"))
+        hold = types.SimpleNamespace(m=None, claimed=False, done=False, idn_grad=None, unmasked=None, sum_unmasked=False, staged=False)
+        out = AddAct.apply(self.use(z), self.use(idn), act, self._hit("drop_identity"), self._hit("no_mask"), hold)
         lz = ELazy(out.detach().to(torch.bfloat16), None, ACT_NONE, out)
         lz.res = (z, idn, act, idn_sole, E.mask_bits_ref(lz.data, act) if act != ACT_NONE else None)
+        lz.hold = hold
         return lz
 
     def conv_bn_add(self, rt, x, cs, bn, idn, act, idn_sole=False, tpool=0, next_cs=None):
@@ -405,6 +469,70 @@ class MiniResNet(nn.Module):
         return torch.cat(outs)
 
 
+class BasicBlock(nn.Module):
+    def __init__(self, inplanes, planes, stride):
+        super().__init__()
+        self.conv1, self.bn1 = nn.Conv2d(inplanes, planes, 3, stride, 1, bias=False), nn.BatchNorm2d(planes)
+        self.conv2, self.bn2 = nn.Conv2d(planes, planes, 3, 1, 1, bias=False), nn.BatchNorm2d(planes)
+        down = stride != 1 or inplanes != planes
+        self.downsample = nn.Sequential(nn.Conv2d(inplanes, planes, 1, stride, bias=False), nn.BatchNorm2d(planes)) if down else None
+
+
+class MiniBasicNet(nn.Module):
+    """stem + max-pool + two 64-channel BasicBlocks + temporal max-pool + a stride-2 128-channel BasicBlock with a downsample branch + a plain
+    one + head, with the parameter names and the op order of the BasicBlock arm of adamml_amd.resnet.ResNet._run"""
+    basic = True
+
+    def __init__(self, frames=4, classes=7):
+        super().__init__()
+        self.frames = frames
+        self.conv1, self.bn1 = nn.Conv2d(3, 64, 7, 2, 3, bias=False), nn.BatchNorm2d(64)
+        self.layer1 = nn.Sequential(BasicBlock(64, 64, 1), BasicBlock(64, 64, 1))
+        self.layer2 = nn.Sequential(BasicBlock(64, 128, 2), BasicBlock(128, 128, 1))
+        self.fc = nn.Linear(128, classes)
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                m.cs = ConvState(m.weight, m.stride[0], m.padding[0])
+
+    def run(self, ops, x, fused=False):
+        """the BasicBlock arm of ResNet._run with `ops` as the executor (which placement the backward takes is the executor's decision)"""
+        rt = ops.rt
+        frames = self.frames
+        h = ELazy(x, requires_grad=False)
+        h = ops.conv_bn(rt, h, self.conv1.cs, self.bn1, ACT_RELU)
+        h = ops.maxpool3x3s2(rt, h, sole_consumer=True)
+        for li, layer in enumerate((self.layer1, self.layer2)):
+            for b in layer:
+                idn = ops.conv_bn(rt, h, b.downsample[0].cs, b.downsample[1], ACT_NONE) if b.downsample is not None else h
+                o = ops.conv_bn(rt, h, b.conv1.cs, b.bn1, ACT_RELU, last_consumer=b.downsample is None)
+                o = ops.conv_bn(rt, o, b.conv2.cs, b.bn2, ACT_NONE, sole_consumer=True)
+                h = ops.add_act(rt, o, idn, ACT_RELU, idn_sole=b.downsample is not None)
+            if li == 0:
+                h = ops.temporal_pool(rt, h, frames, "max", sole_consumer=True)
+                frames //= 2
+        return ops.head(rt, h, self.fc, frames, 0.0)
+
+    def torch_forward(self, x, groups):
+        """plain torch modules, one call per group (x NCHW double)"""
+        outs = []
+        for xg in x.chunk(groups):
+            frames = self.frames
+            h = F.max_pool2d(F.relu(self.bn1(self.conv1(xg))), 3, 2, 1)
+            for li, layer in enumerate((self.layer1, self.layer2)):
+                for b in layer:
+                    idn = b.downsample(h) if b.downsample is not None else h
+                    o = F.relu(b.bn1(b.conv1(h)))
+                    h = F.relu(b.bn2(b.conv2(o)) + idn)
+                if li == 0:
+                    nt, c, hh, ww = h.shape
+                    v = h.view(nt // frames, frames, c, hh, ww).transpose(1, 2)
+                    h = F.max_pool3d(v, (3, 1, 1), (2, 1, 1), (1, 0, 0)).transpose(1, 2).reshape(-1, c, hh, ww)
+                    frames //= 2
+            f = self.fc(h.mean((2, 3)))
+            outs.append(f.view(-1, frames, f.shape[1]).mean(1))
+        return torch.cat(outs)
+
+
 class Recorded:
     """an Emu whose entry points go through a Recorder (what monkeypatch does to the model modules on the GPU)"""
 
@@ -437,8 +565,21 @@ def resnet_case(dup=False):
     return net, x.to(torch.bfloat16), g, G
 
 
+def basic_case():
+    """MiniBasicNet on 2 groups of 2 clips of 4 frames 28 x 28 (spatial sizes 7 and 4; 64 values per channel and group at the least)"""
+    torch.manual_seed(0)
+    net = MiniBasicNet()
+    randomize(net, 1)
+    G, clips, T = 2, 2, net.frames
+    x = torch.randn(G * clips * T, 28, 28, 8, generator=torch.Generator().manual_seed(2))
+    x[..., 3:] = 0
+    g = bf(torch.randn(G * clips, 7, generator=torch.Generator().manual_seed(3)))
+    return net, x.to(torch.bfloat16), g, G
+
+
 def emulate(net, x, g, G, fused=True, defects=None):
     emu = Emu(net, G, defects)
+    emu.fused_residual = fused if getattr(net, "basic", False) else False       # (MiniResNet: `fused` is conv_bn_add, its own graph)
     rec = X.Recorder()
     net.run(Recorded(emu, rec), x, fused)
     emu.logits.backward(g)
@@ -482,6 +623,31 @@ def test_unforced_replay_is_torch_autograd_resnet():
     net.zero_grad()
     out = net.torch_forward(x.double()[..., :3].permute(0, 3, 1, 2), G)
     out.backward(g.double())
+    assert X.rel_l2(rep.logits, out) <= 1e-12
+    gmax = max(p.grad.norm().item() for _, p in named)
+    for n, p in named:               # (a bias in front of another BatchNorm has an analytically zero gradient: absolute against the largest)
+        assert (p64[id(p)].grad - p.grad).norm().item() <= 1e-12 * max(p.grad.norm().item(), X.SMALL * gmax), n
+    for m in net.modules():
+        if isinstance(m, nn.BatchNorm2d):
+            assert X.rel_l2(rep.running[id(m)][0], m.running_mean) <= 1e-12 and X.rel_l2(rep.running[id(m)][1], m.running_var) <= 1e-12
+            assert rep.running[id(m)][2] == int(m.num_batches_tracked) == G
+
+
+def test_unforced_replay_is_torch_autograd_basic():
+    """the BasicBlock graph: two consumers of every block input, the stride-2 conv1 and the stride-2 downsample sharing one, the max-pool
+    output and a temporal pool's output as identity operands"""
+    net, x, g, G = basic_case()
+    emu, rec = emulate(net, x, g, G, fused=False)
+    net.double()
+    named = list(net.named_parameters())
+    p64, names = X.leaves(named, torch.float64)
+    rep = X.Replay(rec.calls, G, p64, X.running_of(net), force=False)
+    rep.backward(g)
+    net.train()
+    net.zero_grad()
+    out = net.torch_forward(x.double()[..., :3].permute(0, 3, 1, 2), G)
+    out.backward(g.double())
+    assert len(rec.calls) == 1 + 1 + 4 * 3 + 1 + 1 + 1 and [c.op for c in rec.calls].count("add_act") == 4
     assert X.rel_l2(rep.logits, out) <= 1e-12
     gmax = max(p.grad.norm().item() for _, p in named)
     for n, p in named:               # (a bias in front of another BatchNorm has an analytically zero gradient: absolute against the largest)
@@ -593,6 +759,67 @@ def test_forcing_leaves_little_undecided(clean):
     share = rep.undecided_share()
     print("undecided share %.4f" % share)
     assert rep.und[1] > 0 and share <= FR.UNDECIDED_CAP
+
+
+# --------------------------------------------------------------------------------------- the BasicBlock graph (ResNet-18 / -34), two placements
+PLACEMENTS = ["unfused", "fused-residual-epilogue", "fused-residual-epilogue-staged-tile"]
+FUSED = {"unfused": False, "fused-residual-epilogue": True, "fused-residual-epilogue-staged-tile": "staged"}
+
+
+@pytest.fixture(scope="module")
+def basic_clean():
+    """placement -> (net, x, g, G) + judge(...) of the clean emulation"""
+    out = {}
+    for placement in PLACEMENTS:
+        net, x, g, G = basic_case()
+        out[placement] = (net, x, g, G) + judge(net, x, g, G, FUSED[placement])
+    return out
+
+
+@pytest.mark.parametrize("placement", PLACEMENTS)
+def test_emulated_basic_blocks_pass_the_bound(basic_clean, placement):
+    """unfused: every add's backward masks its own gradient.  fused-residual-epilogue: where conv1 is the last consumer of an add output
+    (layer1.1.conv1, layer2.1.conv1 -- not layer1.0.conv1, which reads the max-pool output) g' is the float32 data gradient plus the stored
+    identity-path gradient, masked and rounded to bf16 once, and the add's own backward passes it on."""
+    net, x, g, G, wr, name, stat, rep, res, names, bnd = basic_clean[placement]
+    fwd = max(v[1] for v in rep.fwd.values())
+    print("%s: worst err/bound %.3f at %s; running statistics %.3f; forward %.3f; vectors %.3f; undecided share %.5f"
+          % (placement, wr, name, stat, fwd, max(rep.vec_ratio.values()), rep.undecided_share()))
+    assert wr <= 1.0 and stat <= 1.0, (wr, name, stat)
+    assert fwd <= 1.0, rep.fwd
+    assert max(rep.vec_ratio.values()) <= 1.0, rep.vec_ratio
+    assert rep.und[1] > 0 and rep.undecided_share() <= FR.UNDECIDED_CAP
+    assert len(res) == 3 * 10 + 2 and not rep.alg          # ten convs with their BatchNorms, fc; nothing ran algebraically
+
+
+def test_fused_residual_epilogue_runs_where_the_executor_takes_it():
+    """the emulation claims the epilogue at the two convs the production _residual_fusable admits on this graph, and nowhere else"""
+    net, x, g, G = basic_case()
+    emu, rec = emulate(net, x, g, G, fused=True)
+    adds = [st[2] for st in emu.state.values() if getattr(st[2], "hold", None) is not None]
+    assert [(h.hold.claimed, h.hold.done) for h in adds] == [(True, True), (False, False), (True, True), (False, False)]
+    emu, rec = emulate(net, x, g, G, fused=False)
+    assert not [st for st in emu.state.values() if getattr(st[2], "hold", None) is not None and st[2].hold.claimed]
+
+
+# Tensor 9 (in order of first use) is the temporal pool's output, the input of layer2.0: its consumers are the downsample (0), recorded first
+# and so reversed last, and conv1 (1), whose data gradient is in h.grad when the downsample's must ADD to it.  drop_use (9, 1): it overwrote.
+BASIC_DEFECTS = [("a-identity-gradient-of-the-second-add-dropped", {"drop_identity": 1}, PLACEMENTS[:2]),
+                 ("b-first-add-mask-not-applied", {"no_mask": 0}, PLACEMENTS[:2]),
+                 ("c-two-consumer-gradient-overwritten-without-downsample", {"two_consumers": 0}, PLACEMENTS[:2]),
+                 ("d-downsample-data-gradient-overwrites-conv1", {"drop_use": (9, 1)}, PLACEMENTS[:2]),
+                 ("e-epilogue-sums-the-unmasked-gradient", {"sum_unmasked": 0}, PLACEMENTS[1:]),
+                 ("f-running-var-biased", {"running_var": 5}, PLACEMENTS[:1])]
+BASIC_DEFECT_CASES = [(n, d, p) for n, d, ps in BASIC_DEFECTS for p in ps]
+
+
+@pytest.mark.parametrize("name,defect,placement", BASIC_DEFECT_CASES, ids=["%s-%s" % (c[0], c[2]) for c in BASIC_DEFECT_CASES])
+def test_planted_basic_defect_misses_the_bound(basic_clean, name, defect, placement):
+    net, x, g, G, wr0, _, stat0 = basic_clean[placement][:7]
+    assert max(wr0, stat0) <= 1.0                    # the clean run on the same input
+    wr, where, stat = judge(net, x, g, G, FUSED[placement], defect)[:3]
+    print("%s (%s): worst err/bound %.2f at %s, running statistics %.2f" % (name, placement, wr, where, stat))
+    assert max(wr, stat) >= 2.0, (name, wr, where, stat)
 
 
 # ------------------------------------------------------------------------------- op-level graphs (tools/executor_ops.py): the new forms

@@ -236,3 +236,102 @@ def test_a_step_leaves_nothing_to_the_cycle_collector(runs):
         gc.set_debug(flags)
         del gc.garbage[:]
     assert not left, left
+
+
+# ------------------------------------------------------------------------------------------- the BasicBlock arm (ResNet-18 / -34 rows)
+ABSENT_BASIC = ("adamml_conv_fwd_bn_add", "adamml_alg_", "adamml_gram_", "adamml_conv_bwd_data_dual", "adamml_conv_bwd_data_res_prod")
+
+
+def residual_dgrads(r):
+    """-> [(Cin, H, what adamml_conv_bwd_data_res_streams answers for the logged descriptor)] of the adamml_conv_bwd_data_res launches,
+    in forward order (the tape runs them last layer first)"""
+    from ctypes import byref
+    from adamml_amd import hip
+    out = []
+    for a in launches(r, "adamml_conv_bwd_data_res"):
+        d = hip.ConvDesc(*a[0])
+        assert (d.KH, d.KW, d.stride, d.pad, d.Cin, d.H) == (3, 3, 1, 1, d.Cout, d.W), a[0]
+        out.append((d.Cin, d.H, hip.load().adamml_conv_bwd_data_res_streams(byref(d))))
+    return out[::-1]
+
+
+def basic_common(r, convs=19):
+    """what every grad-mode BasicBlock row launches: one plain forward conv and one weight gradient per conv, no Bottleneck-only form"""
+    n = r.counts
+    assert not [k for k in n if k.startswith(ABSENT_BASIC)], sorted(n)
+    assert n["adamml_conv_fwd"] == convs and n["adamml_conv_stem_fwd"] == 1 and n["adamml_bn_finalize"] == convs + 1
+    assert n["adamml_bn_act_add_mask"] == (convs - 3) // 2 and n["adamml_maxpool2d_fwd"] == 1
+
+
+def test_resnet18_c64_g3(rows):
+    r = rows["resnet18-c64-g3"]
+    n = r.counts
+    basic_common(r)
+    assert residual_dgrads(r) == [(64, 11, 2), (128, 6, 0), (256, 3, 0), (512, 2, 0)]          # 2: the resident-weight kernel of conv3x3_c64.hip
+    assert residual_bwd_channels(r) == [512, 256]
+    assert n["adamml_temporal_pool_fwd"] == 3 and n["adamml_temporal_pool_bwd_res"] == 2 and n["adamml_temporal_pool_bwd"] == 1
+    assert n["adamml_conv_bwd_data"] == 7 and n["adamml_conv_bwd_data_bn"] == 8 and n["adamml_conv_bwd_weight"] == 19
+    assert n["adamml_maxpool2d_bwd_bn_apply"] == 1 and n["adamml_conv_stem_bwd_weight"] == 1
+
+
+def test_resnet18_tile_7x7_without_t_stride(rows):
+    r = rows["resnet18-tile-7x7-no-t-stride"]
+    basic_common(r)
+    assert residual_dgrads(r) == [(64, 7, 0), (128, 4, 0), (256, 2, 0), (512, 1, 0)]           # W = 7 < 8: the tile kernel
+    assert residual_bwd_channels(r) == [512, 256, 128, 64]
+    assert not [k for k in r.counts if "temporal_pool" in k]
+
+
+def test_resnet18_avg_pooling(rows):
+    r = rows["resnet18-avg"]
+    n = r.counts
+    basic_common(r)
+    assert n["adamml_temporal_pool_fwd"] == 3 and n["adamml_temporal_pool_bwd"] == 3 and n["adamml_temporal_pool_bwd_res"] == 0
+    assert n["adamml_residual_bwd"] == 4 and n["adamml_conv_bwd_data_res"] == 4
+    assert [a[7] for a in launches(r, "adamml_temporal_pool_fwd")] == [12, 6, 3]
+
+
+def test_resnet18_t8_23x23(rows):
+    r = rows["resnet18-t8-23x23"]
+    n = r.counts
+    basic_common(r)
+    assert [a[7] for a in launches(r, "adamml_temporal_pool_fwd")] == [8, 4, 2]
+    assert residual_dgrads(r) == [(64, 23, 2), (128, 12, 0), (256, 6, 0), (512, 3, 0)]
+    assert n["adamml_temporal_pool_bwd_res"] == 3 and n["adamml_temporal_pool_bwd"] == 0 and residual_bwd_channels(r) == [512]
+
+
+def test_resnet34_g1(rows):
+    r = rows["resnet34-g1"]
+    n = r.counts
+    basic_common(r, convs=35)
+    # 13 blocks have no downsample branch; layer1.0 is one of them, and its conv1 reads the max-pool output (no residual add to finish): 12
+    assert sum(1 for l in (r.net.layer1, r.net.layer2, r.net.layer3, r.net.layer4) for b in l if b.downsample is None) == 13
+    assert [(c, h) for c, h, _ in residual_dgrads(r)] == [(64, 11)] * 2 + [(128, 6)] * 3 + [(256, 3)] * 5 + [(512, 2)] * 2
+    assert [s for _, _, s in residual_dgrads(r)] == [2] * 2 + [0] * 10
+    assert residual_bwd_channels(r) == [512, 256] and n["adamml_bn_finalize"] == 36 and n["adamml_conv_bwd_weight"] == 35
+    assert n["adamml_conv_bwd_data_res"] + n["adamml_temporal_pool_bwd_res"] + n["adamml_residual_bwd"] == 16          # every add finished once
+
+
+def test_resnet18_partly_frozen(rows):
+    n = rows["resnet18-frozen-stem-layer1"].counts
+    assert n["adamml_conv_stem_bwd_weight"] == 0 and n["adamml_conv_bwd_weight"] == 15 and n["adamml_maxpool2d_bwd_bn_apply"] == 0
+    r = rows["resnet18-frozen-batchnorm"]
+    fin = [a for name, a, m in r.log if name.startswith("adamml_bn_bwd_finalize") and m is not None]
+    assert len(fin) == 20 and all(a[6] is None and a[7] is None for a in fin)
+    assert r.counts["adamml_conv_bwd_data_res"] == 4 and r.counts["adamml_conv_bwd_weight"] == 19
+    n = rows["resnet18-frozen-conv-weights"].counts
+    assert not weight_gradient_launches(n) and not [k for k in n if "_bwd_weight" in k]
+    assert n["adamml_conv_bwd_data_res"] == 4
+    for label in ("resnet18-frozen-stem-layer1", "resnet18-frozen-batchnorm", "resnet18-frozen-conv-weights"):
+        assert not [k for k in rows[label].counts if k.startswith(ABSENT_BASIC)], label
+
+
+def test_resnet18_forward_only_rows(rows):
+    for label in ("resnet18-train-nograd", "resnet18-eval"):
+        r = rows[label]
+        assert not [k for k in r.counts if "_bwd" in k], label
+        assert not [e for e in r.log if e[2] is None], label
+        assert [a[10] for a in launches(r, "adamml_bn_act_add_mask")] == [None] * 8, label          # no mask handed to any add
+        assert r.net.rt.pre_pending == 0 and r.net.rt.pre_dropped == 0
+    assert rows["resnet18-train-nograd"].counts["adamml_bn_finalize"] == 20 and rows["resnet18-train-nograd"].counts["adamml_bn_eval_affine"] == 0
+    assert rows["resnet18-eval"].counts["adamml_bn_finalize"] == 0 and rows["resnet18-eval"].counts["adamml_bn_eval_affine"] == 20

@@ -13,9 +13,9 @@ import sys
 import torch
 
 
-def _resnet(frames, frozen=None, **kw):
+def _resnet(frames, frozen=None, depth=50, **kw):
     from adamml_amd.resnet import ResNet
-    net = ResNet(50, num_frames=frames, num_classes=11, dropout=0.0, **kw)
+    net = ResNet(depth, num_frames=frames, num_classes=11, dropout=0.0, **kw)
     return net, ([p for m in frozen(net) for p in m.parameters()] if frozen else [])
 
 
@@ -104,7 +104,23 @@ ROWS = (
     ("sound-mobilenetv2-frozen-batchnorm", _mobilenet_row("sound", frozen=lambda n: [p for p in n.parameters() if p.dim() == 1])),
     ("resnet50-frozen-conv-weights", _resnet_row(4, 44, 2, 1, frozen=lambda n: [_W([p for p in n.parameters() if p.dim() == 4])])),
     ("policy-mobilenetv2-eval", _mobilenet_row("policy", mode="eval")),
-) + tuple((label, _ops_row(label)) for label in _OPS_ROWS)
+) + tuple((label, _ops_row(label)) for label in _OPS_ROWS) + (
+    # the BasicBlock arm of ResNet._run (appended: a pointer's ordinal counts from the first row, so the lines of the rows above stay as they
+    # were).  ResNet-18 at 44 x 44 has spatial sizes 11, 6, 3, 2: the 64-channel 3x3 residual data gradient is the resident-weight kernel
+    ("resnet18-c64-g3", _resnet_row(4, 44, 2, 3, depth=18)),
+    # 28 x 28: 7, 4, 2, 1 -- 64 channels at W = 7 stay with the tile kernel; layer 4 runs its 3x3 convs on 1 x 1 images
+    ("resnet18-tile-7x7-no-t-stride", _resnet_row(4, 28, 2, 2, depth=18, without_t_stride=True)),
+    ("resnet18-avg", _resnet_row(12, 44, 1, 1, depth=18, pooling_method="avg")),
+    # 92 x 92: layer 1 is 23 x 23 (a 20-row strip and a ragged 3-row strip per image, odd width), pools over 8, 4 and 2 frames
+    ("resnet18-t8-23x23", _resnet_row(8, 92, 2, 1, depth=18)),
+    ("resnet34-g1", _resnet_row(4, 44, 2, 1, depth=34)),
+    ("resnet18-frozen-stem-layer1", _resnet_row(4, 44, 2, 3, depth=18, frozen=lambda n: [n.conv1, n.bn1, n.layer1])),
+    ("resnet18-frozen-batchnorm", _resnet_row(4, 44, 2, 3, depth=18, frozen=lambda n: [_W([p for m in n.modules() if isinstance(m, torch.nn.BatchNorm2d)
+                                                                                           for p in m.parameters()])])),
+    ("resnet18-frozen-conv-weights", _resnet_row(4, 44, 2, 3, depth=18, frozen=lambda n: [_W([p for p in n.parameters() if p.dim() == 4])])),
+    ("resnet18-train-nograd", _resnet_row(4, 44, 2, 3, depth=18, mode="train-nograd")),
+    ("resnet18-eval", _resnet_row(4, 44, 2, 3, depth=18, mode="eval")),
+)
 
 
 class _W:
