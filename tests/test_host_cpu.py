@@ -47,9 +47,10 @@ def test_library_exports_every_declared_symbol(built):
 # entry points no test module has to name, with the reason (everything else declared in the header must appear in a tests/test_*.py)
 ABI_TEST_EXEMPT = {
     "adamml_last_error_string": "query: hip.call reads it on every failing launch",
-    "adamml_plan_run": "plan plumbing: driven through adamml_amd/plan.py (tests/test_launch_plan_gpu.py)",
-    "adamml_plan_events_create": "plan plumbing: driven through adamml_amd/plan.py",
-    "adamml_plan_events_destroy": "plan plumbing: driven through adamml_amd/plan.py",
+    "adamml_plan_run": "plan plumbing: every model row replayed through adamml_amd/plan.py, bit for bit against eager (tests/test_launch_plan_rows_gpu.py, "
+                       "tests/test_launch_plan_gpu.py); its records decoded against the eager launch list (tests/test_launch_plan_cpu.py)",
+    "adamml_plan_events_create": "plan plumbing: the weight-gradient stream rows of tests/test_launch_plan_rows_gpu.py replay through its events",
+    "adamml_plan_events_destroy": "plan plumbing: runs when a plan of tests/test_launch_plan_rows_gpu.py is dropped (the eviction scenario)",
 }
 
 
@@ -84,9 +85,10 @@ CONFORMANCE_EXEMPT = {
     "last_error_string": "plumbing: hip.call reads it on every failing launch",
     "set_deterministic": "plumbing: accepted and ignored, there is one reduction mode (test_library_exports_every_declared_symbol)",
     "get_deterministic": "plumbing: always 1 (test_library_exports_every_declared_symbol)",
-    "plan_run": "plan plumbing: replays recorded launches of entry points that have their own rows (tests/test_launch_plan_gpu.py)",
-    "plan_events_create": "plan plumbing: driven through adamml_amd/plan.py",
-    "plan_events_destroy": "plan plumbing: driven through adamml_amd/plan.py",
+    "plan_run": "plan plumbing: replays recorded launches of entry points that have their own rows; the replay itself is compared with eager "
+                "per model row (tests/test_launch_plan_rows_gpu.py, tests/test_launch_plan_gpu.py) and decoded on the host (tests/test_launch_plan_cpu.py)",
+    "plan_events_create": "plan plumbing: the weight-gradient stream rows of tests/test_launch_plan_rows_gpu.py",
+    "plan_events_destroy": "plan plumbing: the eviction scenario of tests/test_launch_plan_rows_gpu.py",
     "plan_num_entry_points": "plan plumbing: the length of the thunk table (test_launch_plan_thunks_are_in_sync_with_the_c_abi)",
 }
 

@@ -51,7 +51,9 @@ def _steps(c, n, planned, forced, stage, dropout=0.0):
             # a real loader hands over a NEW tensor every batch: the plan's pointer slots (input, incoming gradient) must follow the moving
             # addresses (an allocation of changing size in between keeps the caching allocator from returning the same block)
             hold.append(torch.empty(4096 * (it + 1) + 17, device=DEV))
-            xs_it = [t.clone() for t in xs]
+            # ... with OTHER VALUES: a replay that read the recorded call's input buffer (kept alive by the plan, still holding step 3's
+            # values) instead of slot 0 would otherwise compute the right answer.  The same scale in the eager and in the planned run
+            xs_it = [t * (1.0 - 0.0625 * it) for t in xs]
             logits, sel = ddp(xs_it, gumbel_exponential=expo)
             loss = F.cross_entropy(logits, target)
             if stage == "policy":
