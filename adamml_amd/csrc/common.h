@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <type_traits>
 
 typedef uint16_t bf16_t;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -76,6 +77,15 @@ __device__ __forceinline__ f32x4 transform4(bf16x4 raw, const float* scale, cons
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+// f(std::integral_constant<int, 0>{}) .. f(std::integral_constant<int, N - 1>{}): a loop whose index is a compile-time constant in the body
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+    if constexpr (N > 0) {
+        static_for<N - 1>(f);
+        f(std::integral_constant<int, N - 1>{});
+    }
+}
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE attribute of a kernel: raise it once per (kernel, device), thread-safely.
 // `done` = the call site's own bit set (one bit per device).  A process-wide `static bool` (rounds 4-5) left the limit at 64 KB on every
 // device but the first one a process drives, and was a data race between threads (round-5 advisor finding).
@@ -87,6 +97,18 @@ struct AdamLdsOnce {
 static inline int adamml_current_device() {
     int dev = -1;
     return hipGetDevice(&dev) == hipSuccess ? dev : -1;
+}
+// before a launch with `bytes` of dynamic LDS: raise the kernel's limit on the current device unless `once` (the call site's own static) says
+// it is done; 64 KB need no attribute.  0, or the error set (`what`: the entry point's name in the message).
+static inline int adamml_raise_lds_limit(AdamLdsOnce& once, const void* kernel, size_t bytes, const char* what) {
+    const int dev = adamml_current_device();
+    if (once.test(dev)) return ADAMML_OK;
+    if (bytes > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e != hipSuccess) return adamml_set_error(ADAMML_ELAUNCH, "%s: cannot raise the dynamic LDS limit: %s", what, hipGetErrorString(e));
+    }
+    once.set(dev);
+    return ADAMML_OK;
 }
 
 // ---- reproducible per-channel reductions (BatchNorm statistics, BatchNorm-backward sums) ---------------------------------------

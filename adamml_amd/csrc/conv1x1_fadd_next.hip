@@ -17,7 +17,7 @@
 #include <type_traits>
 #include "common.h"
 #include "conv_internal.h"
-#include "../../include/adamml_hip.h"
+#include "waveslice.h"
 
 namespace {
 
@@ -48,8 +48,6 @@ struct FNP {
     long P;
 };
 
-typedef __attribute__((ext_vector_type(4))) short s16x4_;
-
 // ALLFULL: P % 16 == 0 (the launcher's choice) and MASK: mask_out given -- compile-time, so that the tile loop holds no store under a per-lane
 // or run-time condition (behind one, every wait is a conservative one: tpool_bwd_prod.hip went 1.74 -> 1.60 ms on that alone; THIS kernel measured the same either way, 2.32 ms)
 template <bool NEXT, bool ALLFULL, bool MASK>
@@ -78,7 +76,7 @@ __global__ __launch_bounds__(NW * 64, 1) void conv1x1_fadd_next_kernel(FNP p) {
             const int row = i / (CB / 8), ch = i - row * (CB / 8);
             *reinterpret_cast<bf16x8*>(s_w1 + row * W1ROW + ch * 16) = *reinterpret_cast<const bf16x8*>(p.w1 + (size_t)row * CB + ch * 8);
         }
-    for (int i = tid; i < C3IN; i += NW * 64) {
+    for (int i = tid; i < C3IN; i += NW * 64) {                             // (own text, not waveslice.h's helper: with it this kernel's code changes)
         s_vec[i] = p.in_scale ? p.in_scale[(size_t)g * p.in_gs + i] : 1.f;
         s_vec[C3IN + i] = p.in_scale ? p.in_shift[(size_t)g * p.in_gs + i] : 0.f;
     }
@@ -89,9 +87,8 @@ __global__ __launch_bounds__(NW * 64, 1) void conv1x1_fadd_next_kernel(FNP p) {
         s_bn[3 * CB + i] = p.id_scale ? p.id_shift[(size_t)g * p.id_gs + i] : 0.f;
     }
     __syncthreads();
-    auto uniform = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
-    const float alo = uniform(p.in_scale ? act_lo(p.in_act) : -INFINITY), ahi = uniform(p.in_scale ? act_hi(p.in_act) : INFINITY);
-    const float rlo = uniform(act_lo(p.act)), rhi = uniform(act_hi(p.act));
+    const float alo = lazy_lo(p.in_scale, p.in_act), ahi = lazy_hi(p.in_scale, p.in_act);
+    const float rlo = wave_uniform(act_lo(p.act)), rhi = wave_uniform(act_hi(p.act));
     const bool lazy = p.in_scale != nullptr, has_idn = p.idn != nullptr;
     char* stg = s_stage + wave * (TPX * SROW);
     const long ntile = (p.P + TPX - 1) / TPX;
@@ -132,13 +129,7 @@ __global__ __launch_bounds__(NW * 64, 1) void conv1x1_fadd_next_kernel(FNP p) {
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
             fb[k] = rx[k];
-            if (lazy) {
-                const f32x8 sc = load_f32x8(s_vec + k * 32 + lg * 8), sh = load_f32x8(s_vec + C3IN + k * 32 + lg * 8);
-                f32x8 v = bf8_to_f32(fb[k]);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) v[i] = clamp_act(fmaf(v[i], sc[i], sh[i]), alo, ahi);
-                fb[k] = f32_to_bf8(v);
-            }
+            if (lazy) fb[k] = lazy8(fb[k], load_f32x8(s_vec + k * 32 + lg * 8), load_f32x8(s_vec + C3IN + k * 32 + lg * 8), alo, ahi);
         }
         {
             const long tn = t + nw;
@@ -227,12 +218,7 @@ __global__ __launch_bounds__(NW * 64, 1) void conv1x1_fadd_next_kernel(FNP p) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const int e = lane + 64 * i, px = e >> 3, ch = e & 7;
-                if (ALLFULL || px < npx) {
-                    union { struct { s16x4_ a, b; } s; bf16x8 v; } u;
-                    u.s.a = *reinterpret_cast<const s16x4_*>(stg + px * ZROW + ch * 16);
-                    u.s.b = *reinterpret_cast<const s16x4_*>(stg + px * ZROW + ch * 16 + 8);
-                    *reinterpret_cast<bf16x8*>(p.y1 + ((size_t)t * TPX + px) * C1OUT + ch * 8) = u.v;
-                }
+                if (ALLFULL || px < npx) *reinterpret_cast<bf16x8*>(p.y1 + ((size_t)t * TPX + px) * C1OUT + ch * 8) = unstage8(stg + px * ZROW + ch * 16);
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         }
@@ -303,7 +289,7 @@ __global__ __launch_bounds__(NW * 64, 1) void conv1x1_fadd_tpool_kernel(FTP p) {
         const int row = i / (C3IN / 8), ch = i - row * (C3IN / 8);
         *reinterpret_cast<bf16x8*>(s_w3 + row * W3ROW + ch * 16) = *reinterpret_cast<const bf16x8*>(p.w3 + (size_t)row * C3IN + ch * 8);
     }
-    for (int i = tid; i < C3IN; i += NW * 64) {
+    for (int i = tid; i < C3IN; i += NW * 64) {                             // (own text, not waveslice.h's helper: with it this kernel's code changes)
         s_vec[i] = p.in_scale ? p.in_scale[(size_t)g * p.in_gs + i] : 1.f;
         s_vec[C3IN + i] = p.in_scale ? p.in_shift[(size_t)g * p.in_gs + i] : 0.f;
     }
@@ -314,9 +300,8 @@ __global__ __launch_bounds__(NW * 64, 1) void conv1x1_fadd_tpool_kernel(FTP p) {
         s_bn[3 * CB + i] = p.id_scale ? p.id_shift[(size_t)g * p.id_gs + i] : 0.f;
     }
     __syncthreads();
-    auto uniform = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
-    const float alo = uniform(p.in_scale ? act_lo(p.in_act) : -INFINITY), ahi = uniform(p.in_scale ? act_hi(p.in_act) : INFINITY);
-    const float rlo = uniform(act_lo(p.act)), rhi = uniform(act_hi(p.act));
+    const float alo = lazy_lo(p.in_scale, p.in_act), ahi = lazy_hi(p.in_scale, p.in_act);
+    const float rlo = wave_uniform(act_lo(p.act)), rhi = wave_uniform(act_hi(p.act));
     const bool lazy = p.in_scale != nullptr;
     char* stg = s_stage + wave * (TPX * SROW);
     const int tpf = (p.HW + TPX - 1) / TPX;                                  // pixel blocks per frame
@@ -370,13 +355,7 @@ __global__ __launch_bounds__(NW * 64, 1) void conv1x1_fadd_tpool_kernel(FTP p) {
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
                 fb[k] = rx[k];
-                if (lazy) {
-                    const f32x8 sc = load_f32x8(s_vec + k * 32 + lg * 8), sh = load_f32x8(s_vec + C3IN + k * 32 + lg * 8);
-                    f32x8 v = bf8_to_f32(fb[k]);
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) v[i] = clamp_act(fmaf(v[i], sc[i], sh[i]), alo, ahi);
-                    fb[k] = f32_to_bf8(v);
-                }
+                if (lazy) fb[k] = lazy8(fb[k], load_f32x8(s_vec + k * 32 + lg * 8), load_f32x8(s_vec + C3IN + k * 32 + lg * 8), alo, ahi);
             }
             issue(ntask_, nt);
             constexpr unsigned tapbits = ODD ? 0xAAAAu : 0x5555u;            // this frame's tap in the open window: 2 (odd frame) or 1
@@ -463,20 +442,11 @@ int adamml_conv1x1_fadd_next_launch(const adamml_conv_desc_t* d, const void* x, 
     if (p.P <= 0) return ADAMML_OK;
     const int groups = d->groups < 1 ? 1 : d->groups;
     const long ntile = (p.P + TPX - 1) / TPX;
-    long nblk = (ntile + NW - 1) / NW;
-    long cap = 256 / groups;                                             // one workgroup per CU over all groups
-    if (cap < 1) cap = 1;
-    if (nblk > cap) nblk = cap;
-    const dim3 grid((unsigned)nblk, groups);
-    const int attr_dev = adamml_current_device();
+    const dim3 grid((unsigned)persistent_blocks((ntile + NW - 1) / NW, groups, 1), groups);      // one workgroup per CU over all groups
     auto launch = [&](auto next_c, auto full_c, auto mask_c) -> int {
         constexpr bool NEXT = decltype(next_c)::value, FULL = decltype(full_c)::value, MASK = decltype(mask_c)::value;
         static AdamLdsOnce attr_once;                // (per device and instance: common.h)
-        if (!attr_once.test(attr_dev)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_fadd_next_kernel<NEXT, FULL, MASK>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-            if (e != hipSuccess) return adamml_set_error(ADAMML_ELAUNCH, "conv_fwd_bn_add_next: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
-            attr_once.set(attr_dev);
-        }
+        if (int rc = adamml_raise_lds_limit(attr_once, reinterpret_cast<const void*>(conv1x1_fadd_next_kernel<NEXT, FULL, MASK>), LDS_BYTES, "conv_fwd_bn_add_next")) return rc;
         hipLaunchKernelGGL((conv1x1_fadd_next_kernel<NEXT, FULL, MASK>), grid, dim3(NW * 64), LDS_BYTES, stream, p);
         return 0;
     };
@@ -510,20 +480,11 @@ int adamml_conv1x1_fadd_tpool_launch(const adamml_conv_desc_t* d, const void* x,
     const int groups = d->groups < 1 ? 1 : d->groups;
     constexpr int LDS_TP = CB * W3ROW + 2 * C3IN * 4 + 4 * CB * 4 + NW * TPX * SROW;
     const long ntask = (long)p.clips * ((p.HW + TPX - 1) / TPX);
-    long nblk = (ntask + NW - 1) / NW;
-    long cap = 256 / groups;                                             // one workgroup per CU over all groups
-    if (cap < 1) cap = 1;
-    if (nblk > cap) nblk = cap;
-    const dim3 grid((unsigned)nblk, groups);
-    const int attr_dev = adamml_current_device();
+    const dim3 grid((unsigned)persistent_blocks((ntask + NW - 1) / NW, groups, 1), groups);      // one workgroup per CU over all groups
     auto launch = [&](auto full_c, auto code_c) -> int {
         constexpr bool FULL = decltype(full_c)::value, CODE = decltype(code_c)::value;
         static AdamLdsOnce attr_once;                // (per device and instance: common.h)
-        if (!attr_once.test(attr_dev)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_fadd_tpool_kernel<FULL, CODE>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TP);
-            if (e != hipSuccess) return adamml_set_error(ADAMML_ELAUNCH, "conv_fwd_bn_add_tpool: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
-            attr_once.set(attr_dev);
-        }
+        if (int rc = adamml_raise_lds_limit(attr_once, reinterpret_cast<const void*>(conv1x1_fadd_tpool_kernel<FULL, CODE>), LDS_TP, "conv_fwd_bn_add_tpool")) return rc;
         hipLaunchKernelGGL((conv1x1_fadd_tpool_kernel<FULL, CODE>), grid, dim3(NW * 64), LDS_TP, stream, p);
         return 0;
     };

@@ -12,12 +12,10 @@
 // expression as the tile kernel: out and mask_out are bit-identical.
 #include "common.h"
 #include "conv_internal.h"
-#include "../../include/adamml_hip.h"
+#include "waveslice.h"
 #include <type_traits>
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) short s16x4_;
 
 struct FSP {
     const bf16_t* x;         // [groups][P][K] raw conv2 output
@@ -53,10 +51,7 @@ __global__ __launch_bounds__(NQ * 64, 1) void conv1x1_fadd_stream_kernel(FSP p) 
         p.idn += pp * C + q * 64;
         if (MASK) p.mask_out += pp * (C / 8) + q * 8;
     }
-    for (int i = tid; i < K; i += NQ * 64) {
-        s_vec[i] = p.in_scale ? p.in_scale[(size_t)g * p.in_gs + i] : 1.f;
-        s_vec[K + i] = p.in_scale ? p.in_shift[(size_t)g * p.in_gs + i] : 0.f;
-    }
+    fill_lazy_vec(s_vec, K, p, g, tid, NQ * 64);
     for (int i = tid; i < C; i += NQ * 64) {
         s_bn[i] = p.bn_vec[(size_t)g * 4 * C + i];
         s_bn[C + i] = p.bn_vec[(size_t)g * 4 * C + C + i];
@@ -66,9 +61,8 @@ __global__ __launch_bounds__(NQ * 64, 1) void conv1x1_fadd_stream_kernel(FSP p) 
     char* zs = s_stage + q * (TPX * ZROW);
     char* ms = s_stage + NQ * (TPX * ZROW) + q * 256;
     __syncthreads();
-    auto uniform = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
-    const float alo = uniform(p.in_scale ? act_lo(p.in_act) : -INFINITY), ahi = uniform(p.in_scale ? act_hi(p.in_act) : INFINITY);
-    const float rlo = uniform(act_lo(p.act)), rhi = uniform(act_hi(p.act));
+    const float alo = lazy_lo(p.in_scale, p.in_act), ahi = lazy_hi(p.in_scale, p.in_act);
+    const float rlo = wave_uniform(act_lo(p.act)), rhi = wave_uniform(act_hi(p.act));
     const bool lazy = p.in_scale != nullptr;
     // ---- this wave's weight slice: A fragments (row = output channel 64 q + 16 ct + li, k = 32 ks + 8 lg ..)
     bf16x8 wr[4][KS];
@@ -120,12 +114,7 @@ __global__ __launch_bounds__(NQ * 64, 1) void conv1x1_fadd_stream_kernel(FSP p) 
 #pragma unroll
             for (int pg = 0; pg < 2; ++pg) {
                 bf16x8 fb = rx[pg][ks];
-                if (lazy) {
-                    f32x8 v = bf8_to_f32(fb);
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) v[i] = clamp_act(fmaf(v[i], vs[i], vh[i]), alo, ahi);
-                    fb = f32_to_bf8(v);
-                }
+                if (lazy) fb = lazy8(fb, vs, vh, alo, ahi);
 #pragma unroll
                 for (int ct = 0; ct < 4; ++ct) c[pg][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[ct][ks], fb, c[pg][ct], 0, 0, 0);
             }
@@ -134,21 +123,14 @@ __global__ __launch_bounds__(NQ * 64, 1) void conv1x1_fadd_stream_kernel(FSP p) 
 #pragma unroll
         for (int pg = 0; pg < 2; ++pg)
 #pragma unroll
-            for (int ct = 0; ct < 4; ++ct) {
-                union { bf16x4 b; s16x4_ s; } u;
-                u.b = f32_to_bf4(c[pg][ct]);
-                *reinterpret_cast<s16x4_*>(zs + (pg * 16 + li) * ZROW + (ct * 16 + lg * 4) * 2) = u.s;
-            }
+            for (int ct = 0; ct < 4; ++ct) *reinterpret_cast<bf16x4*>(zs + (pg * 16 + li) * ZROW + (ct * 16 + lg * 4) * 2) = f32_to_bf4(c[pg][ct]);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                   // (own LDS writes landed; no other wave touches this area)
         char* ob = reinterpret_cast<char*>(p.out + (size_t)p0 * C);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int px = zpx + 8 * i;
             const char* zp = zs + px * ZROW + zch * 16;
-            union { struct { s16x4_ a, b; } s; bf16x8 v; } u;
-            u.s.a = *reinterpret_cast<const s16x4_*>(zp);
-            u.s.b = *reinterpret_cast<const s16x4_*>(zp + 8);
-            f32x8 f = bf8_to_f32(u.v);
+            f32x8 f = bf8_to_f32(unstage8(zp));
             const f32x8 w = bf8_to_f32(ri[i]);
 #pragma unroll
             for (int j = 0; j < 8; ++j) f[j] = clamp_act(fmaf(f[j], sc[j], sh[j]) + fmaf(w[j], isc[j], ish[j]), rlo, rhi);
@@ -216,7 +198,7 @@ __global__ __launch_bounds__(NQ * 64, NQ == 4 ? 2 : 1) void conv1x1_fadd_tpool_s
         p.pooled += (size_t)g * Pp * C + q * 64;
         if (CODE) p.code += (size_t)g * Pp * (C / 8) + q * 8;
     }
-    for (int i = tid; i < K; i += NQ * 64) {
+    for (int i = tid; i < K; i += NQ * 64) {                        // (own text, not waveslice.h's helper: with it this kernel's code changes)
         s_vec[i] = p.in_scale ? p.in_scale[(size_t)g * p.in_gs + i] : 1.f;
         s_vec[K + i] = p.in_scale ? p.in_shift[(size_t)g * p.in_gs + i] : 0.f;
     }
@@ -229,9 +211,8 @@ __global__ __launch_bounds__(NQ * 64, NQ == 4 ? 2 : 1) void conv1x1_fadd_tpool_s
     char* zs = s_stage + q * (TPX * ZROW);
     char* ms = s_stage + NQ * (TPX * ZROW) + q * 256;
     __syncthreads();
-    auto uniform = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
-    const float alo = uniform(p.in_scale ? act_lo(p.in_act) : -INFINITY), ahi = uniform(p.in_scale ? act_hi(p.in_act) : INFINITY);
-    const float rlo = uniform(act_lo(p.act)), rhi = uniform(act_hi(p.act));
+    const float alo = lazy_lo(p.in_scale, p.in_act), ahi = lazy_hi(p.in_scale, p.in_act);
+    const float rlo = wave_uniform(act_lo(p.act)), rhi = wave_uniform(act_hi(p.act));
     const bool lazy = p.in_scale != nullptr;
     bf16x8 wr[4][KS];
 #pragma unroll
@@ -291,22 +272,12 @@ __global__ __launch_bounds__(NQ * 64, NQ == 4 ? 2 : 1) void conv1x1_fadd_tpool_s
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks) {
                     bf16x8 fb = rx[pg][ks];
-                    if (lazy) {
-                        const f32x8 vs = load_f32x8(s_vec + ks * 32 + lg * 8), vh = load_f32x8(s_vec + K + ks * 32 + lg * 8);
-                        f32x8 v = bf8_to_f32(fb);
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) v[i] = clamp_act(fmaf(v[i], vs[i], vh[i]), alo, ahi);
-                        fb = f32_to_bf8(v);
-                    }
+                    if (lazy) fb = lazy8(fb, load_f32x8(s_vec + ks * 32 + lg * 8), load_f32x8(s_vec + K + ks * 32 + lg * 8), alo, ahi);
 #pragma unroll
                     for (int ct = 0; ct < 4; ++ct) c[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[ct][ks], fb, c[ct], 0, 0, 0);
                 }
 #pragma unroll
-                for (int ct = 0; ct < 4; ++ct) {
-                    union { bf16x4 b; s16x4_ s; } u;
-                    u.b = f32_to_bf4(c[ct]);
-                    *reinterpret_cast<s16x4_*>(zs + (pg * 16 + li) * ZROW + (ct * 16 + lg * 4) * 2) = u.s;
-                }
+                for (int ct = 0; ct < 4; ++ct) *reinterpret_cast<bf16x4*>(zs + (pg * 16 + li) * ZROW + (ct * 16 + lg * 4) * 2) = f32_to_bf4(c[ct]);
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");               // (own LDS writes landed; no other wave touches this area)
             bf16x8 vb[4];
@@ -314,10 +285,7 @@ __global__ __launch_bounds__(NQ * 64, NQ == 4 ? 2 : 1) void conv1x1_fadd_tpool_s
             for (int i = 0; i < 4; ++i) {
                 const int row = (i >> 1) * 16 + zpx + 8 * (i & 1);
                 const char* zp = zs + row * ZROW + zch * 16;
-                union { struct { s16x4_ a, b; } s; bf16x8 v; } u;
-                u.s.a = *reinterpret_cast<const s16x4_*>(zp);
-                u.s.b = *reinterpret_cast<const s16x4_*>(zp + 8);
-                f32x8 f = bf8_to_f32(u.v);
+                f32x8 f = bf8_to_f32(unstage8(zp));
                 const f32x8 w = bf8_to_f32(ri[i]);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) f[j] = clamp_act(fmaf(f[j], sc[j], sh[j]) + fmaf(w[j], isc[j], ish[j]), rlo, rhi);
@@ -364,14 +332,6 @@ __global__ __launch_bounds__(NQ * 64, NQ == 4 ? 2 : 1) void conv1x1_fadd_tpool_s
     }
 }
 
-int fs_blocks(long P, int groups) {
-    const long ntile = (P + TPX - 1) / TPX;
-    constexpr long CAP = 256;                                            // one workgroup per CU over all groups
-    long cap = CAP / (groups < 1 ? 1 : groups);
-    if (cap < 1) cap = 1;
-    return (int)(ntile < cap ? ntile : cap);
-}
-
 bool fs_on() { const char* e = getenv("ADAMML_FADD_STREAM"); return !(e && atoi(e) == 0); }                      // test hook, read at every call
 
 }  // namespace
@@ -395,7 +355,7 @@ int adamml_conv1x1_fadd_stream_launch(const adamml_conv_desc_t* d, const void* x
     p.out = (bf16_t*)out; p.mask_out = mask_out;
     p.in_act = d->act; p.in_gs = d->in_gstride; p.id_gs = id_gstride; p.act = act; p.P = (int)P;
     constexpr size_t lds = (2 * K + 4 * C) * 4 + (size_t)NQ * (TPX * ZROW + 256);
-    const dim3 grid((unsigned)fs_blocks(P, groups), groups);
+    const dim3 grid((unsigned)persistent_blocks((P + TPX - 1) / TPX, groups, 1), groups);      // one workgroup per CU over all groups
     if (mask_out) hipLaunchKernelGGL((conv1x1_fadd_stream_kernel<K, NQ, true>), grid, dim3(NQ * 64), lds, stream, p);
     else hipLaunchKernelGGL((conv1x1_fadd_stream_kernel<K, NQ, false>), grid, dim3(NQ * 64), lds, stream, p);
     return adamml_check_launch("conv_fwd_bn_add(stream)");
@@ -421,9 +381,7 @@ int adamml_conv1x1_fadd_tpool_stream_launch(const adamml_conv_desc_t* d, const v
     p.in_act = d->act; p.in_gs = d->in_gstride; p.id_gs = id_gstride; p.act = act; p.T = frames; p.HW = d->OH * d->OW; p.clips = d->N / frames;
     const long ntask = (long)p.clips * ((p.HW + 15) / 16);
     const bool l2 = d->Cin == 128;
-    long cap = (l2 ? 256 : 512) / groups;
-    if (cap < 1) cap = 1;
-    const dim3 grid((unsigned)(ntask < cap ? ntask : cap), groups);
+    const dim3 grid((unsigned)persistent_blocks(ntask, groups, l2 ? 1 : 2), groups);
     if (l2) {
         constexpr int K = 128, NQ = 8, C = NQ * 64;
         constexpr size_t lds = (2 * K + 4 * C) * 4 + (size_t)NQ * (TPX * ZROW + 256);

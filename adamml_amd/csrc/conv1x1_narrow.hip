@@ -16,7 +16,7 @@
 #include <type_traits>
 #include "common.h"
 #include "conv_internal.h"
-#include "../../include/adamml_hip.h"
+#include "waveslice.h"
 
 namespace {
 
@@ -30,8 +30,6 @@ struct N1P {
     int act, in_gs, Cin;
     long P;                  // pixels per group
 };
-
-typedef __attribute__((ext_vector_type(4))) short s16x4_;
 
 // ALLFULL: P % 32 == 0 (the launcher's choice): the tile's run leaves through unconditional stores (behind a store under a per-lane condition
 // every wait of the loop is a conservative one: csrc/tpool_bwd_prod.hip went 1.74 -> 1.60 ms on that alone)
@@ -69,8 +67,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_narrow_fwd_kernel(N1P p) {
     for (int i = tid; i < 4 * 2 * CW; i += 256) s_sum[i] = 0.f;
     __syncthreads();
 
-    auto uniform = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
-    const float alo = uniform(p.in_scale ? act_lo(p.act) : -INFINITY), ahi = uniform(p.in_scale ? act_hi(p.act) : INFINITY);
+    const float alo = wave_uniform(p.in_scale ? act_lo(p.act) : -INFINITY), ahi = wave_uniform(p.in_scale ? act_hi(p.act) : INFINITY);
     const bool lazy = p.in_scale != nullptr;
     float* csw = s_sum + wave * 2 * CW;
     char* stg = s_stage + wave * (TPX * SROW);
@@ -98,8 +95,8 @@ __global__ __launch_bounds__(256, 2) void conv1x1_narrow_fwd_kernel(N1P p) {
         const long t = wid + (long)u * nw;
         issue(u, t < ntile ? t : ntile - 1);
     }
-    union { s16x4_ h[2]; bf16x8 v; } ones;
-    ones.h[0] = s16x4_{0x3F80, 0x3F80, 0x3F80, 0x3F80};
+    union { s16x4 h[2]; bf16x8 v; } ones;
+    ones.h[0] = s16x4{0x3F80, 0x3F80, 0x3F80, 0x3F80};
     ones.h[1] = ones.h[0];
     const int trow = 8 * lg + (li >> 2);
 
@@ -124,12 +121,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_narrow_fwd_kernel(N1P p) {
                 if (lazy) {                                           // (uniform) act(scale * raw + shift), rounded as the other loaders round it
                     const f32x8 sc = load_f32x8(s_vec + k * 32 + lg * 8), sh = load_f32x8(s_vec + KP + k * 32 + lg * 8);
 #pragma unroll
-                    for (int pg = 0; pg < 2; ++pg) {
-                        f32x8 v = bf8_to_f32(fb[pg]);
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) v[i] = clamp_act(fmaf(v[i], sc[i], sh[i]), alo, ahi);
-                        fb[pg] = f32_to_bf8(v);
-                    }
+                    for (int pg = 0; pg < 2; ++pg) fb[pg] = lazy8(fb[pg], sc, sh, alo, ahi);
                 }
 #pragma unroll
                 for (int ct = 0; ct < NCT; ++ct) {
@@ -159,10 +151,10 @@ __global__ __launch_bounds__(256, 2) void conv1x1_narrow_fwd_kernel(N1P p) {
             if (p.stats) {
 #pragma unroll
                 for (int cb = 0; cb < NCT; ++cb) {
-                    const char* fp = stg + trow * SROW + (cb * 16 + 4 * (li & 3)) * 2;
-                    union { s16x4_ h[2]; bf16x8 v; } f;
-                    f.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_*)(fp));
-                    f.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_*)(fp + 4 * SROW));
+                    const char* fp = stg + trow * SROW + (cb * 16 + 4 * (li & 3)) * 2;                // (tr_frag in its own text: with the helper the prologue is scheduled differently)
+                    union { s16x4 h[2]; bf16x8 v; } f;
+                    f.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(fp));
+                    f.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(fp + 4 * SROW));
                     const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
                     const f32x4 dsum = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones.v, f.v, z4, 0, 0, 0);
                     const f32x4 dsq = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.v, f.v, z4, 0, 0, 0);
@@ -182,12 +174,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_narrow_fwd_kernel(N1P p) {
                 // repeat the chunks 32 below theirs: the same bytes to the same address, no predicate)
                 if (ALLFULL && (TPX * CPR) % 64 != 0 && e >= TPX * CPR) e -= 32;
                 const int px = e / CPR, ch = e - px * CPR;
-                if (ALLFULL || e < npx * CPR) {                      // (two 8-byte LDS reads: the staging rows are 8-byte aligned only)
-                    union { struct { s16x4_ a, b; } s; bf16x8 v; } o;
-                    o.s.a = *reinterpret_cast<const s16x4_*>(stg + px * SROW + ch * 16);
-                    o.s.b = *reinterpret_cast<const s16x4_*>(stg + px * SROW + ch * 16 + 8);
-                    *reinterpret_cast<bf16x8*>(yb + (size_t)e * 8) = o.v;
-                }
+                if (ALLFULL || e < npx * CPR) *reinterpret_cast<bf16x8*>(yb + (size_t)e * 8) = unstage8(stg + px * SROW + ch * 16);
             }
             asm volatile("" ::: "memory");
         }
@@ -207,20 +194,10 @@ int narrow_launch_(const N1P& p, int groups, hipStream_t stream) {
     constexpr int KP = KS * 32, NCT = (COUT + 15) / 16, CW = NCT * 16;
     constexpr size_t lds = (size_t)CW * (KP * 2 + 16) + 2 * KP * 4 + 4 * 2 * CW * 4 + 4 * 32 * (CW * 2 + 8);
     static AdamLdsOnce attr_once;                    // (per device: common.h)
-    const int attr_dev = adamml_current_device();
-    if (!attr_once.test(attr_dev)) {
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_narrow_fwd_kernel<KS, COUT, ALLFULL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return adamml_set_error(ADAMML_ELAUNCH, "conv1x1 (narrow): cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
-        }
-        attr_once.set(attr_dev);
-    }
+    if (int rc = adamml_raise_lds_limit(attr_once, reinterpret_cast<const void*>(conv1x1_narrow_fwd_kernel<KS, COUT, ALLFULL>), lds, "conv1x1 (narrow)")) return rc;
     const long ntile = (p.P + 31) / 32;
-    long nblk = (ntile + 3) / 4;
     const long per_cu = lds > 0 ? (160 * 1024) / (long)lds : 1;
-    long cap = 256 * (per_cu > 4 ? 4 : (per_cu < 1 ? 1 : per_cu)) / groups;         // persistent workgroups over all groups
-    if (cap < 1) cap = 1;
-    if (nblk > cap) nblk = cap;
+    const int nblk = persistent_blocks((ntile + 3) / 4, groups, per_cu > 4 ? 4 : (per_cu < 1 ? 1 : (int)per_cu));   // as many as fit a CU's LDS, <= 4
     hipLaunchKernelGGL((conv1x1_narrow_fwd_kernel<KS, COUT, ALLFULL>), dim3((unsigned)nblk, groups), dim3(256), lds, stream, p);
     return adamml_check_launch("conv_fwd (narrow 1x1 stream)");
 }
@@ -301,8 +278,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_narrow_dgrad_kernel(ND1P p) {
     constexpr int CPRB = BW / 8, PPI = 64 / CPRB, NI = (TPX + PPI - 1) / PPI;
     const int epl = lane / CPRB, ech = lane - epl * CPRB;
     const bool eact = lane < PPI * CPRB;
-    const float blo = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, act_lo(p.bn_act))));
-    const float bhi = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, act_hi(p.bn_act))));
+    const float blo = wave_uniform(act_lo(p.bn_act)), bhi = wave_uniform(act_hi(p.bn_act));
     f32x8 esum[NCB], esq[NCB];
 #pragma unroll
     for (int b = 0; b < NCB; ++b)
@@ -402,11 +378,8 @@ __global__ __launch_bounds__(256, 2) void conv1x1_narrow_dgrad_kernel(ND1P p) {
             for (int i = 0; i < NI; ++i) {
                 const int px = i * PPI + epl;
                 if (cact && px < npx) {
-                    union { struct { s16x4_ a, b; } s; bf16x8 v; } u;
-                    u.s.a = *reinterpret_cast<const s16x4_*>(stg + px * SROW + ech * 16);
-                    u.s.b = *reinterpret_cast<const s16x4_*>(stg + px * SROW + ech * 16 + 8);
-                    f32x8 f = bf8_to_f32(u.v);
-                    bf16x8 v = u.v;
+                    bf16x8 v = unstage8(stg + px * SROW + ech * 16);
+                    f32x8 f = bf8_to_f32(v);
                     if (EPI == 1) {
                         const f32x8 zv = bf8_to_f32(raux[b][i]);
 #pragma unroll
@@ -455,19 +428,9 @@ int narrow_dgrad_launch(const ND1P& p, int groups, hipStream_t stream) {
     constexpr int KP = KS * 32, NCT = (COUT + 15) / 16, NCB = (NCT + 5) / 6, BT = (NCT + NCB - 1) / NCB, BW = BT * 16;
     constexpr size_t lds = (size_t)NCB * BW * (KP * 2 + 16) + 3 * KP * 4 + 4 * NCB * BW * 4 + (EPI == 1 ? 4 * 64 * NCB * 16 * 4 : 0) + 4 * 32 * (BW * 2 + 8);
     static AdamLdsOnce attr_once;                    // (per device: common.h)
-    const int attr_dev = adamml_current_device();
-    if (!attr_once.test(attr_dev)) {
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_narrow_dgrad_kernel<KS, COUT, DUAL, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return adamml_set_error(ADAMML_ELAUNCH, "conv_bwd_data (narrow): cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
-        }
-        attr_once.set(attr_dev);
-    }
+    if (int rc = adamml_raise_lds_limit(attr_once, reinterpret_cast<const void*>(conv1x1_narrow_dgrad_kernel<KS, COUT, DUAL, EPI>), lds, "conv_bwd_data (narrow)")) return rc;
     const long ntile = (p.P + 31) / 32;
-    long nblk = (ntile + 3) / 4;
-    long cap = 768 / groups;
-    if (cap < 1) cap = 1;
-    if (nblk > cap) nblk = cap;
+    const int nblk = persistent_blocks((ntile + 3) / 4, groups, 3);
     hipLaunchKernelGGL((conv1x1_narrow_dgrad_kernel<KS, COUT, DUAL, EPI>), dim3((unsigned)nblk, groups), dim3(256), lds, stream, p);
     return adamml_check_launch("conv_bwd_data_dual (narrow 1x1 stream)");
 }
@@ -515,8 +478,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_narrow_wgrad_kernel(NW1P p) {
     // the padding columns of the staging tiles (channels COUT .. MT*16, CIN .. NT*16) are zero for the whole kernel
     for (int i = lane; i < TPX * (ZROW + XROW) / 8; i += 64) reinterpret_cast<unsigned long long*>(zs)[i] = 0ull;
     __syncthreads();
-    auto uniform = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
-    const float alo = uniform(p.in_scale ? act_lo(p.act) : -INFINITY), ahi = uniform(p.in_scale ? act_hi(p.act) : INFINITY);
+    const float alo = wave_uniform(p.in_scale ? act_lo(p.act) : -INFINITY), ahi = wave_uniform(p.in_scale ? act_hi(p.act) : INFINITY);
     const bool lazy = p.in_scale != nullptr;
     f32x4 acc[MT][NT];
 #pragma unroll
@@ -549,10 +511,10 @@ __global__ __launch_bounds__(256, 2) void conv1x1_narrow_wgrad_kernel(NW1P p) {
         for (int i = 0; i < NZ; ++i) {
             const int e = lane + 64 * i, px = e / ZC, ch = e - px * ZC;
             if (e < TPX * ZC) {
-                union { struct { s16x4_ a, b; } s; bf16x8 v; } u;
+                union { struct { s16x4 a, b; } s; bf16x8 v; } u;
                 u.v = px < npx ? rz[i] : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-                *reinterpret_cast<s16x4_*>(zs + px * ZROW + ch * 16) = u.s.a;
-                *reinterpret_cast<s16x4_*>(zs + px * ZROW + ch * 16 + 8) = u.s.b;
+                *reinterpret_cast<s16x4*>(zs + px * ZROW + ch * 16) = u.s.a;
+                *reinterpret_cast<s16x4*>(zs + px * ZROW + ch * 16 + 8) = u.s.b;
             }
         }
 #pragma unroll
@@ -560,17 +522,8 @@ __global__ __launch_bounds__(256, 2) void conv1x1_narrow_wgrad_kernel(NW1P p) {
             const int e = lane + 64 * i, px = e / XC, ch = e - px * XC;
             if (e < TPX * XC) {
                 bf16x8 v = rx[i];
-                if (lazy) {
-                    const f32x8 sc = load_f32x8(s_vec + ch * 8), sh = load_f32x8(s_vec + NT * 16 + ch * 8);
-                    f32x8 f = bf8_to_f32(v);
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) f[k] = clamp_act(fmaf(f[k], sc[k], sh[k]), alo, ahi);
-                    v = f32_to_bf8(f);
-                }
-                union { struct { s16x4_ a, b; } s; bf16x8 v; } u;
-                u.v = px < npx ? v : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-                *reinterpret_cast<s16x4_*>(xs + px * XROW + ch * 16) = u.s.a;
-                *reinterpret_cast<s16x4_*>(xs + px * XROW + ch * 16 + 8) = u.s.b;
+                if (lazy) v = lazy8(v, load_f32x8(s_vec + ch * 8), load_f32x8(s_vec + NT * 16 + ch * 8), alo, ahi);
+                stage8(xs + px * XROW + ch * 16, px < npx ? v : bf16x8{0, 0, 0, 0, 0, 0, 0, 0});
             }
         }
         {
@@ -578,30 +531,24 @@ __global__ __launch_bounds__(256, 2) void conv1x1_narrow_wgrad_kernel(NW1P p) {
             issue(tn < ntile ? tn : ntile - 1);                           // (unconditional request of this wave's next tile)
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");               // (own LDS writes landed; no other wave touches this area)
-        auto frag = [&](const char* base, int row_bytes, int blk) {
-            const char* q = base + trow * row_bytes + (blk * 16 + 4 * (li & 3)) * 2;
-            union { s16x4_ h[2]; bf16x8 v; } f;
-            f.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_*)(q));
-            f.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_*)(q + 4 * row_bytes));
-            return f.v;
-        };
+        // (staged_outer_product of waveslice.h, in its own text: behind the helper seven of the eight instances change their code)
         if constexpr (NT <= MT) {                                        // (the fragments of the NARROWER operand are held, the other side streams)
             bf16x8 fb[NT];
 #pragma unroll
-            for (int nt = 0; nt < NT; ++nt) fb[nt] = frag(xs, XROW, nt);
+            for (int nt = 0; nt < NT; ++nt) fb[nt] = tr_frag(xs, XROW, nt, trow, li);
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
-                const bf16x8 fa = frag(zs, ZROW, mt);
+                const bf16x8 fa = tr_frag(zs, ZROW, mt, trow, li);
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, fb[nt], acc[mt][nt], 0, 0, 0);
             }
         } else {
             bf16x8 fa[MT];
 #pragma unroll
-            for (int mt = 0; mt < MT; ++mt) fa[mt] = frag(zs, ZROW, mt);
+            for (int mt = 0; mt < MT; ++mt) fa[mt] = tr_frag(zs, ZROW, mt, trow, li);
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
-                const bf16x8 fb = frag(xs, XROW, nt);
+                const bf16x8 fb = tr_frag(xs, XROW, nt, trow, li);
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[mt], fb, acc[mt][nt], 0, 0, 0);
             }
@@ -638,14 +585,7 @@ int narrow_wgrad_launch(const NW1P& p, int groups, int nblk, hipStream_t stream)
     constexpr size_t stage = (size_t)4 * 32 * ((MT * 32 + 8) + (NT * 32 + 8)), foldb = (size_t)MT * 16 * NT * 16 * 4;
     constexpr size_t lds = 2 * NT * 16 * 4 + (stage > foldb ? stage : foldb);
     static AdamLdsOnce attr_once;                    // (per device: common.h)
-    const int attr_dev = adamml_current_device();
-    if (!attr_once.test(attr_dev)) {
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_narrow_wgrad_kernel<COUT, CIN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return adamml_set_error(ADAMML_ELAUNCH, "conv_bwd_weight (narrow): cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
-        }
-        attr_once.set(attr_dev);
-    }
+    if (int rc = adamml_raise_lds_limit(attr_once, reinterpret_cast<const void*>(conv1x1_narrow_wgrad_kernel<COUT, CIN>), lds, "conv_bwd_weight (narrow)")) return rc;
     hipLaunchKernelGGL((conv1x1_narrow_wgrad_kernel<COUT, CIN>), dim3((unsigned)nblk, groups), dim3(256), lds, stream, p);
     return adamml_check_launch("conv_bwd_weight (narrow 1x1 stream)");
 }

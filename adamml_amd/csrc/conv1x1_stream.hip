@@ -8,8 +8,7 @@
 // barrier -> MFMA pipeline of conv_gemm_kernel's CAT instance ran this layer at 3.6 TB/s.
 #include "common.h"
 #include "conv_internal.h"
-#include "../../include/adamml_hip.h"
-
+#include "waveslice.h"
 
 namespace {
 
@@ -66,8 +65,7 @@ __global__ __launch_bounds__(256, 3) void alg_stream_kernel(S1P p) {
     __syncthreads();
 
     // (wave-uniform clamp bounds pinned to scalar registers: as vector registers one of them was spilled to scratch and re-read per tile)
-    auto uniform = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
-    const float alo = uniform(p.a_scale ? act_lo(p.a_act) : -INFINITY), ahi = uniform(p.a_scale ? act_hi(p.a_act) : INFINITY);
+    const float alo = wave_uniform(p.a_scale ? act_lo(p.a_act) : -INFINITY), ahi = wave_uniform(p.a_scale ? act_hi(p.a_act) : INFINITY);
     float ssum[4][4], ssq[4][4];                                    // [cout tile][r]: channel ct*16 + lg*4 + r
 #pragma unroll
     for (int ct = 0; ct < 4; ++ct)
@@ -123,12 +121,7 @@ __global__ __launch_bounds__(256, 3) void alg_stream_kernel(S1P p) {
                 const int c0 = (k - K1 / 32) * 32 + lg * 8;
                 const f32x8 sc = load_f32x8(s_vec + c0), sh = load_f32x8(s_vec + C2 + c0);
 #pragma unroll
-                for (int pg = 0; pg < NPG; ++pg) {
-                    f32x8 v = bf8_to_f32(fb[pg]);
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) v[i] = clamp_act(fmaf(v[i], sc[i], sh[i]), alo, ahi);
-                    fb[pg] = f32_to_bf8(v);
-                }
+                for (int pg = 0; pg < NPG; ++pg) fb[pg] = lazy8(fb[pg], sc, sh, alo, ahi);
             }
             bf16x8 fa[4];
 #pragma unroll
@@ -142,7 +135,7 @@ __global__ __launch_bounds__(256, 3) void alg_stream_kernel(S1P p) {
             __builtin_amdgcn_sched_barrier(0);
         }
         // ---- epilogue: lane (li, lg) holds channels ct*16 + lg*4 .. +3 of pixel pg*16 + li
-        const float blo = uniform(act_lo(p.bn_act)), bhi = uniform(act_hi(p.bn_act));
+        const float blo = wave_uniform(act_lo(p.bn_act)), bhi = wave_uniform(act_hi(p.bn_act));
 #pragma unroll
         for (int pg = 0; pg < NPG; ++pg) {
             const long px = p0 + pg * 16 + li;
@@ -215,9 +208,7 @@ int adamml_alg_stream_launch(const adamml_conv_desc_t* d, const void* g, const v
     if (p.P <= 0) return ADAMML_OK;
     const int groups = d->groups < 1 ? 1 : d->groups;
     const long ntile = (p.P + TPX - 1) / TPX;
-    long nblk = (ntile + 3) / 4;
-    const long cap = 768 / groups > 0 ? 768 / groups : 1;           // ~3 persistent workgroups per CU over all groups
-    if (nblk > cap) nblk = cap;
+    const int nblk = persistent_blocks((ntile + 3) / 4, groups, 3);  // ~3 persistent workgroups per CU over all groups
     hipLaunchKernelGGL(alg_stream_kernel, dim3((unsigned)nblk, groups), dim3(256), 0, stream, p);
     return adamml_check_launch("conv_bwd_data_alg (stream)");
 }

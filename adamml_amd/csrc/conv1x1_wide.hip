@@ -33,19 +33,9 @@
 #include <stdlib.h>
 #include "common.h"
 #include "conv_internal.h"
-#include "../../include/adamml_hip.h"
+#include "waveslice.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) short s16x4_;
-
-template <int N, class F>
-__device__ __forceinline__ void static_for_k(F&& f) {
-    if constexpr (N > 0) {
-        static_for_k<N - 1>(f);
-        f(std::integral_constant<int, N - 1>{});
-    }
-}
 
 struct WXP {
     const bf16_t* x;         // [groups][Pin][K]   activations (forward) or output gradient (data gradient)
@@ -98,8 +88,7 @@ __global__ __launch_bounds__(512, 1) void wide_all_kernel(WXP p) {
         s_vec[i] = (p.in_scale && i < p.K) ? p.in_scale[(size_t)g * p.in_gs + i] : 1.f;
         s_vec[KP + i] = (p.in_scale && i < p.K) ? p.in_shift[(size_t)g * p.in_gs + i] : 0.f;
     }
-    auto uniform = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
-    const float alo = uniform(p.in_scale ? act_lo(p.act) : -INFINITY), ahi = uniform(p.in_scale ? act_hi(p.act) : INFINITY);
+    const float alo = lazy_lo(p.in_scale, p.act), ahi = lazy_hi(p.in_scale, p.act);
     char* stg = s_stage + wave * (TPX * SROW);
     auto in_row = [&](int px) -> size_t {
         if (!S2) return (size_t)px * p.K;
@@ -108,8 +97,8 @@ __global__ __launch_bounds__(512, 1) void wide_all_kernel(WXP p) {
         const int oh = rem / p.OW, ow = rem - oh * p.OW;
         return ((size_t)(n * p.H + 2 * oh) * p.W + 2 * ow) * p.K;
     };
-    union { s16x4_ h[2]; bf16x8 v; } ones;
-    ones.h[0] = s16x4_{0x3F80, 0x3F80, 0x3F80, 0x3F80};
+    union { s16x4 h[2]; bf16x8 v; } ones;
+    ones.h[0] = s16x4{0x3F80, 0x3F80, 0x3F80, 0x3F80};
     ones.h[1] = ones.h[0];
     const int trow = 8 * lg + (li >> 2);
     // weight slab loads of this thread: chunk e = tid + 512 j of the slab's SLAB x KP x 2 contiguous bytes
@@ -205,7 +194,7 @@ __global__ __launch_bounds__(512, 1) void wide_all_kernel(WXP p) {
         bf16x8 fa[2][NCT];
 #pragma unroll
         for (int ct = 0; ct < NCT; ++ct) fa[0][ct] = *reinterpret_cast<const bf16x8*>(wb + (ct * 16 + li) * WROW + ((lg ^ li) << 4));
-        static_for_k<KS>([&](auto kc) {
+        static_for<KS>([&](auto kc) {
             constexpr int k = decltype(kc)::value;
             if constexpr (k + 1 < KS) {
 #pragma unroll
@@ -246,19 +235,15 @@ __global__ __launch_bounds__(512, 1) void wide_all_kernel(WXP p) {
             // all fragment reads first, then all MFMAs, then UNCONDITIONAL slot writes (a lane without a valid element writes to its own sink
             // entry): under exec-masked branches every 16-channel block was its own chain of LDS read -> MFMA -> LDS write latencies
             // (phase probe: 1 900 - 2 200 of the 7 000 cycles of a slab step went to staging + statistics)
-            union { s16x4_ h[2]; bf16x8 v; } fr[NCT];
+            bf16x8 fr[NCT];
 #pragma unroll
-            for (int cb = 0; cb < NCT; ++cb) {
-                const char* fp = stg + trow * SROW + (cb * 16 + 4 * (li & 3)) * 2;
-                fr[cb].h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_*)(fp));
-                fr[cb].h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_*)(fp + 4 * SROW));
-            }
+            for (int cb = 0; cb < NCT; ++cb) fr[cb] = tr_frag(stg, SROW, cb, trow, li);
             f32x4 dsum[NCT], dsq[NCT];
             const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int cb = 0; cb < NCT; ++cb) {
-                dsum[cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones.v, fr[cb].v, z4, 0, 0, 0);
-                dsq[cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fr[cb].v, fr[cb].v, z4, 0, 0, 0);
+                dsum[cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones.v, fr[cb], z4, 0, 0, 0);
+                dsq[cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fr[cb], fr[cb], z4, 0, 0, 0);
             }
             // D rows = lg * 4 + r, column = li: row 0 of dsum (lanes lg == 0) holds the column sums, the diagonal of dsq sits in the lanes
             // with li >> 2 == lg
@@ -290,11 +275,9 @@ __global__ __launch_bounds__(512, 1) void wide_all_kernel(WXP p) {
                 const int e = lane + 64 * i;
                 const int px = e / CPR, ch = e - px * CPR;
                 if (FULL || px < npx) {
-                    union { struct { s16x4_ a, b; } s; bf16x8 v; } o;
-                    o.s.a = *reinterpret_cast<const s16x4_*>(stg + px * SROW + ch * 16);
-                    o.s.b = *reinterpret_cast<const s16x4_*>(stg + px * SROW + ch * 16 + 8);
-                    if (EPI == 2) o.v = f32_to_bf8(bf8_to_f32(o.v) + bf8_to_f32(old[i]));
-                    *reinterpret_cast<bf16x8*>(ys + (size_t)px * p.N + ch * 8) = o.v;
+                    bf16x8 o = unstage8(stg + px * SROW + ch * 16);
+                    if (EPI == 2) o = f32_to_bf8(bf8_to_f32(o) + bf8_to_f32(old[i]));
+                    *reinterpret_cast<bf16x8*>(ys + (size_t)px * p.N + ch * 8) = o;
                 }
             }
         }
@@ -314,12 +297,7 @@ __global__ __launch_bounds__(512, 1) void wide_all_kernel(WXP p) {
             for (int k = 0; k < KS; ++k) {
                 const f32x8 sc = load_f32x8(s_vec + k * 32 + lg * 8), sh = load_f32x8(s_vec + KP + k * 32 + lg * 8);
 #pragma unroll
-                for (int pg = 0; pg < NPG; ++pg) {
-                    f32x8 v = bf8_to_f32(bfr[k][pg]);
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) v[i] = clamp_act(fmaf(v[i], sc[i], sh[i]), alo, ahi);
-                    bfr[k][pg] = f32_to_bf8(v);
-                }
+                for (int pg = 0; pg < NPG; ++pg) bfr[k][pg] = lazy8(bfr[k][pg], sc, sh, alo, ahi);
             }
         }
         for (int sl = 0; sl + 1 < nslab; ++sl) slab_step(ts, sl, npx, yb, full_c, std::false_type{});
@@ -360,18 +338,11 @@ int wide_all_launch(WXP& p, int groups, hipStream_t stream) {
     constexpr size_t lds = (size_t)2 * SLAB * (KP * 2) + 2 * KP * 4 + 2 * 2048 * 4 + 2 * 8 * (2 * SLAB + 64) * 4 + (size_t)8 * 32 * (SLAB * 2 + 8);
     static_assert(lds <= 160 * 1024, "wide_all: LDS budget");
     static AdamLdsOnce attr_once;                    // (per device: common.h)
-    const int attr_dev = adamml_current_device();
-    if (!attr_once.test(attr_dev)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wide_all_kernel<KS, EPI, LAZY, S2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return adamml_set_error(ADAMML_ELAUNCH, "conv1x1 (wide): cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
-        attr_once.set(attr_dev);
-    }
+    if (int rc = adamml_raise_lds_limit(attr_once, reinterpret_cast<const void*>(wide_all_kernel<KS, EPI, LAZY, S2>), lds, "conv1x1 (wide)")) return rc;
     p.nslab = p.N / SLAB;
     p.rpg = groups;
     const long ntile = (p.P + 31) / 32, nset = (ntile + 7) / 8;
-    long wpg = 256 / groups;                                 // workgroups per BatchNorm group: one per CU over all groups
-    if (wpg < 1) wpg = 1;
-    if (wpg > nset) wpg = nset;
+    const int wpg = persistent_blocks(nset, groups, 1);      // workgroups per BatchNorm group: one per CU over all groups
     hipLaunchKernelGGL((wide_all_kernel<KS, EPI, LAZY, S2>), dim3((unsigned)(groups * wpg)), dim3(512), lds, stream, p);
     return adamml_check_launch("conv1x1 (wide, all slabs)");
 }

@@ -762,15 +762,10 @@ static int c3_launch(const adamml_conv_desc_t* d, C3P& p, bool res, hipStream_t 
     p.tpb = ceil_div(p.total_tiles, 1024);
     const size_t patch = (size_t)p.PR * p.PW * PITCH3, stage = (size_t)p.npt * 16 * SROW3;
     const size_t lds = C64 * WROW3 + CS3_BYTES + (patch > stage ? patch : stage);
-    static AdamLdsOnce attr_once;                    // (per device: common.h)
-    const int attr_dev = adamml_current_device();
-    if (!attr_once.test(attr_dev)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_c64_kernel<false, PITCH3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_c64_kernel<true, PITCH3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_c64_kernel<false, PITCH3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return adamml_set_error(ADAMML_ELAUNCH, "conv3x3_c64: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
-        attr_once.set(attr_dev);
-    }
+    static AdamLdsOnce once_res, once_bn, once_plain;     // (per device and instance: common.h)
+    const void* kernel = res ? reinterpret_cast<const void*>(conv3x3_c64_kernel<false, PITCH3, true>)
+                       : p.bn_z ? reinterpret_cast<const void*>(conv3x3_c64_kernel<true, PITCH3>) : reinterpret_cast<const void*>(conv3x3_c64_kernel<false, PITCH3>);
+    if (int rc = adamml_raise_lds_limit(res ? once_res : p.bn_z ? once_bn : once_plain, kernel, 160 * 1024, "conv3x3_c64")) return rc;
     const dim3 grid(ceil_div(p.total_tiles, p.tpb));
     if (res) hipLaunchKernelGGL((conv3x3_c64_kernel<false, PITCH3, true>), grid, dim3(NT3), C64_LDS(lds), stream, p);
     else if (p.bn_z) hipLaunchKernelGGL((conv3x3_c64_kernel<true, PITCH3>), grid, dim3(NT3), C64_LDS(lds), stream, p);
@@ -861,12 +856,7 @@ int adamml_conv3x3_c64_wgrad_launch(const adamml_conv_desc_t* d, const void* dz,
     const int nblk = adamml_conv3x3_c64_wgrad_blocks(d, &p.tpb);
     const size_t lds = (size_t)p.PR * p.PW * PPIX + (size_t)MAXPX3 * SROW3 + MAXPX3 * sizeof(int);
     static AdamLdsOnce attr_once;                    // (per device: common.h)
-    const int attr_dev = adamml_current_device();
-    if (!attr_once.test(attr_dev)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_c64_wgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return adamml_set_error(ADAMML_ELAUNCH, "conv3x3_c64 wgrad: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
-        attr_once.set(attr_dev);
-    }
+    if (int rc = adamml_raise_lds_limit(attr_once, reinterpret_cast<const void*>(conv3x3_c64_wgrad_kernel), 160 * 1024, "conv3x3_c64 wgrad")) return rc;
     hipLaunchKernelGGL(conv3x3_c64_wgrad_kernel, dim3(nblk, (p.cp >> 6) * (p.cp >> 6)), dim3(NT3), C64_LDS(lds), stream, p);
     return adamml_check_launch("conv3x3_c64 wgrad");
 }

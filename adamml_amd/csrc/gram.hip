@@ -15,7 +15,7 @@
 // a workspace with plain stores ([group][split][C*C + C]) and are summed in a fixed order by gram_reduce_kernel, so the
 // result does not depend on the arrival order (deterministic mode needs no special path).
 #include "common.h"
-#include "tile.h"      // NTHREADS, static_for, tr_swz: the transpose-read image of conv_wgrad_kernel
+#include "tile.h"      // NTHREADS, tr_swz: the transpose-read image of conv_wgrad_kernel (static_for: common.h)
 #include "../../include/adamml_hip.h"
 
 namespace {

@@ -14,12 +14,10 @@
 // requested, unconditionally and clamped, between the stores and the product.  g' is bit-identical to the tile kernel's.
 #include "common.h"
 #include "conv_internal.h"
-#include "../../include/adamml_hip.h"
+#include "waveslice.h"
 #include <type_traits>
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) short s16x4_;
 
 struct RPS {
     const bf16_t* dz;        // [groups][P][64] gradient of conv1's raw output
@@ -59,18 +57,13 @@ __global__ __launch_bounds__(NQ * 64, NQ == 4 ? 2 : 1) void res_prod_stream_kern
         if (SECOND) { p.zb += pp * C + q * 64; p.vecb += (size_t)g * 4 * C; p.sums_b += (size_t)g * ADAMML_STAT_SLOTS * 2 * C; }
         p.sums += (size_t)g * ADAMML_STAT_SLOTS * 2 * C;
     }
-    if (PF)
-        for (int i = tid; i < CIN; i += NQ * 64) {
-            s_vec[i] = p.in_scale ? p.in_scale[(size_t)g * p.in_gs + i] : 1.f;
-            s_vec[CIN + i] = p.in_scale ? p.in_shift[(size_t)g * p.in_gs + i] : 0.f;
-        }
+    if (PF) fill_lazy_vec(s_vec, CIN, p, g, tid, NQ * 64);
     constexpr int WAREA = TPX * (ZROW + (PF ? XROW : 0));
     char* zs = s_stage + q * WAREA;
     char* xs = zs + TPX * ZROW;
     for (int i = lane; i < WAREA / 8; i += 64) reinterpret_cast<unsigned long long*>(zs)[i] = 0ull;
     __syncthreads();
-    auto uniform = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
-    const float alo = uniform(p.in_scale ? act_lo(p.act) : -INFINITY), ahi = uniform(p.in_scale ? act_hi(p.act) : INFINITY);
+    const float alo = lazy_lo(p.in_scale, p.act), ahi = lazy_hi(p.in_scale, p.act);
     const bool lazy = PF && p.in_scale != nullptr;
     // ---- this wave's weight slice: A fragments (row = gradient channel 64 q + 16 ct + li, k = 32 ks + 8 lg ..)
     bf16x8 wr[4][KS];
@@ -122,13 +115,6 @@ __global__ __launch_bounds__(NQ * 64, NQ == 4 ? 2 : 1) void res_prod_stream_kern
         }
     };
     const int trow = 8 * lg + (li >> 2);
-    auto frag = [&](const char* base, int row_bytes, int blk) {
-        const char* qq = base + trow * row_bytes + (blk * 16 + 4 * (li & 3)) * 2;
-        union { s16x4_ h[2]; bf16x8 v; } f;
-        f.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_*)(qq));
-        f.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_*)(qq + 4 * row_bytes));
-        return f.v;
-    };
     issue((int)blockIdx.x < ntile ? (int)blockIdx.x : ntile - 1);
     // one tile; FULL (a compile-time flag: 32 pixels) keeps the stores unconditional -- a store under a per-lane condition makes every
     // wait behind it a conservative one
@@ -150,11 +136,7 @@ __global__ __launch_bounds__(NQ * 64, NQ == 4 ? 2 : 1) void res_prod_stream_kern
 #pragma unroll
         for (int pg = 0; pg < 2; ++pg)
 #pragma unroll
-            for (int ct = 0; ct < 4; ++ct) {
-                union { bf16x4 b; s16x4_ s; } u;
-                u.b = f32_to_bf4(c[pg][ct]);
-                *reinterpret_cast<s16x4_*>(zs + (pg * 16 + li) * ZROW + (ct * 16 + lg * 4) * 2) = u.s;
-            }
+            for (int ct = 0; ct < 4; ++ct) *reinterpret_cast<bf16x4*>(zs + (pg * 16 + li) * ZROW + (ct * 16 + lg * 4) * 2) = f32_to_bf4(c[pg][ct]);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                   // (own LDS writes landed; no other wave touches this area)
         // ---- epilogue: + identity gradient, mask, store, sum; g' back into the area; the a rows beside it
         char* ob = reinterpret_cast<char*>(p.dx + (size_t)p0 * C);
@@ -162,10 +144,7 @@ __global__ __launch_bounds__(NQ * 64, NQ == 4 ? 2 : 1) void res_prod_stream_kern
         for (int i = 0; i < 4; ++i) {
             const int px = zpx + 8 * i;
             char* zp = zs + px * ZROW + zch * 16;
-            union { struct { s16x4_ a, b; } s; bf16x8 v; } u;
-            u.s.a = *reinterpret_cast<const s16x4_*>(zp);
-            u.s.b = *reinterpret_cast<const s16x4_*>(zp + 8);
-            f32x8 f = bf8_to_f32(u.v) + bf8_to_f32(old[i]);
+            f32x8 f = bf8_to_f32(unstage8(zp)) + bf8_to_f32(old[i]);
 #pragma unroll
             for (int j = 0; j < 8; ++j) f[j] = (mb[i] >> j) & 1u ? f[j] : 0.f;
             bf16x8 v = f32_to_bf8(f);
@@ -180,45 +159,22 @@ __global__ __launch_bounds__(NQ * 64, NQ == 4 ? 2 : 1) void res_prod_stream_kern
 #pragma unroll
                 for (int j = 0; j < 8; ++j) sb[j] += gq[j] * (z2[j] - mu2[j]) * is2[j];
             }
-            if constexpr (PF) {
-                u.v = v;
-                *reinterpret_cast<s16x4_*>(zp) = u.s.a;
-                *reinterpret_cast<s16x4_*>(zp + 8) = u.s.b;
-            }
+            if constexpr (PF) stage8(zp, v);
         }
         if constexpr (PF) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int px = zpx + 8 * i;
             bf16x8 v = ra[i];
-            if (lazy) {
-                const f32x8 sc = load_f32x8(s_vec + zch * 8), sh = load_f32x8(s_vec + CIN + zch * 8);
-                f32x8 f = bf8_to_f32(v);
-#pragma unroll
-                for (int k = 0; k < 8; ++k) f[k] = clamp_act(fmaf(f[k], sc[k], sh[k]), alo, ahi);
-                v = f32_to_bf8(f);
-            }
-            union { struct { s16x4_ a, b; } s; bf16x8 v; } u;
-            u.v = FULL || px < npx ? v : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-            *reinterpret_cast<s16x4_*>(xs + px * XROW + zch * 16) = u.s.a;
-            *reinterpret_cast<s16x4_*>(xs + px * XROW + zch * 16 + 8) = u.s.b;
+            if (lazy) v = lazy8(v, load_f32x8(s_vec + zch * 8), load_f32x8(s_vec + CIN + zch * 8), alo, ahi);
+            stage8(xs + px * XROW + zch * 16, FULL || px < npx ? v : bf16x8{0, 0, 0, 0, 0, 0, 0, 0});
         }
         }
         // (unconditional request of the workgroup's next tile; past the end: this tile again, unused)
         issue(tile + (int)gridDim.x < ntile ? tile + (int)gridDim.x : tile);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         // ---- product: P[slice][:] += g'^T a over the tile's 32 pixels
-        if constexpr (PF) {
-            bf16x8 fb[4];
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) fb[nt] = frag(xs, XROW, nt);
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) {
-                const bf16x8 fa = frag(zs, ZROW, mt);
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, fb[nt], acc[mt][nt], 0, 0, 0);
-            }
-        }
+        if constexpr (PF) staged_outer_product<4, 4>(acc, zs, ZROW, xs, XROW, trow, li);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                   // (the transpose reads are done before the next tile overwrites the area)
     };
     {
@@ -241,29 +197,17 @@ __global__ __launch_bounds__(NQ * 64, NQ == 4 ? 2 : 1) void res_prod_stream_kern
     // ---- sum(g'): the eight lanes that share a chunk (lane % 8) fold their pixels, one exact publication per channel and wave
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        float v = sa[j];
-        v += __shfl_xor(v, 8, 64);
-        v += __shfl_xor(v, 16, 64);
-        v += __shfl_xor(v, 32, 64);
+        const float v = chunk_lane_fold(sa[j]);
         if (lane < 8 && v != 0.f) stat_publish(p.sums + q * 64 + lane * 8 + j, 2 * C, blockIdx.x & (ADAMML_STAT_SLOTS - 1), v);
         if constexpr (SECOND) {
             if (lane < 8 && v != 0.f) stat_publish(p.sums_b + q * 64 + lane * 8 + j, 2 * C, blockIdx.x & (ADAMML_STAT_SLOTS - 1), v);
-            float v2 = sb[j];
-            v2 += __shfl_xor(v2, 8, 64);
-            v2 += __shfl_xor(v2, 16, 64);
-            v2 += __shfl_xor(v2, 32, 64);
+            const float v2 = chunk_lane_fold(sb[j]);
             if (lane < 8 && v2 != 0.f) stat_publish(p.sums_b + C + q * 64 + lane * 8 + j, 2 * C, blockIdx.x & (ADAMML_STAT_SLOTS - 1), v2);
         }
     }
 }
 
-int rps_blocks(long P, int groups, int per_cu) {
-    const long ntile = (P + TPX - 1) / TPX;
-    constexpr long CUS = 256;
-    long cap = CUS * per_cu / (groups < 1 ? 1 : groups);
-    if (cap < 1) cap = 1;
-    return (int)(ntile < cap ? ntile : cap);
-}
+long rps_tiles(long P) { return (P + TPX - 1) / TPX; }
 
 bool rps_on() { const char* e = getenv("ADAMML_RES_PROD_STREAM"); return !(e && atoi(e) == 0); }                 // test hook, read at every call
 
@@ -280,7 +224,7 @@ int adamml_res_prod_stream_supported(const adamml_conv_desc_t* d, int a_channels
 
 size_t adamml_res_prod_stream_workspace(const adamml_conv_desc_t* d) {
     const int groups = d->groups < 1 ? 1 : d->groups;
-    return (size_t)groups * rps_blocks((long)d->N * d->OH * d->OW, groups, 2) * 256 * CIN * sizeof(float);
+    return (size_t)groups * persistent_blocks(rps_tiles((long)d->N * d->OH * d->OW), groups, 2) * 256 * CIN * sizeof(float);
 }
 
 int adamml_res_prod_stream_launch(const adamml_conv_desc_t* d, const void* dz, const void* w_dgrad_packed, void* dx, const uint8_t* res_mask,
@@ -289,7 +233,7 @@ int adamml_res_prod_stream_launch(const adamml_conv_desc_t* d, const void* dz, c
     constexpr int C = 256;
     const int groups = d->groups < 1 ? 1 : d->groups;
     const long P = (long)d->N * d->OH * d->OW;
-    const int nblk = rps_blocks(P, groups, 2);
+    const int nblk = persistent_blocks(rps_tiles(P), groups, 2);
     if (!workspace || workspace_bytes < (size_t)groups * nblk * C * CIN * sizeof(float))
         return adamml_set_error(ADAMML_EINVAL, "conv_bwd_data_res_prod: workspace too small (adamml_conv_bwd_data_res_prod_workspace)");
     RPS p;
@@ -320,7 +264,7 @@ int adamml_res_stream_launch(const adamml_conv_desc_t* d, const void* dz, const 
     p.a = nullptr; p.in_scale = nullptr; p.in_shift = nullptr; p.ws = nullptr; p.in_gs = 0; p.act = 0; p.P = (int)P;
     p.zb = (const bf16_t*)z_b; p.vecb = vec_b; p.sums_b = sums_b;
     constexpr size_t lds = 2 * CIN * 4 + (size_t)8 * TPX * ZROW;
-    const dim3 grid((unsigned)rps_blocks(P, groups, 1), groups);
+    const dim3 grid((unsigned)persistent_blocks(rps_tiles(P), groups, 1), groups);
     if (z_b) hipLaunchKernelGGL((res_prod_stream_kernel<8, 128, false, true>), grid, dim3(512), lds, stream, p);
     else hipLaunchKernelGGL((res_prod_stream_kernel<8, 128, false, false>), grid, dim3(512), lds, stream, p);
     return adamml_check_launch("conv_bwd_data_res(stream)");

@@ -3,19 +3,10 @@
 // between translation units and every file that includes this header gets its own copy.
 #pragma once
 #include "common.h"
-#include <type_traits>
 
 namespace {
 
 constexpr int NTHREADS = 256;
-
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (N > 0) {
-        static_for<N - 1>(f);
-        f(std::integral_constant<int, N - 1>{});
-    }
-}
 
 // LDS image of one K step: [32 pixels][CH channels] bf16, row-major, 8-byte units XOR-swizzled so that the
 // ds_read_b64_tr_b16 of a 32-lane service group (rows {r..r+3} U {r+8..r+11}) touches 64 distinct banks.

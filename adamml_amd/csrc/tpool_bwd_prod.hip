@@ -12,11 +12,9 @@
 #include <type_traits>
 #include "common.h"
 #include "conv_internal.h"
-#include "../../include/adamml_hip.h"
+#include "waveslice.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) short s16x4_;
 
 struct TPP {
     const bf16_t* gy;        // [groups][clips * T/2][HW][C]
@@ -51,16 +49,12 @@ __global__ __launch_bounds__(NQ * 64, NQ == 4 ? 2 : 1) void tpool_bwd_prod_kerne
         p.a += (size_t)g * p.clips * T * p.HW * CIN;
         p.sums += (size_t)g * ADAMML_STAT_SLOTS * 2 * C;
     }
-    for (int i = tid; i < CIN; i += NQ * 64) {
-        s_vec[i] = p.in_scale ? p.in_scale[(size_t)g * p.in_gs + i] : 1.f;
-        s_vec[CIN + i] = p.in_scale ? p.in_shift[(size_t)g * p.in_gs + i] : 0.f;
-    }
+    fill_lazy_vec(s_vec, CIN, p, g, tid, NQ * 64);
     char* zs = s_stage + q * (TPX * (ZROW + XROW));
     char* xs = zs + TPX * ZROW;
     for (int i = lane; i < TPX * (ZROW + XROW) / 8; i += 64) reinterpret_cast<unsigned long long*>(zs)[i] = 0ull;
     __syncthreads();
-    auto uniform = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
-    const float alo = uniform(p.in_scale ? act_lo(p.act) : -INFINITY), ahi = uniform(p.in_scale ? act_hi(p.act) : INFINITY);
+    const float alo = lazy_lo(p.in_scale, p.act), ahi = lazy_hi(p.in_scale, p.act);
     const bool lazy = p.in_scale != nullptr;
     f32x4 acc[MT][NTL];
 #pragma unroll
@@ -92,13 +86,6 @@ __global__ __launch_bounds__(NQ * 64, NQ == 4 ? 2 : 1) void tpool_bwd_prod_kerne
         }
     };
     const int trow = 8 * lg + (li >> 2);
-    auto frag = [&](const char* base, int row_bytes, int blk) {
-        const char* qq = base + trow * row_bytes + (blk * 16 + 4 * (li & 3)) * 2;
-        union { s16x4_ h[2]; bf16x8 v; } f;
-        f.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_*)(qq));
-        f.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_*)(qq + 4 * row_bytes));
-        return f.v;
-    };
     {
         const long t0 = blockIdx.x < ntask ? blockIdx.x : ntask - 1;
         issue_a(t0, 0);
@@ -153,27 +140,15 @@ __global__ __launch_bounds__(NQ * 64, NQ == 4 ? 2 : 1) void tpool_bwd_prod_kerne
                 const f32x8 gq = bf8_to_f32(gb);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) sa[j] += gq[j];
-                union { struct { s16x4_ a, b; } s; bf16x8 v; } u;
-                u.v = gb;
-                *reinterpret_cast<s16x4_*>(zs + (r0 + px) * ZROW + zch * 16) = u.s.a;
-                *reinterpret_cast<s16x4_*>(zs + (r0 + px) * ZROW + zch * 16 + 8) = u.s.b;
+                stage8(zs + (r0 + px) * ZROW + zch * 16, gb);
             }
             // the a rows of frame t (lazy transform on the way), rows past the end zero
 #pragma unroll
             for (int i = 0; i < NX; ++i) {
                 const int e = lane + 64 * i, px = e / XC, ch = e - px * XC;
                 bf16x8 v = ra[i];
-                if (lazy) {
-                    const f32x8 sc = load_f32x8(s_vec + ch * 8), sh = load_f32x8(s_vec + CIN + ch * 8);
-                    f32x8 f = bf8_to_f32(v);
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) f[k] = clamp_act(fmaf(f[k], sc[k], sh[k]), alo, ahi);
-                    v = f32_to_bf8(f);
-                }
-                union { struct { s16x4_ a, b; } s; bf16x8 v; } u;
-                u.v = FULL || px < npx ? v : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-                *reinterpret_cast<s16x4_*>(xs + (r0 + px) * XROW + ch * 16) = u.s.a;
-                *reinterpret_cast<s16x4_*>(xs + (r0 + px) * XROW + ch * 16 + 8) = u.s.b;
+                if (lazy) v = lazy8(v, load_f32x8(s_vec + ch * 8), load_f32x8(s_vec + CIN + ch * 8), alo, ahi);
+                stage8(xs + (r0 + px) * XROW + ch * 16, FULL || px < npx ? v : bf16x8{0, 0, 0, 0, 0, 0, 0, 0});
             }
         };
         load_win(0, cur);
@@ -192,27 +167,7 @@ __global__ __launch_bounds__(NQ * 64, NQ == 4 ? 2 : 1) void tpool_bwd_prod_kerne
             cur = nxt;
             load_win(to + 2, nxt);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");               // (own LDS writes landed; no other wave touches this area)
-            if constexpr (NTL <= MT) {
-                bf16x8 fb[NTL];
-#pragma unroll
-                for (int nt = 0; nt < NTL; ++nt) fb[nt] = frag(xs, XROW, nt);
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) {
-                    const bf16x8 fa = frag(zs, ZROW, mt);
-#pragma unroll
-                    for (int nt = 0; nt < NTL; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, fb[nt], acc[mt][nt], 0, 0, 0);
-                }
-            } else {
-                bf16x8 fa[MT];
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) fa[mt] = frag(zs, ZROW, mt);
-#pragma unroll
-                for (int nt = 0; nt < NTL; ++nt) {
-                    const bf16x8 fb = frag(xs, XROW, nt);
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[mt], fb, acc[mt][nt], 0, 0, 0);
-                }
-            }
+            staged_outer_product<MT, NTL>(acc, zs, ZROW, xs, XROW, trow, li);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");               // (the transpose reads are done before the next window overwrites the area)
         }
     };
@@ -230,10 +185,7 @@ __global__ __launch_bounds__(NQ * 64, NQ == 4 ? 2 : 1) void tpool_bwd_prod_kerne
     // ---- sum(g2): the eight lanes that share a chunk (lane % 8) fold their pixels, one exact publication per channel and wave
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        float v = sa[j];
-        v += __shfl_xor(v, 8, 64);
-        v += __shfl_xor(v, 16, 64);
-        v += __shfl_xor(v, 32, 64);
+        const float v = chunk_lane_fold(sa[j]);
         if (lane < 8 && v != 0.f) stat_publish(p.sums + q * 64 + lane * 8 + j, 2 * C, blockIdx.x & (ADAMML_STAT_SLOTS - 1), v);
     }
 }
@@ -242,26 +194,13 @@ template <int T, int CIN, int NQ, bool ALLFULL>
 int tpp_launch(const TPP& p, int groups, int nblk, hipStream_t stream) {
     constexpr size_t lds = 2 * CIN * 4 + (size_t)NQ * 32 * ((64 * 2 + 8) + (CIN * 2 + 8));
     static AdamLdsOnce attr_once;                    // (per device: common.h)
-    const int attr_dev = adamml_current_device();
-    if (!attr_once.test(attr_dev)) {
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(tpool_bwd_prod_kernel<T, CIN, NQ, ALLFULL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return adamml_set_error(ADAMML_ELAUNCH, "temporal_pool_bwd_code_prod: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
-        }
-        attr_once.set(attr_dev);
-    }
+    if (int rc = adamml_raise_lds_limit(attr_once, reinterpret_cast<const void*>(tpool_bwd_prod_kernel<T, CIN, NQ, ALLFULL>), lds, "temporal_pool_bwd_code_prod")) return rc;
     hipLaunchKernelGGL((tpool_bwd_prod_kernel<T, CIN, NQ, ALLFULL>), dim3((unsigned)nblk, groups), dim3(NQ * 64), lds, stream, p);
     return adamml_check_launch("temporal_pool_bwd_code_prod");
 }
 
-int tpp_blocks(int NB, int HW, int C, int groups) {
-    const long ntask = (long)NB * ((HW + 15) / 16);
-    // one partial [C][Cin] per workgroup: two workgroups per CU over all groups at C = 256 (four waves each), one at C = 512
-    constexpr long CAP = 512;
-    long cap = (C == 256 ? CAP : CAP / 2) / (groups < 1 ? 1 : groups);
-    if (cap < 1) cap = 1;
-    return (int)(ntask < cap ? ntask : cap);
-}
+// one partial [C][Cin] per workgroup over the (clip, 16-pixel block) tasks: two workgroups per CU over all groups at C = 256 (four waves each), one at C = 512
+int tpp_blocks(int NB, int HW, int C, int groups) { return persistent_blocks((long)NB * ((HW + 15) / 16), groups, C == 256 ? 2 : 1); }
 
 }  // namespace
 

@@ -280,6 +280,62 @@ def test_row_walk_helpers_live_in_one_header():
     assert users >= 3
 
 
+WAVE_SLICE_HELPERS = ("wave_uniform", "lazy_lo", "lazy_hi", "fill_lazy_vec", "lazy8", "stage8", "unstage8", "tr_frag", "staged_outer_product",
+                      "chunk_lane_fold", "persistent_blocks")
+
+
+def wave_slice_hits(csrc):
+    """What test_wave_slice_helpers_live_in_one_header counts in a csrc directory: (copies, missing includes, files that use a helper)"""
+    import glob
+    strip = lambda src: re.sub(r"//[^\n]*|/\*.*?\*/", " ", src, flags=re.S)
+    define = r"\b(?:float|void|bf16x8|int)\s+(%s)\s*\(" % "|".join(WAVE_SLICE_HELPERS)
+    # the idioms the helpers replace, under the names their copies had: the readfirstlane lambda, the private short-vector typedef, the
+    # transpose-read lambda frag(base, row_bytes, blk), the private static_for, the per-file grid helpers
+    idiom = (r"\bauto\s+uniform\s*=\s*\[|\btypedef\b[^;]*\bs16x4_\s*;|\bauto\s+frag\s*=\s*\[[^\]]*\]\s*\(\s*const\s+char\s*\*\s*base\b|"
+             r"\bvoid\s+static_for_k\s*\(|\bint\s+(?:rps|fs)_blocks\s*\(")
+    copies, missing, users = [], [], 0
+    for path in sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h"))):
+        src = open(path).read()
+        code, name = strip(src), os.path.basename(path)
+        # (the one place the attribute may be named: adamml_raise_lds_limit in common.h)
+        attr = len(re.findall(r"\bhipFuncAttributeMaxDynamicSharedMemorySize\b", code))
+        if name == "common.h":
+            body = re.search(r"\bint\s+adamml_raise_lds_limit\s*\([^)]*\)\s*\{(.*?)\n\}", code, flags=re.S)
+            attr -= len(re.findall(r"\bhipFuncAttributeMaxDynamicSharedMemorySize\b", body.group(1))) if body else 0
+        copies += [(name, "hipFuncAttributeMaxDynamicSharedMemorySize")] * attr
+        if name == "waveslice.h" or not name.endswith(".hip"):
+            continue
+        copies += [(name, m.group(0).split("(")[0].strip()) for m in re.finditer(define, code)]
+        copies += [(name, " ".join(m.group(0).split())[:40]) for m in re.finditer(idiom, code, flags=re.S)]
+        if re.search(r"\b(%s)\s*[<(]" % "|".join(WAVE_SLICE_HELPERS), code):
+            users += 1
+            if not re.search(r'^#include "waveslice\.h"', src, flags=re.M):
+                missing.append(name)
+    return copies, missing, users
+
+
+def test_wave_slice_helpers_live_in_one_header():
+    """The idioms of the barrier-free wave-slice streaming kernels -- wave-uniform clamp bounds, the lazy-operand fill and transform, the
+    8-byte staging accesses, the transpose-read fragment and the outer product over two staged tiles, the chunk-lane fold, the persistent
+    grid -- are defined in csrc/waveslice.h and in no csrc/*.hip (these kernels promise the tile kernels' bits through "same rounding
+    points, same epilogue expression": a copy that drifts breaks that unnoticed); no .hip keeps one of the old copies (a `uniform`
+    readfirstlane lambda, an s16x4_ typedef, a `frag` transpose-read lambda, static_for_k, rps_blocks / fs_blocks);
+    hipFuncAttributeMaxDynamicSharedMemorySize is named in csrc only inside common.h's adamml_raise_lds_limit; every .hip that uses a helper
+    includes the header.  (On the csrc of the commit before the header this finds 33 hits: profiles/r11_bench_parent_vs_waveslice.txt.)"""
+    csrc = os.path.join(ROOT, "adamml_amd", "csrc")
+    strip = lambda src: re.sub(r"//[^\n]*|/\*.*?\*/", " ", src, flags=re.S)
+    header = strip(open(os.path.join(csrc, "waveslice.h")).read())
+    for name in WAVE_SLICE_HELPERS:
+        assert len(re.findall(r"\b(?:float|void|bf16x8|int)\s+%s\s*\(" % name, header)) == 1, name
+    common = strip(open(os.path.join(csrc, "common.h")).read())
+    assert len(re.findall(r"\bint\s+adamml_raise_lds_limit\s*\(", common)) == 1
+    assert len(re.findall(r"\bvoid\s+static_for\s*\(", common)) == 1
+    copies, missing, users = wave_slice_hits(csrc)
+    assert not copies, "wave-slice idioms outside csrc/waveslice.h (or the LDS attribute outside adamml_raise_lds_limit): %s" % copies
+    assert not missing, "files that use a wave-slice helper without including csrc/waveslice.h: %s" % missing
+    assert users >= 7
+
+
 def test_environment_switch_registry_matches_the_code():
     """DESIGN.md appendix B is the complete registry of the ADAMML_* variables the product reads: the names adamml_amd/**/*.py takes from
     os.environ plus the names adamml_amd/csrc/* passes to getenv are exactly its operational and test-hook groups (the infrastructure

@@ -179,6 +179,7 @@ def _patched(log):
             setattr(m, n, call if n == "call" else ptr)
         hip._stream = lambda: 0
         hip._wgrad_ws = {}                      # (a scratch buffer grown by an earlier run would change the workspace sizes passed)
+        hip.next_meta = (0.0, 0.0)              # (the meta an earlier, unprofiled launch of the process left behind would show on the first line)
         ws.__enter__, ws.__exit__ = marker("wgrad_stream_enter", ws.__enter__), marker("wgrad_stream_exit", ws.__exit__)
         yield
     finally:
