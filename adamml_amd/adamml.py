@@ -72,6 +72,11 @@ class AdaMML(nn.Module, MeanStdMixin, StockDDPAware):
                 if m == 'sound' or x_.modality != m:
                     raise ValueError("AdaMML: %s Frames given for the %s modality" % (x_.modality, m))
                 x_ = video.augment(x_)
+            if isinstance(x_, audio.Waveforms):
+                # MI355X extension: the loader's sound windows + missing-track flags -> spectrograms, exactly 0 where the track is missing
+                if m != 'sound':
+                    raise ValueError("AdaMML: Waveforms given for the %s modality" % m)
+                x_ = self._sound_spectrogram(x_)
             hip.require_gpu(x_)
             if m == 'sound':
                 if x_.dim() == 3:
@@ -116,12 +121,16 @@ class AdaMML(nn.Module, MeanStdMixin, StockDDPAware):
         return p_x, m_x, num_segments
 
     def _sound_spectrogram(self, wave):
-        """[B, S, L] fp32 waveforms of round(resampling_rate * audio_length) samples -> [B, S, F, T] spectrograms (load_sound)."""
+        """[B, S, L] fp32 waveforms of round(resampling_rate * audio_length) samples (a tensor or an audio.Waveforms) -> [B, S, F, T]
+        spectrograms (load_sound)."""
         need = int(round(self.resampling_rate * self.audio_length))
         if wave.size(-1) != need:
             raise ValueError("AdaMML: sound waveforms of %d samples, expected round(%g Hz * %g s) = %d"
                              % (wave.size(-1), self.resampling_rate, self.audio_length, need))
-        spec = audio.log_spectrogram(wave, sample_rate=self.resampling_rate)
+        if isinstance(wave, audio.Waveforms):
+            spec = wave.spectrogram(sample_rate=self.resampling_rate)
+        else:
+            spec = audio.log_spectrogram(wave, sample_rate=self.resampling_rate)
         if spec.size(-1) != spec.size(-2):
             raise ValueError("AdaMML: the sound spectrogram is %d x %d; the sound backbones take a square image"
                              % (spec.size(-2), spec.size(-1)))

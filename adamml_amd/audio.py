@@ -5,13 +5,16 @@
 
 `sound_window` is the loader's slicing and tiling; `log_spectrogram` is librosa.stft(n_fft=511, window='hann', win_length,
 hop_length, center=True, pad_mode='constant') followed by log(|X|^2 + eps), computed by the HIP kernel adamml_log_spectrogram.
-AdaMML.forward also takes the sound modality as waveforms [B, S, L] and runs `log_spectrogram` itself."""
+AdaMML.forward also takes the sound modality as waveforms [B, S, L] and runs `log_spectrogram` itself; a loader that
+has to say which clips had no track hands over a `Waveforms` (adamml_amd/data.py)."""
+import copy
+
 import numpy as np
 import torch
 
 from . import hip, runtime
 
-__all__ = ['log_spectrogram', 'sound_window', 'stft_sizes']
+__all__ = ['Waveforms', 'log_spectrogram', 'sound_window', 'stft_sizes']
 
 
 def stft_sizes(sample_rate=24000, window_ms=10, step_ms=5):
@@ -67,3 +70,60 @@ def sound_window(samples, centre_frame, start_frame, fps=29.97, audio_length=1.2
     if out.shape[0] < required:
         out = np.tile(out, int(required / out.shape[0] + 0.5) + 1)
     return np.ascontiguousarray(out[:required], dtype=np.float32)
+
+
+class Waveforms:
+    """A batch of sound windows as a loader hands it over: wave [B, S, L] float32 (`sound_window` of every clip) and missing [B, S]
+    bool, set where the video has no track.  The reference's loader substitutes an all-zero image there, not the log(eps) image of
+    silence (video_dataset.py:102-103), so `spectrogram` sets those images to exactly 0.  A plain class, like video.Frames:
+    DistributedDataParallel's input scatter passes it through as it is."""
+
+    def __init__(self, wave, missing=None):
+        wave = torch.as_tensor(wave)
+        if wave.dim() != 3 or wave.dtype != torch.float32 or wave.shape[-1] < 1:
+            raise ValueError("Waveforms: expected float32 samples [B, S, L], got %s %s" % (wave.dtype, tuple(wave.shape)))
+        missing = torch.zeros(wave.shape[:2], dtype=torch.bool) if missing is None else torch.as_tensor(missing)
+        if missing.dtype != torch.bool or missing.shape != wave.shape[:2]:
+            raise ValueError("Waveforms: expected bool flags %s, got %s %s" % (tuple(wave.shape[:2]), missing.dtype, tuple(missing.shape)))
+        self.wave, self.missing = wave, missing
+        # known on the host, so that `spectrogram` decides without reading the flags back from the GPU
+        self.num_missing = int(missing.sum())
+
+    @property
+    def device(self):
+        return self.wave.device
+
+    @property
+    def shape(self):
+        """Shape of the waveforms: [B, S, L]."""
+        return self.wave.shape
+
+    def size(self, dim=None):
+        return self.shape if dim is None else self.shape[dim]
+
+    def to(self, device, non_blocking=False):
+        out = copy.copy(self)
+        out.wave = self.wave.to(device, non_blocking=non_blocking)
+        out.missing = self.missing.to(device, non_blocking=non_blocking)
+        return out
+
+    def pin_memory(self):
+        out = copy.copy(self)
+        out.wave, out.missing = self.wave.pin_memory(), self.missing.pin_memory()
+        return out
+
+    def spectrogram(self, sample_rate=24000, window_ms=10, step_ms=5, n_fft=511, eps=1e-6):
+        """[B, S, F, T] fp32 on the GPU: `log_spectrogram` of the windows, exactly 0 for the missing clips.  When every clip of the
+        batch is missing the spectrogram kernel is not launched."""
+        hip.require_gpu(self.wave)
+        if self.num_missing == self.missing.numel():
+            _, hop = stft_sizes(sample_rate, window_ms, step_ms)
+            frames = 1 + (self.wave.shape[-1] + 2 * (n_fft // 2) - n_fft) // hop
+            return torch.zeros(*self.wave.shape[:2], n_fft // 2 + 1, frames, dtype=torch.float32, device=self.wave.device)
+        spec = log_spectrogram(self.wave, sample_rate, window_ms, step_ms, n_fft, eps)
+        if self.num_missing:
+            spec.masked_fill_(self.missing[:, :, None, None], 0.0)
+        return spec
+
+    def __repr__(self):
+        return "Waveforms(%s, %d missing, %s)" % (tuple(self.wave.shape), self.num_missing, self.device)

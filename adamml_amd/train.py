@@ -9,10 +9,13 @@ schedules, and the reference's checkpoint dictionary (`state_dict` with the DDP 
 `epoch`, `best_top1`, ...), so checkpoints (weights, optimizer state in torch.optim's
 per-parameter layout, scheduler epoch, stage, temperature) interchange with the reference in both directions.
 
-The dataset / decoding / augmentation pipeline of the reference is out of scope of this repository (SURVEY.md section 8:
-CPU-side I/O): pass your own iterables of `(list_of_modal_tensors, target)` to `main(train_loader=..., val_loader=...)`, name a
-factory with `--loader_factory MODULE:FUNCTION` (called in every rank with (args, rank, world, device); `--datadir`, `-j`, ... are in
-`args`), or use `--synthetic N` (N synthetic batches per epoch, adamml_amd.synth) to exercise the whole schedule.
+The dataset pipeline is a loader factory: name it with `--loader_factory MODULE:FUNCTION` (called in every rank with (args, rank,
+world, device); `--datadir`, `-j`, ... are in `args`) -- `adamml_amd.data:loaders` reads the reference's dataset layout and leaves
+decoding, augmentation and the spectrogram to the GPU -- or pass your own iterables of `(list_of_modal_inputs, target)` to
+`main(train_loader=..., val_loader=...)`, or use `--synthetic N` (N synthetic batches per epoch, adamml_amd.synth) to exercise the
+whole schedule.
+
+    python -m adamml_amd.train ... --dense_sampling --datadir RGB_DIR SOUND_DIR --loader_factory adamml_amd.data:loaders
 
     python -m adamml_amd.train --backbone_net adamml -d 50 --groups 8 --num_segments 5 --modality rgb sound \\
         --causality_modeling lstm --learnable_lf_weights -b 72 --epochs 20 --warmup_epochs 5 --finetune_epochs 10 \\
@@ -496,8 +499,8 @@ def main_worker(gpu, ngpus_per_node, args, train_loader=None, val_loader=None, l
             train_loader = SyntheticLoader(args, args.synthetic, per_rank_batch, device, rank)
             val_loader = SyntheticLoader(args, max(1, args.synthetic // 4), per_rank_batch, device, rank + 7777, args.val_num_clips)
         else:
-            raise SystemExit("no dataset pipeline in this repository (SURVEY.md section 8: CPU-side I/O is out of scope): pass "
-                             "train_loader / val_loader to main(), name a factory with --loader_factory MODULE:FUNCTION, or use "
+            raise SystemExit("no dataset pipeline was named: pass --loader_factory adamml_amd.data:loaders (the reference's dataset layout "
+                             "below --datadir) or another MODULE:FUNCTION, pass train_loader / val_loader to main(), or use "
                              "--synthetic N" + ("; --datadir %s was parsed and is handed to the factory" % args.datadir if args.datadir else ""))
 
     def make_optimizers():
