@@ -462,6 +462,20 @@ class HipBackbone(nn.Module):
         """Shape of the fp32 head output for an input of shape x_shape (fake / meta implementation of adamml::backbone_call)."""
         raise NotImplementedError
 
+    # -- the surface distributed.HipDDP queries on the module it wraps: a bare backbone is wrapped by adamml_amd.train_unimodal ---------
+    def backbones(self):
+        return [self]
+
+    def enable_sync_bn(self, group=None, force=False):
+        """SyncBatchNorm (train_unimodal.py:155-157): this backbone's BN statistic sums are all-reduced over `group`."""
+        from .runtime import SyncCtx
+        self.rt.sync = SyncCtx(group, True, force)
+
+    def flat_grad_buffers(self):
+        """The flat fp32 gradient buffer of this backbone when it owns one (inside AdaMML the enclosing sub-network does)."""
+        fb = self.flat_owner
+        return [fb.flat_grad] if fb is not None and fb.flat_grad is not None else []
+
     # -- launch plans (plan.py) ----------------------------------------------------------------------------------------
     def _plan_key(self, x, groups, need_grad):
         """Everything the launch sequence of a call depends on; None: this call is not plannable."""

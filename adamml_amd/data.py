@@ -411,37 +411,52 @@ class Collate:
     def __init__(self, modality, num_clips, groups, pillow=False):
         self.modality, self.num_clips, self.groups, self.pillow = list(modality), int(num_clips), int(groups), bool(pillow)
 
-    def __call__(self, items):
+    def modal_input(self, items, j):
+        """The batch of modality j of the items: an EncodedFrames, the Pillow-decoded Frames where the GPU decoder refuses a file, or
+        the sound Waveforms."""
         global pillow_fallbacks
         want = self.num_clips * self.groups
-        inputs = []
-        for j, m in enumerate(self.modality):
-            parts = [it['data'][j] for it in items]
-            if m == 'sound':
-                inputs.append(audio.Waveforms(np.stack([p['wave'] for p in parts]), np.stack([p['missing'] for p in parts])))
-                continue
-            for it, p in zip(items, parts):
-                if len(it['indices']) != want or len(p['files']) != want * self.FILES[m]:
-                    raise ValueError("%s: video %d has %d frame indices (%d files), the model takes num_clips x groups = %d x %d = %d "
-                                     "(%d files): uniform sampling ignores num_clips -- the README recipes use --dense_sampling"
-                                     % (m, it['index'], len(it['indices']), len(p['files']), self.num_clips, self.groups, want,
-                                        want * self.FILES[m]))
-            geos = [p['geometry'] for p in parts]
-            encoded = None
-            if not self.pillow:
-                try:
-                    encoded = video.EncodedFrames([p['files'] for p in parts], geos)
-                except jpeg.Unsupported:
-                    pillow_fallbacks += 1
-            inputs.append(encoded or video.Frames([_pillow_video(p['files'], p['names'], m) for p in parts], geos))
+        m = self.modality[j]
+        parts = [it['data'][j] for it in items]
+        if m == 'sound':
+            return audio.Waveforms(np.stack([p['wave'] for p in parts]), np.stack([p['missing'] for p in parts]))
+        for it, p in zip(items, parts):
+            if len(it['indices']) != want or len(p['files']) != want * self.FILES[m]:
+                raise ValueError("%s: video %d has %d frame indices (%d files), the model takes num_clips x groups = %d x %d = %d "
+                                 "(%d files): uniform sampling ignores num_clips -- the README recipes use --dense_sampling"
+                                 % (m, it['index'], len(it['indices']), len(p['files']), self.num_clips, self.groups, want,
+                                    want * self.FILES[m]))
+        geos = [p['geometry'] for p in parts]
+        encoded = None
+        if not self.pillow:
+            try:
+                encoded = video.EncodedFrames([p['files'] for p in parts], geos)
+            except jpeg.Unsupported:
+                pillow_fallbacks += 1
+        return encoded or video.Frames([_pillow_video(p['files'], p['names'], m) for p in parts], geos)
+
+    @staticmethod
+    def targets(items):
         labels = [it['label'] for it in items]
         if torch.is_tensor(labels[0]):
-            target = torch.stack(labels)
-        elif isinstance(labels[0], str):
-            target = labels                                  # test_mode: the video ids
-        else:
-            target = torch.tensor(labels, dtype=torch.long)
-        return inputs, target
+            return torch.stack(labels)
+        if isinstance(labels[0], str):
+            return labels                                    # test_mode: the video ids
+        return torch.tensor(labels, dtype=torch.long)
+
+    def __call__(self, items):
+        return [self.modal_input(items, j) for j in range(len(self.modality))], self.targets(items)
+
+
+class UnimodalCollate(Collate):
+    """Items of a VideoDataSet -> (EncodedFrames | Frames | Waveforms, targets): the one modality as a single object, as the bare
+    backbones take it (train_unimodal.py hands `images` to the model as the loader yields it)."""
+
+    def __init__(self, modality, num_clips, groups, pillow=False):
+        super().__init__([modality], num_clips, groups, pillow)
+
+    def __call__(self, items):
+        return self.modal_input(items, 0), self.targets(items)
 
 
 class Loader:
@@ -467,7 +482,7 @@ class Loader:
         in_workers = self.loader.num_workers > 0 and not getattr(self.loader.collate_fn, 'pillow', False)
         for inputs, target in self.loader:
             if in_workers:
-                pillow_fallbacks += sum(isinstance(x, video.Frames) for x in inputs)
+                pillow_fallbacks += sum(isinstance(x, video.Frames) for x in (inputs if isinstance(inputs, list) else [inputs]))
             yield inputs, target
         if self.rank == 0 and self.log is not None:
             self.log("data: %d batches so far held a JPEG file the GPU decoder does not take and were decoded with Pillow" % pillow_fallbacks)
@@ -499,5 +514,34 @@ def loaders(args, rank, world, device):
             sampler = torch.utils.data.distributed.DistributedSampler(ds, num_replicas=world, rank=rank, shuffle=is_train)
         dl = torch.utils.data.DataLoader(ds, batch_size=batch, shuffle=is_train and sampler is None, sampler=sampler, num_workers=workers,
                                          collate_fn=Collate(modality, num_clips, args.groups), pin_memory=device.type == 'cuda')
+        out.append(Loader(dl, sampler, rank, log))
+    return tuple(out)
+
+
+def unimodal_loaders(args, rank, world, device):
+    """(train_loader, val_loader) of train_unimodal.py:207-256 for `--loader_factory adamml_amd.data:unimodal_loaders` (the unimodal
+    launcher's default with --datadir): ONE modality below ONE root, args.num_clips clips per video in both loaders, and batches
+    whose first element is the modality's object itself, not a list."""
+    modality = args.modality if isinstance(args.modality, str) else args.modality[0]
+    root = args.datadir if isinstance(args.datadir, str) or not args.datadir else args.datadir[0]
+    if not root:
+        raise SystemExit("adamml_amd.data:unimodal_loaders needs --datadir (the root of the one modality)")
+    cfg = DATASETS.get(args.dataset, DATASETS['kinetics-sounds'])
+    device = torch.device(device)
+    batch = max(1, int(args.batch_size / world))
+    workers = min(args.workers, len(os.sched_getaffinity(0)))
+    log = print if rank == 0 else None
+    out = []
+    for is_train, list_file in ((True, cfg['train_list']), (False, cfg['val_list'])):
+        aug = None if modality == 'sound' else video.augmentor_for(args, modality, is_train)
+        ds = VideoDataSet(root, list_file, args.groups, args.frames_per_group, num_clips=args.num_clips, modality=modality,
+                          dense_sampling=args.dense_sampling, image_tmpl=cfg['image_tmpl'], augmentor=aug, is_train=is_train,
+                          separator=cfg['separator'], filter_video=cfg['filter_video'], num_classes=args.num_classes, fps=args.fps,
+                          audio_length=args.audio_length, resampling_rate=args.resampling_rate, log=log)
+        sampler = None
+        if world > 1:
+            sampler = torch.utils.data.distributed.DistributedSampler(ds, num_replicas=world, rank=rank, shuffle=is_train)
+        dl = torch.utils.data.DataLoader(ds, batch_size=batch, shuffle=is_train and sampler is None, sampler=sampler, num_workers=workers,
+                                         collate_fn=UnimodalCollate(modality, args.num_clips, args.groups), pin_memory=device.type == 'cuda')
         out.append(Loader(dl, sampler, rank, log))
     return tuple(out)

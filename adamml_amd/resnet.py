@@ -6,11 +6,11 @@ Mirrors the interface and state_dict of models/resnet.py:116-259 (class ResNet, 
 import torch
 import torch.nn as nn
 
-from . import hip
+from . import hip, video
 from .backbone import HipBackbone, FlatBuffers, StockDDPAware
 from .common import MeanStdMixin
-from .runtime import (Lazy, conv_bn, conv_bn_add, conv_bn_add_supported, conv_bn_add_tpool_supported, add_act, maxpool3x3s2, temporal_pool, head, clip_to_nhwc, pad8,
-                      ACT_NONE, ACT_RELU)
+from .runtime import (Lazy, conv_bn, conv_bn_add, conv_bn_add_supported, conv_bn_add_tpool_supported, add_act, maxpool3x3s2, temporal_pool, head, clip_to_nhwc,
+                      clip_u8_to_nhwc, pad8, ACT_NONE, ACT_RELU)
 
 __all__ = ['ResNet', 'resnet']
 
@@ -65,6 +65,9 @@ class ResNet(HipBackbone, MeanStdMixin, StockDDPAware):
         self.num_classes = num_classes
         self.without_t_stride = without_t_stride
         self.input_channels = input_channels
+        # what a video.Frames input is checked against and normalised with (_forward_frames); the unimodal launcher sets all three
+        self.input_modality = {3: 'rgb', 10: 'flow', 15: 'rgbdiff'}.get(input_channels)
+        self.input_mean = self.input_std = None
 
         self.inplanes = 64
         self.conv1 = nn.Conv2d(input_channels, 64, kernel_size=7, stride=2, padding=3, bias=False)
@@ -160,7 +163,10 @@ class ResNet(HipBackbone, MeanStdMixin, StockDDPAware):
         return out, tape
 
     def forward(self, x):
-        """models/resnet.py:195-223 contract: x [N, T*C, H, W] fp32 -> logits [N, num_classes]."""
+        """models/resnet.py:195-223 contract: x [N, T*C, H, W] fp32 -> logits [N, num_classes].  x may also be one clip per video as a
+        loader hands it over (video.Frames / video.EncodedFrames, adamml_amd/data.py unimodal_loaders)."""
+        if isinstance(x, (video.Frames, video.EncodedFrames)):
+            return self._forward_frames(x)
         hip.require_gpu(x)
         self.flat_owner.ensure(x.device)
         if self.training and torch.is_grad_enabled():
@@ -168,6 +174,24 @@ class ResNet(HipBackbone, MeanStdMixin, StockDDPAware):
         n, c_t, hh, ww = x.shape
         frames = self.orig_num_frames if c_t != 1 else 1
         xs = clip_to_nhwc(x, 1, frames, c_t // frames, cpad=self.input_cpad(hh, ww))[0]
+        return self.call(xs)
+
+    def _forward_frames(self, x):
+        """MI355X extension, AdaMML.data_layer's decoded-frame route for ONE segment: the files / decoded windows + their sampled geometry
+        -> the uint8 arrays `Stack` would return (video.augment: decode, crop / scale / flip, and for rgbdiff the difference images,
+        byte-exact) -> ToTorchFormatTensor + GroupNormalize inside the re-layout launch.  mean / std: input_mean / input_std when the
+        launcher set them (--mean / --std, train_unimodal.py:100-117), else this model's values for input_modality."""
+        m, frames = self.input_modality, self.orig_num_frames
+        if x.modality != m or x.k_out != frames * self.input_channels:
+            raise ValueError("ResNet: %s Frames with %d channels given to a %s stem that takes %d frames x %d channels"
+                             % (x.modality, x.k_out, m, frames, self.input_channels))
+        u8 = video.augment(x)
+        self.flat_owner.ensure(u8.device)
+        if self.training and torch.is_grad_enabled():
+            self.flat_owner.ensure_grads()
+        mean = self.input_mean if self.input_mean is not None else self.mean(m)
+        std = self.input_std if self.input_std is not None else self.std(m)
+        xs = clip_u8_to_nhwc(u8, 1, frames, self.input_channels, mean, std, cpad=self.input_cpad(u8.size(1), u8.size(2)))[0]
         return self.call(xs)
 
     def input_cpad(self, h, w):

@@ -3,7 +3,7 @@ Mirrors models/sound_mobilenet_v2.py:33-198 (class MobileNetV2, factory sound_mo
 import torch
 import torch.nn as nn
 
-from . import hip
+from . import audio, hip
 from .backbone import HipBackbone, FlatBuffers, StockDDPAware, NotifyingSequential
 from .common import MeanStdMixin
 from .mobilenet_common import BlockPlan, run_blocks
@@ -58,7 +58,8 @@ class MobileNetV2(HipBackbone, MeanStdMixin, StockDDPAware):
         input_channel = _make_divisible(32 * width_mult, round_nearest)
         self.last_channel = _make_divisible(1280 * max(1.0, width_mult), round_nearest)
         self.input_channels = input_channels
-        features = [ConvBNReLU(input_channels, input_channel, stride=2)]
+        self.resampling_rate = 24000          # of an audio.Waveforms input (forward); the unimodal launcher sets --resampling_rate
+        features =[ConvBNReLU(input_channels, input_channel, stride=2)]
         for t, c, n, s in _CFG:
             output_channel = _make_divisible(c * width_mult, round_nearest)
             for i in range(n):
@@ -119,7 +120,13 @@ class MobileNetV2(HipBackbone, MeanStdMixin, StockDDPAware):
         return out, tape
 
     def forward(self, x):
-        """x [B, 1, H, W] fp32 -> logits (models/sound_mobilenet_v2.py:152-162)."""
+        """x [B, 1, H, W] fp32 -> logits (models/sound_mobilenet_v2.py:152-162).  x may also be the loader's sound windows, one per
+        video (audio.Waveforms [B, 1, L]): their log-power spectrograms at self.resampling_rate are computed here, exactly 0 where the
+        track is missing (video_dataset.py:102-103)."""
+        if isinstance(x, audio.Waveforms):
+            if x.size(1) != 1:
+                raise ValueError("sound MobileNetV2: Waveforms with %d windows per video, the bare backbone takes one" % x.size(1))
+            x = x.spectrogram(sample_rate=self.resampling_rate)
         hip.require_gpu(x)
         self.flat_owner.ensure(x.device)
         if self.training and torch.is_grad_enabled():

@@ -402,7 +402,13 @@ def main(argv=None, train_loader=None, val_loader=None, log=print):
     """train_adamml.py:32-63: parse, resolve the node topology, then either run this process as ONE rank (plain call, or a rank
     started by torch.distributed.run: RANK / LOCAL_RANK / WORLD_SIZE in the environment) or, with --multiprocessing-distributed,
     spawn one process per visible GPU and run `main_worker` in each."""
-    args = arg_parser().parse_args(argv)
+    return launch(arg_parser().parse_args(argv), main_worker, _spawned_worker, train_loader, val_loader, log, "adamml_amd.train")
+
+
+def launch(args, worker, spawned_worker, train_loader=None, val_loader=None, log=print, who="adamml_amd.train"):
+    """The part of `main` behind the parser, shared by the launchers (train_adamml.py:37-63 and train_unimodal.py:38-61 are the same
+    lines): worker(gpu, ngpus_per_node, args, train_loader, val_loader, log) runs one rank, spawned_worker(gpu, ngpus_per_node, args) is
+    its picklable form for torch.multiprocessing.spawn."""
     if args.gpu_id:                                                          # train_adamml.py:37-38
         os.environ["HIP_VISIBLE_DEVICES"] = os.environ["CUDA_VISIBLE_DEVICES"] = args.gpu_id
     if args.hostfile != "":                                                  # train_adamml.py:40-50
@@ -417,7 +423,7 @@ def main(argv=None, train_loader=None, val_loader=None, log=print):
         args.world_size = len(nodes)
         args.dist_url = "tcp://{}:10598".format(nodes[0].split(" ")[0])
     if not torch.cuda.is_available():
-        raise SystemExit("adamml_amd.train needs an MI355X: the HIP hot path has no CPU fallback")
+        raise SystemExit("%s needs an MI355X: the HIP hot path has no CPU fallback" % who)
     under_launcher = "WORLD_SIZE" in os.environ and "RANK" in os.environ
     if args.multiprocessing_distributed and not under_launcher:
         ngpus = int(os.environ.get("ADAMML_SPAWN_RANKS", 0)) or torch.cuda.device_count()     # (test aid: ranks sharing one GPU)
@@ -427,9 +433,9 @@ def main(argv=None, train_loader=None, val_loader=None, log=print):
         args.world_size = ngpus * args.world_size                            # train_adamml.py:55-57
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")             # dmabuf IPC: RCCL needs it on this driver
         import torch.multiprocessing as mp
-        mp.spawn(_spawned_worker, nprocs=ngpus, args=(ngpus, args))
+        mp.spawn(spawned_worker, nprocs=ngpus, args=(ngpus, args))
         return None
-    return main_worker(args.gpu, torch.cuda.device_count(), args, train_loader, val_loader, log)
+    return worker(args.gpu, torch.cuda.device_count(), args, train_loader, val_loader, log)
 
 
 def _spawned_worker(gpu, ngpus_per_node, args):
@@ -444,8 +450,9 @@ def _load_factory(spec):
     return getattr(importlib.import_module(mod), fn)
 
 
-def main_worker(gpu, ngpus_per_node, args, train_loader=None, val_loader=None, log=print):
-    """train_adamml.py:66-629 for one rank."""
+def init_rank(gpu, ngpus_per_node, args):
+    """This process's place among the ranks (train_adamml.py:73-83): sets args.gpu / args.rank / args.world_size / args.distributed,
+    selects the device and joins the process group.  Returns (device, rank, world)."""
     if "WORLD_SIZE" in os.environ and "RANK" in os.environ:                  # started by torch.distributed.run
         world, rank = int(os.environ["WORLD_SIZE"]), int(os.environ["RANK"])
         local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -469,16 +476,26 @@ def main_worker(gpu, ngpus_per_node, args, train_loader=None, val_loader=None, l
     if world > 1 and not dist.is_initialized():
         dist.init_process_group(backend, **init)                             # train_adamml.py:83
     args.distributed = world > 1
-    resolve_args(args, log, rank)
-    per_rank_batch = max(1, args.batch_size // world)                       # train_adamml.py:122
+    return device, rank, world
+
+
+def enable_launch_plans(per_rank_batch):
     if "ADAMML_LAUNCH_PLAN" not in os.environ and per_rank_batch <= 16:
         # small per-GPU batches (the README recipe: 72 videos over 8 GPUs) are bound by the Python issue of ~1300 launches per step:
         # replay the static launch sequences from C (adamml_amd/plan.py; costs the sum instead of the peak of a step's activations)
         from . import plan as _plan
         _plan.ENABLED = True
+
+
+def main_worker(gpu, ngpus_per_node, args, train_loader=None, val_loader=None, log=print):
+    """train_adamml.py:66-629 for one rank."""
+    device, rank, world = init_rank(gpu, ngpus_per_node, args)
+    resolve_args(args, log, rank)
+    per_rank_batch = max(1, args.batch_size // world)                       # train_adamml.py:122
+    enable_launch_plans(per_rank_batch)
     if args.backbone_net != "adamml":
-        raise SystemExit("adamml_amd.train restates train_adamml.py; unimodal training is models.resnet / sound_mobilenet_v2 "
-                         "behind the same registry (build_model) with a plain loop")
+        raise SystemExit("adamml_amd.train restates train_adamml.py; unimodal training (models.resnet / sound_mobilenet_v2 behind the "
+                         "same registry) is adamml_amd.train_unimodal: python3 train_unimodal.py ...")
 
     model, arch_name = build_model(args)
     model = model.to(device)
