@@ -15,6 +15,10 @@ decoding, augmentation and the spectrogram to the GPU -- or pass your own iterab
 `main(train_loader=..., val_loader=...)`, or use `--synthetic N` (N synthetic batches per epoch, adamml_amd.synth) to exercise the
 whole schedule.
 
+Validation reports what the reference's does (`validate_report`; metrics.py): loss, top-1 / top-5, mAP, ms per batch, GFLOPs per video and
+the selection rate of each modality on one line after each `Val:` line, the per-video selections as all_selection*.npz and, under -e,
+the logits as .npy in the log folder.
+
     python -m adamml_amd.train ... --dense_sampling --datadir RGB_DIR SOUND_DIR --loader_factory adamml_amd.data:loaders
 
     python -m adamml_amd.train --backbone_net adamml -d 50 --groups 8 --num_segments 5 --modality rgb sound \\
@@ -27,11 +31,12 @@ import os
 import shutil
 import time
 
+import numpy as np
 import torch
 import torch.distributed as dist
 import torch.nn.functional as F
 
-from . import synth
+from . import metrics, synth
 from .distributed import HipDDP
 from .model_builder import build_model
 from .optim import FlatAdam, FlatSGD
@@ -374,27 +379,87 @@ def train_epoch(loader, ddp, opt, p_opt, epoch, args, cost_weights, rank=0, log=
     return meters, sel_meter
 
 
+def major_modalities(modality):
+    """train_adamml.py:169-172: rgbdiff is only the policy net's proxy for flow when both are given; decisions, selection rates and
+    the FLOPs estimate are per major modality."""
+    if "rgbdiff" in modality and "flow" in modality:
+        return [m for m in modality if m != "rgbdiff"]
+    return list(modality)
+
+
 @torch.no_grad()
-def validate(loader, ddp, args, num_segments):
-    """utils/utils.py:427-507 (top-k on the concatenated outputs; mAP needs torchnet in the reference and is not restated)."""
+def validate_report(loader, ddp, args, num_segments):
+    """utils/utils.py:427-507 with everything the reference's validation line reports.  Returns a dict:
+    top1 / top5 / loss (as `validate`), mAP (metrics.actnet_acc on the gathered logits), speed_ms (mean wall time per batch),
+    selection {major modality: Meter}, flops (metrics.flops_computation on those meters), all_selections [N, S, M] and
+    outputs [N, K] (device tensors) and, when the model skips unselected clips, executed {modality: (clips run, clips total)}
+    summed over THIS rank's batches.
+
+    The selection meter is the reference's: per batch the mean of `selection` over videos and segments, averaged over the ranks,
+    updated with n = 1 -- so `.avg` is the mean of the batch means, not the sample-weighted mean (the per-batch all-reduces of
+    utils/utils.py:475-476 travel as one [batches, M] all-reduce after the loop: the same sums).
+    Row order of all_selections / outputs: rank-major, each rank's batches in loader order (the reference gathers per batch, so its
+    rows are batch-major); what a DistributedSampler pads a rank's share with is included, as in the reference."""
     model = ddp.module
     model.eval()
     device = next(model.parameters()).device
-    outs, labels, sels = [], [], []
-    loss_m = Meter()
+    major = major_modalities(args.modality)
+    outs, labels, sels, ratios = [], [], [], []
+    loss_m, time_m = Meter(), Meter()
+    executed, total = None, 0
+    end = time.time()
     for images, target in loader:
         images = [x.to(device, non_blocking=True) for x in images]
         target = target.to(device, non_blocking=True)
+        model.last_skip_stats = None
         output, selection = model(images, num_segments)
         loss_m.update(F.cross_entropy(output, target).item(), target.size(0))
         outs.append(output)
         labels.append(target)
         sels.append(selection)
-    output, target, selection = torch.cat(outs), torch.cat(labels), torch.cat(sels)
+        ratios.append(selection.mean(0).mean(0))
+        if model.last_skip_stats is not None:
+            ran = model.last_skip_stats["executed_per_modality"]
+            executed = [a + b for a, b in zip(executed, ran)] if executed is not None else list(ran)
+            total += model.last_skip_stats["clips"]
+        time_m.update(time.time() - end)
+        end = time.time()
+    output, target, selection, ratios = torch.cat(outs), torch.cat(labels), torch.cat(sels), torch.stack(ratios)
     if dist.is_initialized():
         output, target, selection = concat_all_gather(output), concat_all_gather(target), concat_all_gather(selection)
+        dist.all_reduce(ratios)
+        ratios /= dist.get_world_size()
     top1, top5 = accuracy(output, target)
-    return top1.item(), top5.item(), loss_m.avg, selection
+    _, mAP = metrics.actnet_acc(output, target)
+    sel_meter = {m: Meter() for m in major}
+    for row in ratios.tolist():
+        for m, r in zip(major, row):
+            sel_meter[m].update(r)
+    report = {"top1": top1.item(), "top5": top5.item(), "loss": loss_m.avg, "mAP": mAP, "speed_ms": time_m.avg * 1000.0,
+              "selection": sel_meter, "flops": metrics.flops_computation(major, sel_meter, num_segments),
+              "all_selections": selection, "outputs": output}
+    if executed is not None:
+        report["executed"] = {m: (n, total) for m, n in zip(model.main_net.modality, executed)}
+    return report
+
+
+def validate(loader, ddp, args, num_segments):
+    """(top1, top5, loss, selections [N, S, M]) of `validate_report`."""
+    r = validate_report(loader, ddp, args, num_segments)
+    return r["top1"], r["top5"], r["loss"], r["all_selections"]
+
+
+def report_line(head, r):
+    """The reference's validation line (train_adamml.py:214-215, 494-495, 605-606) behind its `head`."""
+    return "{}: \tLoss: {:4.4f}\tTop@1: {:.4f}\tTop@5: {:.4f}\tmAP: {:.4f}\tSpeed: {:.2f} ms/batch\tflops: {:.2f}\tSelection: {}".format(
+        head, r["loss"], r["top1"], r["top5"], r["mAP"], r["speed_ms"], r["flops"],
+        "".join("{}:{:.2f} ".format(k, v.avg * 100) for k, v in r["selection"].items()))
+
+
+def save_selections(path, args, r):
+    """all_selection*.npz (train_adamml.py:209-210, 489-490, 600-601): the decisions as bool [N, S, M] and the major modalities'
+    names joined by '_' (the reference's per-epoch files carry a bare '_' there: `'_'.format(...)`)."""
+    np.savez(path, modality="_".join(major_modalities(args.modality)), selections=r["all_selections"].cpu().numpy().astype(bool))
 
 
 # ------------------------------------------------------------------------------------------------ schedule
@@ -514,7 +579,8 @@ def main_worker(gpu, ngpus_per_node, args, train_loader=None, val_loader=None, l
             train_loader, val_loader = _load_factory(args.loader_factory)(args, rank, world, device)
         elif args.synthetic:
             train_loader = SyntheticLoader(args, args.synthetic, per_rank_batch, device, rank)
-            val_loader = SyntheticLoader(args, max(1, args.synthetic // 4), per_rank_batch, device, rank + 7777, args.val_num_clips)
+            if val_loader is None:                                          # (a val_loader passed to main() alone is kept)
+                val_loader = SyntheticLoader(args, max(1, args.synthetic // 4), per_rank_batch, device, rank + 7777, args.val_num_clips)
         else:
             raise SystemExit("no dataset pipeline was named: pass --loader_factory adamml_amd.data:loaders (the reference's dataset layout "
                              "below --datadir) or another MODULE:FUNCTION, pass train_loader / val_loader to main(), or use "
@@ -559,9 +625,20 @@ def main_worker(gpu, ngpus_per_node, args, train_loader=None, val_loader=None, l
 
     zero_cost = [0.0] * len(args.modality)
     if args.evaluate:
-        top1, top5, loss, _ = validate(val_loader, ddp, args, args.val_num_clips)
+        r = validate_report(val_loader, ddp, args, args.val_num_clips)
+        top1, top5, loss = r["top1"], r["top5"], r["loss"]
         log("Val: Loss {:.4f}\tTop@1 {:.4f}\tTop@5 {:.4f}".format(loss, top1, top5))
-        return {"top1": top1, "top5": top5, "loss": loss}
+        if rank == 0:                                                        # train_adamml.py:207-223
+            log(report_line("Val@{}@{}".format(args.input_size, args.val_num_clips), r))
+            save_selections(os.path.join(log_folder, "all_selection.npz"), args, r)
+            postfix = os.path.basename(args.pretrained).split(".")[0] if args.pretrained is not None else ""
+            np.save(os.path.join(log_folder, "val_{}crops_{}clips_{}_details_{}.npy".format(args.num_crops, args.val_num_clips, args.input_size,
+                                                                                          postfix)), r["outputs"].float().cpu().numpy())
+        res = {"top1": top1, "top5": top5, "loss": loss, "mAP": r["mAP"], "flops": r["flops"], "speed_ms": r["speed_ms"],
+               "selection": {k: v.avg for k, v in r["selection"].items()}}
+        if "executed" in r:
+            res["executed"] = r["executed"]
+        return res
 
     history = []
     if stage == "warmup":                                                   # train_adamml.py:340-392
@@ -587,13 +664,16 @@ def main_worker(gpu, ngpus_per_node, args, train_loader=None, val_loader=None, l
             model.freeze_main_net()
             m, _ = train_epoch(train_loader, ddp, opt, p_opt, epoch + 1, args, args.cost_weights, rank, log)
             history.append(("policy", epoch + 1, m["loss"].avg))
-            top1, top5, vloss, _ = validate(val_loader, ddp, args, args.val_num_clips)
+            r = validate_report(val_loader, ddp, args, args.val_num_clips)
+            top1, top5, vloss = r["top1"], r["top5"], r["loss"]
             sched.step(epoch + 1, vloss)
             p_sched.step(epoch + 1, vloss)
             is_best = top1 > best_top1
             best_top1 = max(top1, best_top1)
             if rank == 0:
                 log("Val: [{:03d}/{:03d}]\tLoss {:.4f}\tTop@1 {:.4f}\tTop@5 {:.4f}".format(epoch + 1, args.epochs, vloss, top1, top5))
+                log(report_line("Val: [{:03d}/{:03d}]".format(epoch + 1, args.epochs), r))
+                save_selections(os.path.join(log_folder, "all_selection_main_{}.npz".format(epoch + 1)), args, r)
             snapshot(epoch + 1, "alternative_training", is_best, "_main")
             model.decay_temperature()
         stage, args.start_epoch = "finetune", 0
@@ -620,13 +700,16 @@ def main_worker(gpu, ngpus_per_node, args, train_loader=None, val_loader=None, l
         for epoch in range(args.start_epoch, args.finetune_epochs):
             m, _ = train_epoch(train_loader, ddp, opt, p_opt, epoch + 1, args, zero_cost, rank, log)
             history.append(("finetune", epoch + 1, m["loss"].avg))
-            top1, top5, vloss, _ = validate(val_loader, ddp, args, args.val_num_clips)
+            r = validate_report(val_loader, ddp, args, args.val_num_clips)
+            top1, top5, vloss = r["top1"], r["top5"], r["loss"]
             sched.step(epoch + 1, vloss)
             p_sched.step(epoch + 1, vloss)
             is_best = top1 > best_top1
             best_top1 = max(top1, best_top1)
             if rank == 0:
                 log("Val: [{:03d}/{:03d}]\tLoss {:.4f}\tTop@1 {:.4f}\tTop@5 {:.4f}".format(epoch + 1, args.finetune_epochs, vloss, top1, top5))
+                log(report_line("Val: [{:03d}/{:03d}]".format(epoch + 1, args.finetune_epochs), r))
+                save_selections(os.path.join(log_folder, "all_selection_finetune_{}.npz".format(epoch + 1)), args, r)
             snapshot(epoch + 1, "finetune", is_best, "_finetune")
     return {"history": history, "best_top1": best_top1, "log_folder": log_folder, "temperature": model.policy_net.temperature}
 
