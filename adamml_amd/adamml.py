@@ -72,6 +72,11 @@ class AdaMML(nn.Module, MeanStdMixin, StockDDPAware):
                 if m == 'sound' or x_.modality != m:
                     raise ValueError("AdaMML: %s Frames given for the %s modality" % (x_.modality, m))
                 x_ = video.augment(x_)
+            elif isinstance(x_, video.Augmented):
+                # the same arrays, made ahead of the step (adamml_amd/prefetch.py): nothing left to launch here
+                if m == 'sound' or x_.modality != m:
+                    raise ValueError("AdaMML: %s Frames given for the %s modality" % (x_.modality, m))
+                x_ = x_.u8
             if isinstance(x_, audio.Waveforms):
                 # MI355X extension: the loader's sound windows + missing-track flags -> spectrograms, exactly 0 where the track is missing
                 if m != 'sound':
@@ -147,7 +152,7 @@ class AdaMML(nn.Module, MeanStdMixin, StockDDPAware):
 
     def forward(self, x, num_segments=None, gumbel_exponential=None):
         """x: list over modality of [N, S*F*C, H, W] fp32 GPU tensors (sound may also be raw waveforms [N, S, L] fp32, rgb / flow /
-        rgbdiff decoded videos as a video.Frames: data_layer).
+        rgbdiff decoded videos as a video.Frames, or what the prefetcher made of them, a video.Augmented: data_layer).
         Returns (logits [N, classes], decisions [N,S,M]).
         gumbel_exponential (optional, [S, M*N, 2]) replaces the device-side Exponential(1) draw for parity runs."""
         num_segments = num_segments if num_segments else self.num_segments

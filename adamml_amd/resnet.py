@@ -164,8 +164,9 @@ class ResNet(HipBackbone, MeanStdMixin, StockDDPAware):
 
     def forward(self, x):
         """models/resnet.py:195-223 contract: x [N, T*C, H, W] fp32 -> logits [N, num_classes].  x may also be one clip per video as a
-        loader hands it over (video.Frames / video.EncodedFrames, adamml_amd/data.py unimodal_loaders)."""
-        if isinstance(x, (video.Frames, video.EncodedFrames)):
+        loader hands it over (video.Frames / video.EncodedFrames, adamml_amd/data.py unimodal_loaders), or what the prefetcher has made of
+        that ahead of the step (video.Augmented, adamml_amd/prefetch.py)."""
+        if isinstance(x, (video.Frames, video.EncodedFrames, video.Augmented)):
             return self._forward_frames(x)
         hip.require_gpu(x)
         self.flat_owner.ensure(x.device)
@@ -180,12 +181,17 @@ class ResNet(HipBackbone, MeanStdMixin, StockDDPAware):
         """MI355X extension, AdaMML.data_layer's decoded-frame route for ONE segment: the files / decoded windows + their sampled geometry
         -> the uint8 arrays `Stack` would return (video.augment: decode, crop / scale / flip, and for rgbdiff the difference images,
         byte-exact) -> ToTorchFormatTensor + GroupNormalize inside the re-layout launch.  mean / std: input_mean / input_std when the
-        launcher set them (--mean / --std, train_unimodal.py:100-117), else this model's values for input_modality."""
+        launcher set them (--mean / --std, train_unimodal.py:100-117), else this model's values for input_modality.  A video.Augmented
+        holds the uint8 arrays already and passes the same check."""
         m, frames = self.input_modality, self.orig_num_frames
         if x.modality != m or x.k_out != frames * self.input_channels:
             raise ValueError("ResNet: %s Frames with %d channels given to a %s stem that takes %d frames x %d channels"
                              % (x.modality, x.k_out, m, frames, self.input_channels))
-        u8 = video.augment(x)
+        return self._forward_u8(x.u8 if isinstance(x, video.Augmented) else video.augment(x))
+
+    def _forward_u8(self, u8):
+        """`Stack`'s uint8 arrays [N, H, W, T*C] -> logits: everything of _forward_frames behind video.augment."""
+        m, frames = self.input_modality, self.orig_num_frames
         self.flat_owner.ensure(u8.device)
         if self.training and torch.is_grad_enabled():
             self.flat_owner.ensure_grads()

@@ -36,7 +36,7 @@ import torch
 import torch.distributed as dist
 import torch.nn.functional as F
 
-from . import metrics, synth
+from . import metrics, prefetch, synth
 from .distributed import HipDDP
 from .model_builder import build_model
 from .optim import FlatAdam, FlatSGD
@@ -58,7 +58,7 @@ def arg_parser():
     """Every flag of the reference's parser (opts.py:5-149), same spelling, type and default -- except `--backbone_net` (the
     reference's default 's3d' is not among its own choices, opts.py:9-10: 'adamml' here), `-d` (18 there; 50 here, the depth of
     the AdaMML recipes -- 18 / 34 / 101 / 152 run as well) and `--dataset` (the reference's default 'activitynet' is absent from its own table:
-    'kinetics-sounds' here).  Three flags are additions: --synthetic, --loader_factory, --num_classes."""
+    'kinetics-sounds' here).  The additions: --synthetic, --loader_factory, --num_classes, --prefetch, --imagenet_weights."""
     p = argparse.ArgumentParser(description="AdaMML training on MI355X (restated reference launcher)")
     # model definition (opts.py:8-35)
     p.add_argument("--backbone_net", default="adamml", type=str, choices=["adamml", "resnet", "sound_mobilenet_v2"])
@@ -146,6 +146,9 @@ def arg_parser():
     p.add_argument("--loader_factory", default=None, type=str, metavar="MODULE:FUNCTION",
                    help="data pipeline hook: FUNCTION(args, rank, world, device) -> (train_loader, val_loader), imported in every rank")
     p.add_argument("--num_classes", default=None, type=int, help="overrides the class count of --dataset")
+    p.add_argument("--prefetch", default=0, type=int, choices=[0, 1, 2], metavar="N",
+                   help="copy, decode and augment the next N batches on a stream of their own, beside the step (adamml_amd/prefetch.py); "
+                        "0: in front of the step, on its stream")
     p.add_argument("--imagenet_weights", default=[], nargs="+", metavar="ARCH=PATH",
                    help="local torchvision ImageNet state_dict files the reference would download (models/resnet.py:251-257, "
                         "models/policy_net.py:193-203,221): resnet50=PATH mobilenet_v2=PATH mobilenetv2_160x160=PATH; also $ADAMML_IMAGENET_DIR")
@@ -335,6 +338,7 @@ def train_epoch(loader, ddp, opt, p_opt, epoch, args, cost_weights, rank=0, log=
     gammas = torch.tensor(args.gammas, device=device)
     meters = {k: Meter() for k in ("loss", "top1", "top5", "time")}
     sel_meter = {m: Meter() for m in args.modality}
+    late = prefetch.late(loader)
     end = time.time()
     for i, (images, target) in enumerate(loader):
         images = [x.to(device, non_blocking=True) for x in images]
@@ -376,6 +380,9 @@ def train_epoch(loader, ddp, opt, p_opt, epoch, args, cost_weights, rank=0, log=
             log("Epoch: [{}][{}/{}]\tTime {:.3f}\tLoss {:.4f}\tPrec@1 {:.3f}\tPrec@5 {:.3f}\t{}".format(
                 epoch, i, len(loader), meters["time"].avg, meters["loss"].avg, meters["top1"].avg, meters["top5"].avg,
                 " ".join("{}:{:.2f}".format(k, v.avg * 100) for k, v in sel_meter.items())))
+    line = prefetch.late_line(loader, late, epoch)
+    if line and rank == 0:
+        log(line)
     return meters, sel_meter
 
 
@@ -585,6 +592,8 @@ def main_worker(gpu, ngpus_per_node, args, train_loader=None, val_loader=None, l
             raise SystemExit("no dataset pipeline was named: pass --loader_factory adamml_amd.data:loaders (the reference's dataset layout "
                              "below --datadir) or another MODULE:FUNCTION, pass train_loader / val_loader to main(), or use "
                              "--synthetic N" + ("; --datadir %s was parsed and is handed to the factory" % args.datadir if args.datadir else ""))
+    # --prefetch N: whatever loaders these are, their batches are prepared N ahead on a stream of their own
+    train_loader, val_loader = prefetch.wrap(train_loader, args, device), prefetch.wrap(val_loader, args, device)
 
     def make_optimizers():
         o = FlatSGD(model._flat_main, args.lr, args.momentum, args.weight_decay, args.nesterov)

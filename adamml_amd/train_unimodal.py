@@ -26,7 +26,7 @@ import torch
 import torch.distributed as dist
 import torch.nn.functional as F
 
-from . import train
+from . import prefetch, train
 from .distributed import HipDDP
 from .model_builder import build_model
 from .optim import FlatSGD
@@ -113,6 +113,7 @@ def train_epoch(loader, ddp, opt, epoch, args, rank=0, log=print):
     device = next(model.parameters()).device
     meters = {k: Meter() for k in ("loss", "top1", "top5", "time", "data")}
     meters["losses"] = []
+    late = prefetch.late(loader)
     end = time.time()
     for i, (images, target) in enumerate(loader):
         meters["data"].update(time.time() - end)
@@ -141,6 +142,9 @@ def train_epoch(loader, ddp, opt, epoch, args, rank=0, log=print):
         if i % args.print_freq == 0 and rank == 0:
             log("Epoch: [{}][{}/{}]\tTime {:.3f}\tData {:.3f}\tLoss {:.4f}\tPrec@1 {:.3f}\tPrec@5 {:.3f}".format(
                 epoch, i, len(loader), meters["time"].avg, meters["data"].avg, meters["loss"].avg, meters["top1"].avg, meters["top5"].avg))
+    line = prefetch.late_line(loader, late, epoch)
+    if line and rank == 0:
+        log(line)
     return meters
 
 
@@ -223,6 +227,8 @@ def main_worker(gpu, ngpus_per_node, args, train_loader=None, val_loader=None, l
                              "MODULE:FUNCTION, train_loader / val_loader to main(), or --synthetic N" % DEFAULT_FACTORY)
         train_loader = made[0] if train_loader is None else train_loader
         val_loader = made[1] if val_loader is None else val_loader
+    # --prefetch N: whatever loaders these are, their batches are prepared N ahead on a stream of their own
+    train_loader, val_loader = prefetch.wrap(train_loader, args, device), prefetch.wrap(val_loader, args, device)
 
     if args.evaluate:                                                        # train_unimodal.py:228-241
         top1, top5, loss, speed = validate(val_loader, ddp)

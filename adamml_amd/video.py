@@ -24,7 +24,7 @@ import torch
 
 from . import hip, jpeg, runtime
 
-__all__ = ['Augmentor', 'EncodedFrames', 'Frames', 'Geometry', 'augment', 'augmentor_for', 'coeffs', 'resized_size', 'check_table', 'KMAX']
+__all__ = ['Augmented', 'Augmentor', 'EncodedFrames', 'Frames', 'Geometry', 'augment', 'augment_nowait', 'augmentor_for', 'coeffs', 'resized_size', 'check_table', 'KMAX']
 
 PRECISION_BITS = 22      # Pillow's Resample.c, 8 bits per channel
 # Taps per table entry (include/adamml_hip.h): the bilinear support of a downscale by s is s on each side, so KMAX = 32 covers every
@@ -421,20 +421,78 @@ class EncodedFrames:
         out.batch, out.meta = self.batch.pin_memory(), self.meta.pin_memory()
         return out
 
-    def decode(self):
-        """The decoded videos as one flat uint8 buffer on the GPU (video i is [H_i, W_i, K_in] at the offset of its descriptor).
-        Waits for the decode status (one small device-to-host copy) and raises if a file's stream was damaged."""
-        y, status = jpeg.decode(self.batch)
-        bad = torch.nonzero(status).flatten().tolist()
+    def decode_nowait(self):
+        """(y, status): the decoded videos as one flat uint8 buffer on the GPU (video i is [H_i, W_i, K_in] at the offset of its
+        descriptor) and the int32 decode status of every file, both on the device and on the current stream: no host read.  The
+        caller brings `status` to the host when it suits it and hands it to `check_status`."""
+        return jpeg.decode(self.batch)
+
+    def check_status(self, status_host):
+        """Raise if a file's stream was damaged: status_host is `decode_nowait`'s status as a host tensor."""
+        bad = torch.nonzero(status_host).flatten().tolist()
         if bad:
             i, j = self.file_of[bad[0]]
             raise RuntimeError("EncodedFrames: video %d, file %d has a damaged JPEG stream (decode status %d; %d files of the batch affected)"
-                               % (i, j, int(status[bad[0]]), len(bad)))
+                               % (i, j, int(status_host[bad[0]]), len(bad)))
+
+    def decode(self):
+        """`decode_nowait`'s buffer.  Waits for the decode status (one small device-to-host copy) and raises if a file's stream was
+        damaged."""
+        y, status = self.decode_nowait()
+        self.check_status(status.cpu())
         return y
 
     def __repr__(self):
         return "EncodedFrames(%s, N=%d, %dx%d, K %d -> %d, %s)" % (self.modality, self.n, self.out_h, self.out_w, self.k_in, self.k_out,
                                                                    self.device)
+
+
+class Augmented:
+    """A batch of N videos that `augment` has already been through, the prepared input of adamml_amd/prefetch.py: u8 is
+    [N, OH, OW, K_out] uint8 on the device, modality and k_out say what it holds.  AdaMML.forward and ResNet.forward take it where
+    they take a `Frames` and skip the decode and the resampling.  A plain class, like `Frames`: DistributedDataParallel's input
+    scatter passes it through as it is."""
+
+    def __init__(self, u8, modality, k_out):
+        if not torch.is_tensor(u8) or u8.dtype != torch.uint8 or u8.dim() != 4:
+            raise ValueError("Augmented: expected a uint8 tensor [N, OH, OW, K_out], got %s %s"
+                             % (getattr(u8, 'dtype', type(u8).__name__), tuple(getattr(u8, 'shape', ()))))
+        if modality not in MODALITIES:
+            raise ValueError("Augmented: modality %r, expected one of %s" % (modality, MODALITIES))
+        if int(k_out) != u8.size(3):
+            raise ValueError("Augmented: k_out %d but the tensor holds %d channels" % (k_out, u8.size(3)))
+        self.u8, self.modality, self.k_out = u8, modality, int(k_out)
+
+    @property
+    def device(self):
+        return self.u8.device
+
+    @property
+    def shape(self):
+        return self.u8.shape
+
+    def size(self, dim=None):
+        return self.shape if dim is None else self.shape[dim]
+
+    def to(self, device, non_blocking=False):
+        """`self` when the tensor is on `device` already, else an Augmented whose tensor lives there."""
+        u8 = self.u8.to(device, non_blocking=non_blocking)
+        return self if u8 is self.u8 else Augmented(u8, self.modality, self.k_out)
+
+    def __repr__(self):
+        return "Augmented(%s, %s, %s)" % (self.modality, tuple(self.u8.shape), self.device)
+
+
+def augment_nowait(frames):
+    """(u8, status): `augment`'s [N, OH, OW, K_out] uint8 tensor without its host synchronisation, and the per-file int32 decode
+    status on the device for `EncodedFrames.check_status` -- None for a `Frames`, which has none.  Runs on the current stream.  Where
+    the status is not 0 the pixels of that video are not to be used."""
+    if isinstance(frames, EncodedFrames):
+        y, status = frames.decode_nowait()
+        return runtime.video_resample_u8(y, frames.meta, frames.n, frames.out_h, frames.out_w, frames.k_in, frames.k_out, frames.diffs), status
+    if not isinstance(frames, Frames):
+        raise TypeError("augment: expected a video.Frames, got %s" % type(frames).__name__)
+    return runtime.video_resample_u8(frames.data, frames.meta, frames.n, frames.out_h, frames.out_w, frames.k_in, frames.k_out, frames.diffs), None
 
 
 def augment(frames):
@@ -443,6 +501,4 @@ def augment(frames):
     if isinstance(frames, EncodedFrames):
         return runtime.video_resample_u8(frames.decode(), frames.meta, frames.n, frames.out_h, frames.out_w, frames.k_in, frames.k_out,
                                          frames.diffs)
-    if not isinstance(frames, Frames):
-        raise TypeError("augment: expected a video.Frames, got %s" % type(frames).__name__)
-    return runtime.video_resample_u8(frames.data, frames.meta, frames.n, frames.out_h, frames.out_w, frames.k_in, frames.k_out, frames.diffs)
+    return augment_nowait(frames)[0]
