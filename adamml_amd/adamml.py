@@ -296,6 +296,12 @@ class AdaMML(nn.Module, MeanStdMixin, StockDDPAware):
         self.last_skip_stats = {"clips": S * B, "executed_per_modality": ran}
         return self.main_net.fuse_segments(stacked, decisions, S), decisions.permute((2, 0, 1))
 
+    def online(self, num_segments=None, batch_size=1, gumbel_exponential=None):
+        """MI355X extension: an online.Session on this model (eval mode, under no_grad) -- decisions, selected main-net clips and a
+        running prediction one segment at a time (adamml_amd/online.py)."""
+        from .online import Session
+        return Session(self, num_segments if num_segments else self.num_segments, batch_size, gumbel_exponential)
+
     def _main_cpad(self, modality, h, w):
         """Channel padding the main net of `modality` wants for its NHWC input (ResNet.input_cpad: 4-channel pixels for the 7x7 stem
         kernel), None = the generic multiple of 8."""

@@ -36,7 +36,7 @@ import torch
 import torch.distributed as dist
 import torch.nn.functional as F
 
-from . import metrics, prefetch, synth
+from . import metrics, online, prefetch, synth
 from .distributed import HipDDP
 from .model_builder import build_model
 from .optim import FlatAdam, FlatSGD
@@ -58,7 +58,7 @@ def arg_parser():
     """Every flag of the reference's parser (opts.py:5-149), same spelling, type and default -- except `--backbone_net` (the
     reference's default 's3d' is not among its own choices, opts.py:9-10: 'adamml' here), `-d` (18 there; 50 here, the depth of
     the AdaMML recipes -- 18 / 34 / 101 / 152 run as well) and `--dataset` (the reference's default 'activitynet' is absent from its own table:
-    'kinetics-sounds' here).  The additions: --synthetic, --loader_factory, --num_classes, --prefetch, --imagenet_weights."""
+    'kinetics-sounds' here).  The additions: --synthetic, --loader_factory, --num_classes, --prefetch, --online, --imagenet_weights."""
     p = argparse.ArgumentParser(description="AdaMML training on MI355X (restated reference launcher)")
     # model definition (opts.py:8-35)
     p.add_argument("--backbone_net", default="adamml", type=str, choices=["adamml", "resnet", "sound_mobilenet_v2"])
@@ -149,6 +149,9 @@ def arg_parser():
     p.add_argument("--prefetch", default=0, type=int, choices=[0, 1, 2], metavar="N",
                    help="copy, decode and augment the next N batches on a stream of their own, beside the step (adamml_amd/prefetch.py); "
                         "0: in front of the step, on its stream")
+    p.add_argument("--online", action="store_true",
+                   help="with -e: step every validation batch through an online.Session, one segment at a time (adamml_amd/online.py), and "
+                        "report the latency per segment step beside the validation line")
     p.add_argument("--imagenet_weights", default=[], nargs="+", metavar="ARCH=PATH",
                    help="local torchvision ImageNet state_dict files the reference would download (models/resnet.py:251-257, "
                         "models/policy_net.py:193-203,221): resnet50=PATH mobilenet_v2=PATH mobilenetv2_160x160=PATH; also $ADAMML_IMAGENET_DIR")
@@ -406,7 +409,11 @@ def validate_report(loader, ddp, args, num_segments):
     updated with n = 1 -- so `.avg` is the mean of the batch means, not the sample-weighted mean (the per-batch all-reduces of
     utils/utils.py:475-476 travel as one [batches, M] all-reduce after the loop: the same sums).
     Row order of all_selections / outputs: rank-major, each rank's batches in loader order (the reference gathers per batch, so its
-    rows are batch-major); what a DistributedSampler pads a rank's share with is included, as in the reference."""
+    rows are batch-major); what a DistributedSampler pads a rank's share with is included, as in the reference.
+
+    With args.online every batch is split into its segments (online.split_segments) and stepped through an online.Session instead of one
+    forward; the report then carries "online": mean / maximum milliseconds per segment step (each step waited for on the device) and the
+    mean time to a batch's first decision, over this rank's batches."""
     model = ddp.module
     model.eval()
     device = next(model.parameters()).device
@@ -414,12 +421,25 @@ def validate_report(loader, ddp, args, num_segments):
     outs, labels, sels, ratios = [], [], [], []
     loss_m, time_m = Meter(), Meter()
     executed, total = None, 0
+    stepwise, step_ms, first_ms = getattr(args, "online", False), [], []
     end = time.time()
     for images, target in loader:
-        images = [x.to(device, non_blocking=True) for x in images]
         target = target.to(device, non_blocking=True)
         model.last_skip_stats = None
-        output, selection = model(images, num_segments)
+        if stepwise:
+            session = model.online(num_segments, target.size(0))
+            for piece in online.split_segments(images, num_segments):
+                torch.cuda.synchronize(device)
+                t0 = time.perf_counter()
+                step = session.step([x.to(device, non_blocking=True) for x in piece])
+                torch.cuda.synchronize(device)
+                step_ms.append((time.perf_counter() - t0) * 1000.0)
+                if session.t == 1:
+                    first_ms.append(step.decision_seconds * 1000.0)
+            output, selection = session.result()
+        else:
+            images = [x.to(device, non_blocking=True) for x in images]
+            output, selection = model(images, num_segments)
         loss_m.update(F.cross_entropy(output, target).item(), target.size(0))
         outs.append(output)
         labels.append(target)
@@ -447,6 +467,9 @@ def validate_report(loader, ddp, args, num_segments):
               "all_selections": selection, "outputs": output}
     if executed is not None:
         report["executed"] = {m: (n, total) for m, n in zip(model.main_net.modality, executed)}
+    if stepwise:
+        report["online"] = {"step_ms_mean": sum(step_ms) / max(len(step_ms), 1), "step_ms_max": max(step_ms, default=0.0),
+                            "first_decision_ms": sum(first_ms) / max(len(first_ms), 1), "steps": len(step_ms)}
     return report
 
 
@@ -463,6 +486,20 @@ def report_line(head, r):
         "".join("{}:{:.2f} ".format(k, v.avg * 100) for k, v in r["selection"].items()))
 
 
+def online_line(head, r):
+    """The --online line behind the validation line: wall time per segment step and to a batch's first decision."""
+    o = r["online"]
+    return "{}: \tOnline: {:.2f} ms/segment (max {:.2f}) over {} steps\tFirst decision: {:.2f} ms".format(
+        head, o["step_ms_mean"], o["step_ms_max"], o["steps"], o["first_decision_ms"])
+
+
+def check_online(args):
+    """--online steps the VALIDATION batches: without -e there is nothing for it to do."""
+    if getattr(args, "online", False) and not args.evaluate:
+        raise SystemExit("--online is valid only with -e / --evaluate: it steps the validation batches through an online.Session; "
+                         "training needs all segments of a video at once")
+
+
 def save_selections(path, args, r):
     """all_selection*.npz (train_adamml.py:209-210, 489-490, 600-601): the decisions as bool [N, S, M] and the major modalities'
     names joined by '_' (the reference's per-epoch files carry a bare '_' there: `'_'.format(...)`)."""
@@ -474,7 +511,9 @@ def main(argv=None, train_loader=None, val_loader=None, log=print):
     """train_adamml.py:32-63: parse, resolve the node topology, then either run this process as ONE rank (plain call, or a rank
     started by torch.distributed.run: RANK / LOCAL_RANK / WORLD_SIZE in the environment) or, with --multiprocessing-distributed,
     spawn one process per visible GPU and run `main_worker` in each."""
-    return launch(arg_parser().parse_args(argv), main_worker, _spawned_worker, train_loader, val_loader, log, "adamml_amd.train")
+    args = arg_parser().parse_args(argv)
+    check_online(args)
+    return launch(args, main_worker, _spawned_worker, train_loader, val_loader, log, "adamml_amd.train")
 
 
 def launch(args, worker, spawned_worker, train_loader=None, val_loader=None, log=print, who="adamml_amd.train"):
@@ -639,6 +678,8 @@ def main_worker(gpu, ngpus_per_node, args, train_loader=None, val_loader=None, l
         log("Val: Loss {:.4f}\tTop@1 {:.4f}\tTop@5 {:.4f}".format(loss, top1, top5))
         if rank == 0:                                                        # train_adamml.py:207-223
             log(report_line("Val@{}@{}".format(args.input_size, args.val_num_clips), r))
+            if "online" in r:
+                log(online_line("Val@{}@{}".format(args.input_size, args.val_num_clips), r))
             save_selections(os.path.join(log_folder, "all_selection.npz"), args, r)
             postfix = os.path.basename(args.pretrained).split(".")[0] if args.pretrained is not None else ""
             np.save(os.path.join(log_folder, "val_{}crops_{}clips_{}_details_{}.npy".format(args.num_crops, args.val_num_clips, args.input_size,
@@ -647,6 +688,8 @@ def main_worker(gpu, ngpus_per_node, args, train_loader=None, val_loader=None, l
                "selection": {k: v.avg for k, v in r["selection"].items()}}
         if "executed" in r:
             res["executed"] = r["executed"]
+        if "online" in r:
+            res["online"] = r["online"]
         return res
 
     history = []
