@@ -302,6 +302,12 @@ class AdaMML(nn.Module, MeanStdMixin, StockDDPAware):
         from .online import Session
         return Session(self, num_segments if num_segments else self.num_segments, batch_size, gumbel_exponential)
 
+    def online_pool(self, num_segments=None, capacity=8):
+        """MI355X extension: an online.Pool on this model (eval mode, under no_grad) -- up to `capacity` streams that open, step and
+        close independently, the streams of a tick served by one batched step (adamml_amd/online.py)."""
+        from .online import Pool
+        return Pool(self, num_segments if num_segments else self.num_segments, capacity)
+
     def _main_cpad(self, modality, h, w):
         """Channel padding the main net of `modality` wants for its NHWC input (ResNet.input_cpad: 4-channel pixels for the 7x7 stem
         kernel), None = the generic multiple of 8."""

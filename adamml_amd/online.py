@@ -17,7 +17,13 @@ segments seen so far ([t, N, 2048]) and, at step t, runs `PolicyNet.decide` on a
 noise and reads the last row: the first t rows of that call are, bit for bit, what the earlier steps computed
 (tests/test_online_gpu.py pins this prefix property).  With S <= 10 that is at most 55 head launches per batch instead of 10.
 
-`split_segments` turns what a loader hands `forward` (one entry per modality, all S segments) into S per-step inputs."""
+`split_segments` turns what a loader hands `forward` (one entry per modality, all S segments) into S per-step inputs.
+
+A `Session` serves its N videos in lock-step.  Streams that start and end independently go through a `Pool` (`model.online_pool`):
+every tick names the streams that have a segment and runs ONE batched step for them, whatever their positions -- one head launch
+again, on the per-slot features the pool keeps.  `gather_videos` assembles such a tick's input from rows of `split_segments`
+pieces, `stagger_schedule` is the schedule `-e --online --online_stagger K` serves a validation batch by, and `batch_noise` cuts
+one session's noise draw into the per-stream noise that makes a pool decide what that session decides."""
 import copy
 import time
 
@@ -25,7 +31,7 @@ import torch
 
 from . import audio, jpeg, video
 
-__all__ = ['Session', 'Step', 'split_segments']
+__all__ = ['Session', 'Pool', 'Step', 'split_segments', 'gather_videos', 'augmented', 'stagger_schedule', 'batch_noise']
 
 
 class Step:
@@ -153,6 +159,302 @@ class Session:
         if self.t == 0:
             raise RuntimeError("online.Session: result() before the first step")
         return self._sum / self.t, torch.stack(self._decisions, 1)
+
+
+class _Stream:
+    """One open stream of a `Pool`: its slot, its position and the clips run for it per main net (host side)."""
+    __slots__ = ('slot', 't', 'ran')
+
+    def __init__(self, slot, M):
+        self.slot, self.t, self.ran = slot, 0, [0] * M
+
+
+class Pool:
+    """Up to `capacity` streams that open, step and close independently, served in batched ticks.  `model`: an AdaMML in eval mode,
+    under torch.no_grad().
+
+        pool = model.online_pool(num_segments=10, capacity=8)
+        a = pool.open()                                       # draws the stream's noise as Session(model, S, 1) would
+        st = pool.step([a, b], x)                             # x: ONE segment per modality, row i the next segment of ids[i]
+        logits, decisions = pool.result(a)                    # [classes], [t, M]
+        pool.close(a)
+
+    A tick is `Session.step` over the n streams named, which may be at different positions t_i: the data layer and the policy
+    backbones on n rows, ONE `PolicyNet.decide`, each main net on the selected rows, the fusion and a per-stream running sum.  The
+    LSTM head is one workgroup per video from segment 0, so streams at different positions share its one launch: the pool keeps the
+    joint policy features and the noise rows of every slot ([S, capacity, ...]; the rows a stream has not reached hold zeros and
+    ones), hands `decide` the first max(t_i) + 1 rows of the n columns and reads row t_i of column i.  The FC heads have no
+    recurrence: they see the current row only.  Nothing was added to the C ABI.
+
+    Forced decisions behave as in `Session`: the segment's features are recorded, the decisions do not enter the recurrence."""
+
+    def __init__(self, model, num_segments, capacity=8):
+        if model.training:
+            raise RuntimeError("online.Pool: the model is in training mode; call model.eval() first")
+        if torch.is_grad_enabled():
+            raise RuntimeError("online.Pool: gradients are enabled; create and step the pool under torch.no_grad()")
+        S, C = int(num_segments), int(capacity)
+        if S < 1 or C < 1:
+            raise ValueError("online.Pool: num_segments %d and capacity %d must both be >= 1" % (S, C))
+        self.model, self.num_segments, self.capacity = model, S, C
+        M = self.num_modality = model.num_modality
+        dev = self.device = next(model.parameters()).device
+        self._lstm = not model.rng_policy and model.policy_net.causality_modeling is not None
+        # every slot's noise, segment-major: Exponential(1) rows [S, capacity, M, 2], or the rng_policy's uniforms [S, capacity, M]
+        self._noise = torch.ones((S, C, M) if model.rng_policy else (S, C, M, 2), dtype=torch.float32, device=dev)
+        self._decisions = torch.zeros(C, S, M, dtype=torch.float32, device=dev)
+        # allocated by the first tick, which knows their widths: the LSTM head's input (features [S, capacity, F], exactly 0 and
+        # noise [S, capacity, M, 2], exactly 1 in the rows a slot's stream has not reached) and the running sums [capacity, classes]
+        self._feats = self._live = self._sum = None
+        self._slots, self._streams, self._next_id = [None] * C, {}, 0
+        self._clips, self._ran, self.ticks = 0, [0] * M, 0
+        model.last_skip_stats = None
+
+    # -- streams ------------------------------------------------------------------------------------------------
+    def open(self, gumbel_exponential=None, rand=None):
+        """Takes a free slot and returns the new stream's id (ids are never reused, slots are).  The stream's noise is drawn as
+        `Session(model, S, 1)` draws it, from the same generator state; gumbel_exponential [S, M, 2] (segment-major for both head
+        variants) or, for an rng_policy model, rand [S, M] replaces the draw."""
+        model, S, M, dev = self.model, self.num_segments, self.num_modality, self.device
+        if None not in self._slots:
+            raise RuntimeError("online.Pool: all %d slots are in use (capacity = %d); close a stream first" % (self.capacity, self.capacity))
+        given, name, other = (rand, "rand", gumbel_exponential) if model.rng_policy else (gumbel_exponential, "gumbel_exponential", rand)
+        shape = (S, M) if model.rng_policy else (S, M, 2)
+        if other is not None:
+            raise ValueError("online.Pool: a model with rng_policy = %s takes %s, not %s"
+                             % (model.rng_policy, name, "gumbel_exponential" if model.rng_policy else "rand"))
+        if given is not None:
+            if tuple(given.shape) != shape:
+                raise ValueError("online.Pool: %s of shape %s, expected %s = %s"
+                                 % (name, tuple(given.shape), "[S, M]" if model.rng_policy else "[S, M, 2]", list(shape)))
+            noise = given.to(device=dev, dtype=torch.float32)
+        elif model.rng_policy:
+            noise = torch.rand((S, M, 1), dtype=torch.float32, device=dev).reshape(S, M)
+        else:
+            noise = torch.empty(S * M, 2, dtype=torch.float32, device=dev).exponential_()
+            # the rows of that draw are segment-major for the LSTM head and modality-major for the FC heads (Session._expo)
+            noise = noise.reshape(S, M, 2) if self._lstm else noise.reshape(M, S, 2).transpose(0, 1)
+        slot = self._slots.index(None)
+        self._noise[:, slot] = noise
+        if self._sum is not None:
+            self._sum[slot].zero_()
+        if self._feats is not None:
+            self._feats[:, slot].zero_()
+            self._live[:, slot].fill_(1.0)
+        sid, self._next_id = self._next_id, self._next_id + 1
+        self._slots[slot] = sid
+        self._streams[sid] = _Stream(slot, M)
+        return sid
+
+    def _stream(self, sid):
+        try:
+            return self._streams[sid]
+        except (KeyError, TypeError):
+            raise KeyError("online.Pool: no open stream with id %r" % (sid,)) from None
+
+    def close(self, sid):
+        """Frees the stream's slot for the next `open`; the id is unknown from here on."""
+        self._slots[self._stream(sid).slot] = None
+        del self._streams[sid]
+
+    def position(self, sid):
+        """The number of segments the stream has been stepped through."""
+        return self._stream(sid).t
+
+    def executed(self, sid):
+        """Clips run for this stream so far, per main net."""
+        return list(self._stream(sid).ran)
+
+    def result(self, sid):
+        """(logits [classes], decisions [t, M]) over the t segments of this stream seen: row `sid` of what `Session.result` returns."""
+        st = self._stream(sid)
+        if st.t == 0:
+            raise RuntimeError("online.Pool: result() of stream %r before its first step" % (sid,))
+        return self._sum[st.slot] / st.t, self._decisions[st.slot, :st.t].clone()
+
+    # -- one tick -----------------------------------------------------------------------------------------------
+    def _check(self, ids, x, decisions):
+        model, M = self.model, self.num_modality
+        ids = list(ids)
+        n = len(ids)
+        if n < 1:
+            raise ValueError("online.Pool: a step needs at least one stream")
+        streams = [self._stream(sid) for sid in ids]
+        if len(set(ids)) != n:
+            raise ValueError("online.Pool: a stream id occurs more than once in one step (%s)" % (ids,))
+        if not isinstance(x, (list, tuple)) or len(x) != len(model.modality):
+            raise ValueError("online.Pool: %d inputs for the model's %d modalities (%s)"
+                             % (len(x) if isinstance(x, (list, tuple)) else 1, len(model.modality), " ".join(model.modality)))
+        for x_, m in zip(x, model.modality):
+            if x_.size(0) != n:
+                raise ValueError("online.Pool: the %s input holds %d videos, the step names %d streams" % (m, x_.size(0), n))
+        for sid, st in zip(ids, streams):
+            if st.t >= self.num_segments:
+                raise RuntimeError("online.Pool: step %d of stream %r in a pool created for num_segments = %d"
+                                   % (st.t + 1, sid, self.num_segments))
+        if decisions is not None:
+            decisions = torch.as_tensor(decisions, dtype=torch.float32)
+            if tuple(decisions.shape) != (n, M):
+                raise ValueError("online.Pool: forced decisions of shape %s, expected [n, M] = [%d, %d]" % (tuple(decisions.shape), n, M))
+        return streams, decisions
+
+    def _record(self, cur, slots, tpos):
+        """Keeps the joint features [n, F] of the segments that arrived, and their noise rows, for the LSTM head's calls."""
+        if not self._lstm:
+            return
+        if self._feats is None:
+            S, C, M = self.num_segments, self.capacity, self.num_modality
+            self._feats = torch.zeros(S, C, cur.size(1), dtype=torch.float32, device=self.device)
+            self._live = torch.ones(S, C, M, 2, dtype=torch.float32, device=self.device)
+        self._feats.index_put_((tpos, slots), cur)
+        self._live.index_put_((tpos, slots), self._noise[tpos, slots])
+
+    def _decide(self, cur, slots, tpos, T):
+        """This tick's (decisions [n, M], policy logits [n, M, 2]): ONE `decide` for all positions.  cur: the joint features [n, F]
+        of the segments that arrived, recorded already; slots, tpos: [n] int64 on the device; T = max(tpos) on the host."""
+        pol, n = self.model.policy_net, cur.size(0)
+        if not self._lstm:
+            # FC heads: no recurrence, the current row only -- noise modality-major, as their `decide` reads it
+            dec, logits = pol.decide(cur[None], self._noise[tpos, slots].transpose(0, 1).reshape(self.num_modality, 1, n, 2).contiguous())
+            return dec[0].t(), logits[0].transpose(0, 1)
+        feats = self._feats[:T + 1].index_select(1, slots)                    # [T + 1, n, F]: column i is stream i from segment 0
+        expo = self._live[:T + 1].index_select(1, slots).transpose(1, 2)      # [T + 1, M, n, 2]
+        dec, logits = pol.decide(feats, expo.contiguous())
+        cols = torch.arange(n, device=self.device)
+        return dec[tpos, :, cols], logits[tpos, :, cols]                      # row t_i of column i
+
+    @torch.no_grad()
+    def step(self, ids, x, decisions=None):
+        """ids: n distinct open streams; x: ONE segment per modality holding n videos, row i the next segment of ids[i], in every
+        form `forward` accepts with num_segments = 1.  Returns a `Step` whose rows follow `ids`; `logits` row i is stream i's own
+        running mean.  A refused step launches nothing and leaves every stream where it was."""
+        start = time.perf_counter()
+        streams, forced = self._check(ids, x, decisions)
+        model, M, dev, n = self.model, self.num_modality, self.device, len(streams)
+        if model.training:
+            raise RuntimeError("online.Pool: the model was put into training mode while the pool was in use")
+        model._flat_policy.ensure(dev)
+        model._flat_main.ensure(dev)
+        index = torch.tensor([[st.slot for st in streams], [st.t for st in streams]], dtype=torch.int64).to(dev, non_blocking=True)
+        slots, tpos = index[0], index[1]
+        p_x, m_x, _ = model.data_layer(x, 1)
+        policy_logits = dec = None
+        if not model.rng_policy:
+            pol = model.policy_net
+            cur = pol.joint_net.features([p if p.dtype == torch.float32 else p.flatten(0, 1) for p in p_x], groups=1)
+            self._record(cur, slots, tpos)                                    # also when the decisions are forced, as in Session
+        if forced is not None:
+            dec = forced.to(dev)
+        elif model.rng_policy:
+            dec = (self._noise[tpos, slots] > model.rng_threshold).float()
+        else:
+            dec, policy_logits = self._decide(cur, slots, tpos, max(st.t for st in streams))
+            policy_logits = policy_logits.transpose(0, 1)                      # [M, n, 2]
+        dec = dec.t().contiguous()                                            # [M, n]
+        chosen = (dec > 0.5).tolist()                                         # host sync: the launch sizes depend on the decisions
+        decided = time.perf_counter() - start
+        stacked, ran = [], []
+        for m_i in range(M):
+            out, k = _run_selected(model.main_net.nets[m_i], m_x[m_i], dec[m_i], sum(chosen[m_i]), n)
+            stacked.append(out)
+            ran.append(k)
+        fused = model.main_net.fuse_segments(stacked, dec.reshape(1, M, n), 1)
+        if self._sum is None:
+            self._sum = torch.zeros(self.capacity, fused.size(1), dtype=torch.float32, device=dev)
+        self._sum.index_add_(0, slots, fused)
+        self._decisions.index_put_((slots, tpos), dec.t())
+        for i, st in enumerate(streams):
+            st.t += 1
+            st.ran = [a + int(chosen[m_i][i]) for m_i, a in enumerate(st.ran)]
+        self._clips, self._ran, self.ticks = self._clips + n, [a + b for a, b in zip(self._ran, ran)], self.ticks + 1
+        model.last_skip_stats = {"clips": self._clips, "executed_per_modality": list(self._ran)}
+        logits = self._sum.index_select(0, slots) / (tpos + 1).to(torch.float32)[:, None]
+        return Step(dec.t(), policy_logits, logits, ran, decided)
+
+
+def batch_noise(model, num_segments, batch_size, gumbel_exponential=None):
+    """The noise of ONE `Session(model, S, N)`, cut into what `Pool.open` takes: a list of N keyword dicts, entry j holding column j.
+    Drawn in one draw exactly as the session draws it (gumbel_exponential [S, M*N, 2] replaces the draw, read as the session reads
+    it), so N pool streams opened with these decide as the lock-step session from the same generator state decides."""
+    S, N, M = int(num_segments), int(batch_size), model.num_modality
+    dev = next(model.parameters()).device
+    if model.rng_policy:
+        rand = torch.rand((S, M, N), dtype=torch.float32, device=dev)
+        return [dict(rand=rand[:, :, j]) for j in range(N)]
+    if gumbel_exponential is None:
+        expo = torch.empty(S * M * N, 2, dtype=torch.float32, device=dev).exponential_()
+    else:
+        if gumbel_exponential.numel() != S * M * N * 2:
+            raise ValueError("online.batch_noise: gumbel_exponential holds %d values, [S, M*N, 2] = [%d, %d, 2] needs %d"
+                             % (gumbel_exponential.numel(), S, M * N, S * M * N * 2))
+        expo = gumbel_exponential.to(device=dev, dtype=torch.float32).contiguous()
+    if model.policy_net.causality_modeling is not None:
+        expo = expo.reshape(S, M, N, 2)
+    else:
+        expo = expo.reshape(M, S, N, 2).transpose(0, 1)
+    return [dict(gumbel_exponential=expo[:, :, j]) for j in range(N)]
+
+
+def stagger_schedule(n, num_segments, k):
+    """Which streams step when, for n streams of S = num_segments segments each, stream j opening at tick j * k: a list over the
+    ticks of [(stream, t), ...], stream j being at segment t at tick j * k + t.  k = 0 is lock-step (S ticks of all n streams), with
+    k >= S no two streams overlap; ticks in which no stream steps (k > S) are left out."""
+    n, S, k = int(n), int(num_segments), int(k)
+    if n < 1 or S < 1 or k < 0:
+        raise ValueError("stagger_schedule: n = %d and num_segments = %d must be >= 1, k = %d >= 0" % (n, S, k))
+    ticks = [[(j, tick - j * k) for j in range(n) if 0 <= tick - j * k < S] for tick in range((n - 1) * k + S)]
+    return [tick for tick in ticks if tick]
+
+
+# ---------------------------------------------------------------------------------------------------- gather_videos
+def augmented(piece):
+    """A step's per-modality input with every video.Frames / video.EncodedFrames entry turned into the video.Augmented it decodes
+    to (`video.augment`, on the device the entry is on); the other entries as they are.  What `gather_videos` does with such
+    entries on every call: a caller that takes rows of one piece in several ticks passes this instead, and decodes once."""
+    return [video.Augmented(video.augment(x), x.modality, x.k_out) if isinstance(x, (video.Frames, video.EncodedFrames)) else x
+            for x in piece]
+
+
+def _gather_one(entries):
+    """entries: [(x, row), ...] of ONE modality -> the input holding those rows, in the form of x."""
+    first = entries[0][0]
+    if isinstance(first, audio.Waveforms):
+        form, same = "Waveforms", lambda x: isinstance(x, audio.Waveforms)
+    elif isinstance(first, video.Augmented):
+        form, same = "Augmented", lambda x: isinstance(x, video.Augmented) and x.modality == first.modality and x.k_out == first.k_out
+    elif torch.is_tensor(first) and first.dtype in (torch.float32, torch.uint8):
+        form, same = "%s tensor" % str(first.dtype)[6:], lambda x: torch.is_tensor(x) and x.dtype == first.dtype
+    else:
+        what = "%s tensor" % str(first.dtype)[6:] if torch.is_tensor(first) else type(first).__name__
+        raise TypeError("gather_videos: expected float32 or uint8 tensors, Waveforms, Frames, EncodedFrames or Augmented, got a %s" % what)
+    for x, _ in entries:
+        if not same(x):
+            raise TypeError("gather_videos: the pieces of one modality differ in form: %s and %s"
+                            % (form, "%s tensor" % str(x.dtype)[6:] if torch.is_tensor(x) else type(x).__name__))
+    if form == "Waveforms":
+        return audio.Waveforms(torch.stack([x.wave[r] for x, r in entries]), torch.stack([x.missing[r] for x, r in entries]))
+    if form == "Augmented":
+        return video.Augmented(torch.stack([x.u8[r] for x, r in entries]), first.modality, first.k_out)
+    return torch.stack([x[r] for x, r in entries])
+
+
+def gather_videos(parts):
+    """parts: [(piece, row), ...], `piece` one element of `split_segments(...)` (ONE segment per modality of a batch of videos), row
+    a video of it.  Returns the per-modality input of a step made of those rows, in that order: what `Pool.step` takes when its
+    streams come from one loader's batches at different positions.  fp32 and uint8 frame tensors, audio.Waveforms (waves and missing
+    flags) and video.Augmented keep their form; video.Frames / video.EncodedFrames pieces are first turned into Augmented (`augmented`:
+    one decode per distinct piece and call -- pass `augmented(piece)` to decode once for several calls)."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("gather_videos: no (piece, row) given")
+    M = len(parts[0][0])
+    if any(len(piece) != M for piece, _ in parts):
+        raise ValueError("gather_videos: the pieces hold different numbers of modalities (%s)" % sorted({len(p) for p, _ in parts}))
+    decoded = {}
+    for piece, _ in parts:
+        if id(piece) not in decoded:
+            decoded[id(piece)] = augmented(piece)
+    return [_gather_one([(decoded[id(piece)][m], int(row)) for piece, row in parts]) for m in range(M)]
 
 
 def _run_selected(net, m_x, decisions, nsel, B):

@@ -152,6 +152,9 @@ def arg_parser():
     p.add_argument("--online", action="store_true",
                    help="with -e: step every validation batch through an online.Session, one segment at a time (adamml_amd/online.py), and "
                         "report the latency per segment step beside the validation line")
+    p.add_argument("--online_stagger", default=0, type=int, metavar="K",
+                   help="with -e --online: K >= 1 serves every validation batch through an online.Pool instead, video j starting K steps "
+                        "after video j - 1, the videos of a step batched whatever their positions; 0: lock-step through a Session")
     p.add_argument("--imagenet_weights", default=[], nargs="+", metavar="ARCH=PATH",
                    help="local torchvision ImageNet state_dict files the reference would download (models/resnet.py:251-257, "
                         "models/policy_net.py:193-203,221): resnet50=PATH mobilenet_v2=PATH mobilenetv2_160x160=PATH; also $ADAMML_IMAGENET_DIR")
@@ -413,7 +416,12 @@ def validate_report(loader, ddp, args, num_segments):
 
     With args.online every batch is split into its segments (online.split_segments) and stepped through an online.Session instead of one
     forward; the report then carries "online": mean / maximum milliseconds per segment step (each step waited for on the device) and the
-    mean time to a batch's first decision, over this rank's batches."""
+    mean time to a batch's first decision, over this rank's batches.
+
+    With args.online_stagger = K >= 1 the batch goes through an online.Pool of capacity = its size instead, video j opening K steps
+    after video j - 1 (online.stagger_schedule), each step made of the rows that are due (online.gather_videos).  The batch's noise is
+    drawn in one draw as the Session draws it and stream j takes its column (online.batch_noise): the decisions are those of the
+    lock-step run from the same seed.  "online" then also carries "streams_per_step_mean"."""
     model = ddp.module
     model.eval()
     device = next(model.parameters()).device
@@ -422,11 +430,33 @@ def validate_report(loader, ddp, args, num_segments):
     loss_m, time_m = Meter(), Meter()
     executed, total = None, 0
     stepwise, step_ms, first_ms = getattr(args, "online", False), [], []
+    stagger, stream_steps = getattr(args, "online_stagger", 0) if stepwise else 0, 0
     end = time.time()
     for images, target in loader:
         target = target.to(device, non_blocking=True)
         model.last_skip_stats = None
-        if stepwise:
+        if stagger:
+            N = target.size(0)
+            pool = model.online_pool(num_segments, capacity=N)
+            noise = online.batch_noise(model, num_segments, N)
+            pieces, ready, sids = online.split_segments(images, num_segments), {}, {}
+            for tick in online.stagger_schedule(N, num_segments, stagger):
+                torch.cuda.synchronize(device)
+                t0 = time.perf_counter()
+                for j, t in tick:
+                    if t == 0:
+                        sids[j] = pool.open(**noise[j])
+                    if t not in ready:                                        # a segment's piece is copied and decoded once
+                        ready[t] = online.augmented([x.to(device, non_blocking=True) for x in pieces[t]])
+                step = pool.step([sids[j] for j, _ in tick], online.gather_videos([(ready[t], j) for j, t in tick]))
+                torch.cuda.synchronize(device)
+                step_ms.append((time.perf_counter() - t0) * 1000.0)
+                stream_steps += len(tick)
+                if pool.ticks == 1:
+                    first_ms.append(step.decision_seconds * 1000.0)
+            results = [pool.result(sids[j]) for j in range(N)]
+            output, selection = torch.stack([r[0] for r in results]), torch.stack([r[1] for r in results])
+        elif stepwise:
             session = model.online(num_segments, target.size(0))
             for piece in online.split_segments(images, num_segments):
                 torch.cuda.synchronize(device)
@@ -470,6 +500,8 @@ def validate_report(loader, ddp, args, num_segments):
     if stepwise:
         report["online"] = {"step_ms_mean": sum(step_ms) / max(len(step_ms), 1), "step_ms_max": max(step_ms, default=0.0),
                             "first_decision_ms": sum(first_ms) / max(len(first_ms), 1), "steps": len(step_ms)}
+        if stagger:
+            report["online"]["streams_per_step_mean"] = stream_steps / max(len(step_ms), 1)
     return report
 
 
@@ -489,15 +521,24 @@ def report_line(head, r):
 def online_line(head, r):
     """The --online line behind the validation line: wall time per segment step and to a batch's first decision."""
     o = r["online"]
-    return "{}: \tOnline: {:.2f} ms/segment (max {:.2f}) over {} steps\tFirst decision: {:.2f} ms".format(
+    line = "{}: \tOnline: {:.2f} ms/segment (max {:.2f}) over {} steps\tFirst decision: {:.2f} ms".format(
         head, o["step_ms_mean"], o["step_ms_max"], o["steps"], o["first_decision_ms"])
+    if "streams_per_step_mean" in o:                                         # --online_stagger: a step serves the videos that are due
+        line += "\tStreams/step: {:.2f}".format(o["streams_per_step_mean"])
+    return line
 
 
 def check_online(args):
-    """--online steps the VALIDATION batches: without -e there is nothing for it to do."""
+    """--online steps the VALIDATION batches: without -e there is nothing for it to do; --online_stagger says how --online serves them."""
     if getattr(args, "online", False) and not args.evaluate:
         raise SystemExit("--online is valid only with -e / --evaluate: it steps the validation batches through an online.Session; "
                          "training needs all segments of a video at once")
+    stagger = getattr(args, "online_stagger", 0)
+    if stagger < 0:
+        raise SystemExit("--online_stagger %d: the number of steps between two videos' starts cannot be negative" % stagger)
+    if stagger and not (args.evaluate and getattr(args, "online", False)):
+        raise SystemExit("--online_stagger is valid only with -e --online: it staggers the videos of the validation batches that --online "
+                         "steps (through an online.Pool instead of a Session)")
 
 
 def save_selections(path, args, r):

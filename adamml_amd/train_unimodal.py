@@ -41,8 +41,8 @@ def resolve_args(args):
     if args.backbone_net == "adamml":
         raise SystemExit("adamml_amd.train_unimodal trains ONE backbone (--backbone_net resnet | sound_mobilenet_v2); "
                          "--backbone_net adamml is adamml_amd.train: python3 train_adamml.py ...")
-    if getattr(args, "online", False):
-        raise SystemExit("--online steps AdaMML's policy one segment at a time; a single backbone has no policy: "
+    if getattr(args, "online", False) or getattr(args, "online_stagger", 0):
+        raise SystemExit("--online / --online_stagger step AdaMML's policy one segment at a time; a single backbone has no policy: "
                          "python3 train_adamml.py -e --online ...")
     if args.threed_data:
         raise SystemExit("--threed_data: the registry holds 2-D backbones only (resnet, sound_mobilenet_v2), and their forward takes "
