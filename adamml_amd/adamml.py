@@ -21,6 +21,39 @@ def _frames(t):
     return t if t.dtype == torch.float32 else t.flatten(0, 1)
 
 
+def run_selected(net, m_x, selected, S, B, nsel=None, pad_to=0):
+    """One main net on exactly the clips whose decision is 1.  m_x: the data layer's tensor for this net, S segments of B videos
+    ([S, B*F, H, W, C] bf16, or the one-channel fp32 form [B, S, H, W]); selected: the S*B decisions, segment-major (s*B + b);
+    nsel: how many of them are 1, where the caller knows it on the host already (None: read here, a host sync either way -- the
+    launch sizes depend on it).  Returns ([S*B, classes] fp32 logits, exactly 0 for the clips not run, and the number run).
+    Nothing is launched on the net when no clip is selected, and the whole input goes through as it is when all are.  Exact:
+    eval-mode BatchNorm is a per-sample affine map, so a clip's logits do not depend on which other clips share the launch.
+    pad_to = 8 repeats the first selected clip up to the next multiple of 8 (the duplicates' logits overwrite identical values):
+    launch plans are per call shape, and the whole-video forward keeps the distinct shapes few this way; a stream of one video
+    would run 8 clips per segment, so the online steps pass 0."""
+    raw32 = m_x.dtype == torch.float32
+    frames = _frames(m_x)                                                     # [S*B*F, H, W, C], clips contiguous
+    idx = None
+    if nsel is None:
+        idx = (selected > 0.5).nonzero().flatten()
+        nsel = int(idx.numel())
+    if nsel == S * B:
+        return net.forward_nhwc(frames, S if raw32 else 1), nsel              # (eval BatchNorm: the grouping is immaterial)
+    ncls = net.fc.out_features if hasattr(net, "fc") else net.classifier[1].out_features
+    out = torch.zeros(S * B, ncls, dtype=torch.float32, device=m_x.device)
+    if nsel > 0:
+        if idx is None:
+            idx = (selected > 0.5).nonzero().flatten()
+        if pad_to and nsel % pad_to:
+            idx = torch.cat([idx, idx[:1].expand(pad_to - nsel % pad_to)])
+        if raw32:
+            sel = frames.transpose(0, 1).reshape(S * B, 1, *frames.shape[2:]).index_select(0, idx)      # [n, 1, H, W]: one group
+        else:
+            sel = frames.view(S * B, frames.shape[0] // (S * B), *frames.shape[1:]).index_select(0, idx).flatten(0, 1)
+        out.index_copy_(0, idx, net.forward_nhwc(sel, 1))
+    return out, nsel
+
+
 class AdaMML(nn.Module, MeanStdMixin, StockDDPAware):
 
     def __init__(self, policy_net, main_net, num_frames, num_segments, modality, rng_policy, rng_threshold, num_classes,
@@ -230,8 +263,7 @@ class AdaMML(nn.Module, MeanStdMixin, StockDDPAware):
                     decisions, decision_logits = self.policy_net.decide(list(joint.view(S, -1, joint.shape[-1]).unbind(0)), gumbel_exponential)
                 self.last_policy_logits = decision_logits
             else:
-                decisions = (torch.rand((num_segments, self.num_modality, x[0].size(0)), dtype=torch.float32, device=dev)
-                             > self.rng_threshold).float()
+                decisions = self._rng_decisions(num_segments, x[0].size(0), dev)
             main.wait_stream(side)
             main.wait_stream(pside)
             for t in [decisions] + list(stacked):
@@ -248,8 +280,7 @@ class AdaMML(nn.Module, MeanStdMixin, StockDDPAware):
                 decisions, decision_logits = self.policy_net.decide(self.policy_net.all_segment_features(p_x), gumbel_exponential)
             self.last_policy_logits = decision_logits
         else:
-            decisions = (torch.rand((num_segments, self.num_modality, x[0].size(0)), dtype=torch.float32, device=dev)
-                         > self.rng_threshold).float()
+            decisions = self._rng_decisions(num_segments, x[0].size(0), dev)
         if side is not None:
             main.wait_stream(side)
             main.wait_stream(pside)
@@ -258,39 +289,24 @@ class AdaMML(nn.Module, MeanStdMixin, StockDDPAware):
         final_logits = self.main_net.fuse_segments(stacked, decisions, num_segments)
         return final_logits, decisions.permute((2, 0, 1))
 
+    def _rng_decisions(self, S, B, dev):
+        """The rng_policy's decisions [S, M, B]: each clip kept with probability 1 - rng_threshold (one torch.rand of that shape)."""
+        return (torch.rand((S, self.num_modality, B), dtype=torch.float32, device=dev) > self.rng_threshold).float()
+
     def _forward_skipping(self, x, p_x, m_x, num_segments, gumbel_exponential):
         """Eval-mode forward with decision-driven compaction: the decisions are taken first, then each main net only sees
-        the (segment, video) clips whose decision is 1 -- the compute saving AdaMML is about.  Exact: eval-mode BatchNorm is
-        a per-sample affine map, so a clip's logits do not depend on which other clips share the launch, and the skipped
-        clips' logits are multiplied by 0 in the reference (joint_resnet_mobilenetv2.py:94)."""
+        the (segment, video) clips whose decision is 1 (`run_selected`) -- the compute saving AdaMML is about.  Exact: the
+        skipped clips' logits are multiplied by 0 in the reference (joint_resnet_mobilenetv2.py:94)."""
         S, B, dev = num_segments, x[0].size(0), x[0].device
         if not self.rng_policy:
             decisions, decision_logits = self.policy_net.decide(self.policy_net.all_segment_features(p_x), gumbel_exponential)
             self.last_policy_logits = decision_logits
         else:
-            decisions = (torch.rand((S, self.num_modality, B), dtype=torch.float32, device=dev) > self.rng_threshold).float()
+            decisions = self._rng_decisions(S, B, dev)
+        pad_to = 8 if plan.ENABLED and plan.EVAL_ENABLED else 0
         stacked, ran = [], []
         for m_i in range(self.num_modality):
-            net = self.main_net.nets[m_i]
-            raw32 = m_x[m_i].dtype == torch.float32                           # one-channel fp32 input [B, S, H, W] (data_layer)
-            frames = _frames(m_x[m_i])                                        # [S*B*F, H, W, C], clips contiguous
-            fpc = 1 if raw32 else frames.shape[0] // (S * B)
-            idx = (decisions[:, m_i, :].reshape(-1) > 0.5).nonzero().flatten()      # host sync: the launch sizes depend on it
-            ncls = net.fc.out_features if hasattr(net, "fc") else net.classifier[1].out_features
-            out = torch.zeros(S * B, ncls, dtype=torch.float32, device=dev)
-            if idx.numel() == S * B:
-                out = net.forward_nhwc(frames, S if raw32 else 1)             # (eval BatchNorm: the grouping is immaterial)
-            nsel = int(idx.numel())
-            if 0 < nsel < S * B:
-                if plan.ENABLED and plan.EVAL_ENABLED and idx.numel() % 8:
-                    # launch plans are per call shape: pad the selected clips to a multiple of 8 (the first one repeated; eval BatchNorm is
-                    # per sample, the duplicates' logits overwrite identical values) so that few distinct shapes occur
-                    idx = torch.cat([idx, idx[:1].expand(8 - idx.numel() % 8)])
-                if raw32:
-                    sel = frames.transpose(0, 1).reshape(S * B, 1, *frames.shape[2:]).index_select(0, idx)      # [n, 1, H, W]: one group
-                else:
-                    sel = frames.view(S * B, fpc, *frames.shape[1:]).index_select(0, idx).flatten(0, 1)
-                out.index_copy_(0, idx, net.forward_nhwc(sel, 1))
+            out, nsel = run_selected(self.main_net.nets[m_i], m_x[m_i], decisions[:, m_i, :].reshape(-1), S, B, pad_to=pad_to)
             stacked.append(out)
             ran.append(nsel)
         self.last_skip_stats = {"clips": S * B, "executed_per_modality": ran}

@@ -8,8 +8,9 @@
         logits, decisions = session.result()                          # what forward returns for the segments seen
 
 `AdaMML.forward` needs all S segments of a video before it returns anything.  The policy is causal (an LSTM over the segments
-seen), so the decision for segment t can be taken when segment t arrives, the main nets can run on exactly the clips it selects,
-and a running prediction exists after every segment.
+seen), so the decision for segment t can be taken when segment t arrives, the main nets can run on exactly the clips it selects
+(`run_selected` of adamml_amd/adamml.py, the runner of the whole-video eval forward, with S = 1), and a running prediction exists
+after every segment.
 
 No state is carried between the steps on the device side and nothing was added to the C ABI: the head is ONE tiny launch
 (adamml_policy_head_fwd) whose per-video recurrence runs inside the kernel.  The session keeps the joint policy features of the
@@ -30,6 +31,7 @@ import time
 import torch
 
 from . import audio, jpeg, video
+from .adamml import run_selected
 
 __all__ = ['Session', 'Pool', 'Step', 'split_segments', 'gather_videos', 'augmented', 'stagger_schedule', 'batch_noise']
 
@@ -49,13 +51,80 @@ class Step:
         return "Step(decisions %s, logits %s, executed %s)" % (tuple(self.decisions.shape), tuple(self.logits.shape), self.executed)
 
 
+def _draw_noise(who, model, S, N, gumbel_exponential=None):
+    """The policy's noise for N videos of S segments, drawn exactly as one `forward` call draws it, from the same generator state
+    (Gumbel policy: torch.empty(S*M*N, 2).exponential_(); rng_policy: torch.rand((S, M, N))); gumbel_exponential [S, M*N, 2]
+    replaces the Gumbel draw, as in `forward`.  Returned segment-major for both head variants, [S, M, N, 2] (or [S, M, N] for the
+    rng_policy): the rows of the draw are segment-major for the LSTM head and modality-major for the FC heads (`PolicyNet.decide`)."""
+    M, dev = model.num_modality, next(model.parameters()).device
+    if model.rng_policy:
+        return torch.rand((S, M, N), dtype=torch.float32, device=dev)
+    if gumbel_exponential is None:
+        expo = torch.empty(S * M * N, 2, dtype=torch.float32, device=dev).exponential_()
+    else:
+        if gumbel_exponential.numel() != S * M * N * 2:
+            raise ValueError("%s: gumbel_exponential holds %d values, [S, M*N, 2] = [%d, %d, 2] needs %d"
+                             % (who, gumbel_exponential.numel(), S, M * N, S * M * N * 2))
+        expo = gumbel_exponential.to(device=dev, dtype=torch.float32).contiguous()
+    if model.policy_net.causality_modeling is not None:
+        return expo.reshape(S, M, N, 2)
+    return expo.reshape(M, S, N, 2).transpose(0, 1)
+
+
+def _accept(who, model, x, n, held, decisions):
+    """The refusals the two `step` methods share, before anything is launched.  x: the step's input; n: the videos it must hold
+    (`held` says why, for the message); decisions: the forced decisions or None, returned as an fp32 [n, M] tensor."""
+    if not isinstance(x, (list, tuple)) or len(x) != len(model.modality):
+        raise ValueError("%s: %d inputs for the model's %d modalities (%s)"
+                         % (who, len(x) if isinstance(x, (list, tuple)) else 1, len(model.modality), " ".join(model.modality)))
+    for x_, m in zip(x, model.modality):
+        if x_.size(0) != n:
+            raise ValueError("%s: the %s input holds %d videos, %s" % (who, m, x_.size(0), held))
+    if decisions is not None:
+        decisions = torch.as_tensor(decisions, dtype=torch.float32)
+        if tuple(decisions.shape) != (n, model.num_modality):
+            raise ValueError("%s: forced decisions of shape %s, expected [N, M] = [%d, %d]"
+                             % (who, tuple(decisions.shape), n, model.num_modality))
+    if model.training:
+        raise RuntimeError("%s: the model was put into training mode; call model.eval() before the next step" % who)
+    return decisions
+
+
+def _segment(model, x, n, forced, policy, start):
+    """ONE segment of n videos through the model, the body of both `step` methods.  x: an accepted input (`_accept`); forced: its
+    decisions [n, M] or None; policy(cur, decide): the caller's state -- it keeps the joint policy features cur [n, F] of this
+    segment (None for an rng_policy model) and, if `decide`, returns this segment's (decisions [M, n], policy logits [M, n, 2] or
+    None); start: time.perf_counter() on entering `step`.  Returns the decisions [M, n], the policy logits, the fused logits
+    [n, classes] of this segment, the clips run per main net, the per-video flags behind those counts (M lists of n, on the host)
+    and the seconds from `start` until the decisions were known on the host."""
+    M, dev = model.num_modality, next(model.parameters()).device
+    model._flat_policy.ensure(dev)
+    model._flat_main.ensure(dev)
+    p_x, m_x, _ = model.data_layer(x, 1)
+    cur = None
+    if not model.rng_policy:
+        # the policy backbones on this segment, one BatchNorm group; kept also when the decisions are forced
+        cur = model.policy_net.joint_net.features([p if p.dtype == torch.float32 else p.flatten(0, 1) for p in p_x], groups=1)
+    dec, policy_logits = policy(cur, forced is None)
+    if forced is not None:
+        dec = forced.to(dev).t().contiguous()                                 # [M, n]
+    chosen = (dec > 0.5).tolist()                                             # host sync: the launch sizes depend on the decisions
+    decided = time.perf_counter() - start
+    stacked, ran = [], []
+    for m_i in range(M):
+        out, k = run_selected(model.main_net.nets[m_i], m_x[m_i], dec[m_i], 1, n, nsel=sum(chosen[m_i]))
+        stacked.append(out)
+        ran.append(k)
+    return dec, policy_logits, model.main_net.fuse_segments(stacked, dec.reshape(1, M, n), 1), ran, chosen, decided
+
+
 class Session:
     """One batch of N = batch_size videos, served for at most num_segments steps.  `model`: an AdaMML in eval mode, under
     torch.no_grad().
 
-    The constructor draws the policy's randomness exactly as one `forward` call would, from the same generator state (Gumbel
-    policy: torch.empty(S*M*N, 2).exponential_(); rng_policy: torch.rand((S, M, N))): a session and a forward started from the same
-    seed see the same noise.  gumbel_exponential [S, M*N, 2] replaces the draw, as in `forward`.
+    The constructor draws the policy's randomness exactly as one `forward` call would, from the same generator state
+    (`_draw_noise`): a session and a forward started from the same seed see the same noise.  gumbel_exponential [S, M*N, 2]
+    replaces the draw, as in `forward`.
 
     Everything runs on the current stream.  `step(x, decisions=...)` forces this step's decisions (an external policy, a test); the
     policy features of the segment are still recorded, but forced decisions do not enter the LSTM's recurrence: a later unforced
@@ -71,48 +140,25 @@ class Session:
             raise ValueError("online.Session: num_segments %d and batch_size %d must both be >= 1" % (S, N))
         self.model, self.num_segments, self.batch_size, self.t = model, S, N, 0
         M = self.num_modality = model.num_modality
-        dev = self.device = next(model.parameters()).device
-        self._rand = self._expo = None
-        if model.rng_policy:
-            self._rand = torch.rand((S, M, N), dtype=torch.float32, device=dev)
-            self._lstm = False
-        else:
-            if gumbel_exponential is None:
-                expo = torch.empty(S * M * N, 2, dtype=torch.float32, device=dev).exponential_()
-            else:
-                if gumbel_exponential.numel() != S * M * N * 2:
-                    raise ValueError("online.Session: gumbel_exponential holds %d values, [S, M*N, 2] = [%d, %d, 2] needs %d"
-                                     % (gumbel_exponential.numel(), S, M * N, S * M * N * 2))
-                expo = gumbel_exponential.to(device=dev, dtype=torch.float32).contiguous()
-            # the row order `PolicyNet.decide` reads: segment-major for the LSTM head, modality-major for the FC heads
-            self._lstm = model.policy_net.causality_modeling is not None
-            self._expo = expo.reshape(S, M, N, 2) if self._lstm else expo.reshape(M, S, N, 2)
+        self.device = next(model.parameters()).device
+        noise = _draw_noise("online.Session", model, S, N, gumbel_exponential)
+        self._rand, self._expo = (noise, None) if model.rng_policy else (None, noise)
+        self._lstm = not model.rng_policy and model.policy_net.causality_modeling is not None
         self._feats, self._decisions, self._sum, self._ran = [], [], None, [0] * M
         model.last_skip_stats = None
 
     # -- one segment --------------------------------------------------------------------------------------------
-    def _check(self, x, decisions):
-        model, N, M = self.model, self.batch_size, self.num_modality
-        if self.t >= self.num_segments:
-            raise RuntimeError("online.Session: step %d of a session created for num_segments = %d" % (self.t + 1, self.num_segments))
-        if not isinstance(x, (list, tuple)) or len(x) != len(model.modality):
-            raise ValueError("online.Session: %d inputs for the model's %d modalities (%s)"
-                             % (len(x) if isinstance(x, (list, tuple)) else 1, len(model.modality), " ".join(model.modality)))
-        for x_, m in zip(x, model.modality):
-            if x_.size(0) != N:
-                raise ValueError("online.Session: the %s input holds %d videos, the session was created for batch_size = %d"
-                                 % (m, x_.size(0), N))
-        if decisions is not None:
-            decisions = torch.as_tensor(decisions, dtype=torch.float32)
-            if tuple(decisions.shape) != (N, M):
-                raise ValueError("online.Session: forced decisions of shape %s, expected [N, M] = [%d, %d]" % (tuple(decisions.shape), N, M))
-        return decisions
-
-    def _decide(self):
-        """This step's (decisions [M, N], policy logits [M, N, 2]) from the features seen so far."""
+    def _policy(self, cur, decide):
+        """Keeps this segment's features; this step's (decisions [M, N], policy logits [M, N, 2]) from the features seen so far."""
         model, t = self.model, self.t
+        if cur is not None:
+            self._feats.append(cur)
+        if not decide:
+            return None, None
+        if model.rng_policy:
+            return (self._rand[t] > model.rng_threshold).float(), None
         feats = torch.stack(self._feats, 0)                                   # [t + 1, N, F]
-        expo = self._expo[:t + 1] if self._lstm else self._expo[:, :t + 1]
+        expo = self._expo[:t + 1] if self._lstm else self._expo[:t + 1].transpose(0, 1)      # the FC heads read it modality-major
         dec, logits = model.policy_net.decide(feats, expo.contiguous())
         model.last_policy_logits = logits                                    # [t + 1, M, N, 2], as forward leaves it
         return dec[t], logits[t]
@@ -121,32 +167,11 @@ class Session:
     def step(self, x, decisions=None):
         """x: ONE segment per modality, in every form `forward` accepts with num_segments = 1.  Returns a `Step`."""
         start = time.perf_counter()
-        forced = self._check(x, decisions)
-        model, N, M, dev = self.model, self.batch_size, self.num_modality, self.device
-        if model.training:
-            raise RuntimeError("online.Session: the model was put into training mode during the session")
-        model._flat_policy.ensure(dev)
-        model._flat_main.ensure(dev)
-        p_x, m_x, _ = model.data_layer(x, 1)
-        policy_logits = None
-        if not model.rng_policy:
-            # the policy backbones on this segment, one BatchNorm group; the joint feature is kept for the later steps' head calls
-            pol = model.policy_net
-            self._feats.append(pol.joint_net.features([p if p.dtype == torch.float32 else p.flatten(0, 1) for p in p_x], groups=1))
-        if forced is not None:
-            dec = forced.to(dev).t().contiguous()                             # [M, N]
-        elif model.rng_policy:
-            dec = (self._rand[self.t] > model.rng_threshold).float()
-        else:
-            dec, policy_logits = self._decide()
-        counts = (dec > 0.5).sum(1).tolist()                                  # host sync: the launch sizes depend on the decisions
-        decided = time.perf_counter() - start
-        stacked, ran = [], []
-        for m_i in range(M):
-            out, n = _run_selected(model.main_net.nets[m_i], m_x[m_i], dec[m_i], counts[m_i], N)
-            stacked.append(out)
-            ran.append(n)
-        fused = model.main_net.fuse_segments(stacked, dec.reshape(1, M, N), 1)
+        model, N = self.model, self.batch_size
+        if self.t >= self.num_segments:
+            raise RuntimeError("online.Session: step %d of a session created for num_segments = %d" % (self.t + 1, self.num_segments))
+        forced = _accept("online.Session", model, x, N, "the session was created for batch_size = %d" % N, decisions)
+        dec, policy_logits, fused, ran, _, decided = _segment(model, x, N, forced, self._policy, start)
         self._sum = fused if self._sum is None else self._sum + fused
         self._decisions.append(dec.t())
         self._ran = [a + b for a, b in zip(self._ran, ran)]
@@ -228,12 +253,8 @@ class Pool:
                 raise ValueError("online.Pool: %s of shape %s, expected %s = %s"
                                  % (name, tuple(given.shape), "[S, M]" if model.rng_policy else "[S, M, 2]", list(shape)))
             noise = given.to(device=dev, dtype=torch.float32)
-        elif model.rng_policy:
-            noise = torch.rand((S, M, 1), dtype=torch.float32, device=dev).reshape(S, M)
         else:
-            noise = torch.empty(S * M, 2, dtype=torch.float32, device=dev).exponential_()
-            # the rows of that draw are segment-major for the LSTM head and modality-major for the FC heads (Session._expo)
-            noise = noise.reshape(S, M, 2) if self._lstm else noise.reshape(M, S, 2).transpose(0, 1)
+            noise = _draw_noise("online.Pool", model, S, 1)[:, :, 0]
         slot = self._slots.index(None)
         self._noise[:, slot] = noise
         if self._sum is not None:
@@ -273,31 +294,6 @@ class Pool:
         return self._sum[st.slot] / st.t, self._decisions[st.slot, :st.t].clone()
 
     # -- one tick -----------------------------------------------------------------------------------------------
-    def _check(self, ids, x, decisions):
-        model, M = self.model, self.num_modality
-        ids = list(ids)
-        n = len(ids)
-        if n < 1:
-            raise ValueError("online.Pool: a step needs at least one stream")
-        streams = [self._stream(sid) for sid in ids]
-        if len(set(ids)) != n:
-            raise ValueError("online.Pool: a stream id occurs more than once in one step (%s)" % (ids,))
-        if not isinstance(x, (list, tuple)) or len(x) != len(model.modality):
-            raise ValueError("online.Pool: %d inputs for the model's %d modalities (%s)"
-                             % (len(x) if isinstance(x, (list, tuple)) else 1, len(model.modality), " ".join(model.modality)))
-        for x_, m in zip(x, model.modality):
-            if x_.size(0) != n:
-                raise ValueError("online.Pool: the %s input holds %d videos, the step names %d streams" % (m, x_.size(0), n))
-        for sid, st in zip(ids, streams):
-            if st.t >= self.num_segments:
-                raise RuntimeError("online.Pool: step %d of stream %r in a pool created for num_segments = %d"
-                                   % (st.t + 1, sid, self.num_segments))
-        if decisions is not None:
-            decisions = torch.as_tensor(decisions, dtype=torch.float32)
-            if tuple(decisions.shape) != (n, M):
-                raise ValueError("online.Pool: forced decisions of shape %s, expected [n, M] = [%d, %d]" % (tuple(decisions.shape), n, M))
-        return streams, decisions
-
     def _record(self, cur, slots, tpos):
         """Keeps the joint features [n, F] of the segments that arrived, and their noise rows, for the LSTM head's calls."""
         if not self._lstm:
@@ -310,18 +306,18 @@ class Pool:
         self._live.index_put_((tpos, slots), self._noise[tpos, slots])
 
     def _decide(self, cur, slots, tpos, T):
-        """This tick's (decisions [n, M], policy logits [n, M, 2]): ONE `decide` for all positions.  cur: the joint features [n, F]
+        """This tick's (decisions [M, n], policy logits [M, n, 2]): ONE `decide` for all positions.  cur: the joint features [n, F]
         of the segments that arrived, recorded already; slots, tpos: [n] int64 on the device; T = max(tpos) on the host."""
         pol, n = self.model.policy_net, cur.size(0)
         if not self._lstm:
             # FC heads: no recurrence, the current row only -- noise modality-major, as their `decide` reads it
             dec, logits = pol.decide(cur[None], self._noise[tpos, slots].transpose(0, 1).reshape(self.num_modality, 1, n, 2).contiguous())
-            return dec[0].t(), logits[0].transpose(0, 1)
+            return dec[0].contiguous(), logits[0]
         feats = self._feats[:T + 1].index_select(1, slots)                    # [T + 1, n, F]: column i is stream i from segment 0
         expo = self._live[:T + 1].index_select(1, slots).transpose(1, 2)      # [T + 1, M, n, 2]
         dec, logits = pol.decide(feats, expo.contiguous())
         cols = torch.arange(n, device=self.device)
-        return dec[tpos, :, cols], logits[tpos, :, cols]                      # row t_i of column i
+        return dec[tpos, :, cols].t().contiguous(), logits[tpos, :, cols].transpose(0, 1)       # row t_i of column i
 
     @torch.no_grad()
     def step(self, ids, x, decisions=None):
@@ -329,36 +325,31 @@ class Pool:
         form `forward` accepts with num_segments = 1.  Returns a `Step` whose rows follow `ids`; `logits` row i is stream i's own
         running mean.  A refused step launches nothing and leaves every stream where it was."""
         start = time.perf_counter()
-        streams, forced = self._check(ids, x, decisions)
-        model, M, dev, n = self.model, self.num_modality, self.device, len(streams)
-        if model.training:
-            raise RuntimeError("online.Pool: the model was put into training mode while the pool was in use")
-        model._flat_policy.ensure(dev)
-        model._flat_main.ensure(dev)
+        model, dev, ids = self.model, self.device, list(ids)
+        n = len(ids)
+        if n < 1:
+            raise ValueError("online.Pool: a step needs at least one stream")
+        streams = [self._stream(sid) for sid in ids]
+        if len(set(ids)) != n:
+            raise ValueError("online.Pool: a stream id occurs more than once in one step (%s)" % (ids,))
+        for sid, st in zip(ids, streams):
+            if st.t >= self.num_segments:
+                raise RuntimeError("online.Pool: step %d of stream %r in a pool created for num_segments = %d"
+                                   % (st.t + 1, sid, self.num_segments))
+        forced = _accept("online.Pool", model, x, n, "the step names %d streams" % n, decisions)
         index = torch.tensor([[st.slot for st in streams], [st.t for st in streams]], dtype=torch.int64).to(dev, non_blocking=True)
         slots, tpos = index[0], index[1]
-        p_x, m_x, _ = model.data_layer(x, 1)
-        policy_logits = dec = None
-        if not model.rng_policy:
-            pol = model.policy_net
-            cur = pol.joint_net.features([p if p.dtype == torch.float32 else p.flatten(0, 1) for p in p_x], groups=1)
-            self._record(cur, slots, tpos)                                    # also when the decisions are forced, as in Session
-        if forced is not None:
-            dec = forced.to(dev)
-        elif model.rng_policy:
-            dec = (self._noise[tpos, slots] > model.rng_threshold).float()
-        else:
-            dec, policy_logits = self._decide(cur, slots, tpos, max(st.t for st in streams))
-            policy_logits = policy_logits.transpose(0, 1)                      # [M, n, 2]
-        dec = dec.t().contiguous()                                            # [M, n]
-        chosen = (dec > 0.5).tolist()                                         # host sync: the launch sizes depend on the decisions
-        decided = time.perf_counter() - start
-        stacked, ran = [], []
-        for m_i in range(M):
-            out, k = _run_selected(model.main_net.nets[m_i], m_x[m_i], dec[m_i], sum(chosen[m_i]), n)
-            stacked.append(out)
-            ran.append(k)
-        fused = model.main_net.fuse_segments(stacked, dec.reshape(1, M, n), 1)
+
+        def policy(cur, decide):
+            if cur is not None:
+                self._record(cur, slots, tpos)                                # also when the decisions are forced, as in Session
+            if not decide:
+                return None, None
+            if model.rng_policy:
+                return (self._noise[tpos, slots] > model.rng_threshold).float().t().contiguous(), None
+            return self._decide(cur, slots, tpos, max(st.t for st in streams))
+
+        dec, policy_logits, fused, ran, chosen, decided = _segment(model, x, n, forced, policy, start)
         if self._sum is None:
             self._sum = torch.zeros(self.capacity, fused.size(1), dtype=torch.float32, device=dev)
         self._sum.index_add_(0, slots, fused)
@@ -376,23 +367,9 @@ def batch_noise(model, num_segments, batch_size, gumbel_exponential=None):
     """The noise of ONE `Session(model, S, N)`, cut into what `Pool.open` takes: a list of N keyword dicts, entry j holding column j.
     Drawn in one draw exactly as the session draws it (gumbel_exponential [S, M*N, 2] replaces the draw, read as the session reads
     it), so N pool streams opened with these decide as the lock-step session from the same generator state decides."""
-    S, N, M = int(num_segments), int(batch_size), model.num_modality
-    dev = next(model.parameters()).device
-    if model.rng_policy:
-        rand = torch.rand((S, M, N), dtype=torch.float32, device=dev)
-        return [dict(rand=rand[:, :, j]) for j in range(N)]
-    if gumbel_exponential is None:
-        expo = torch.empty(S * M * N, 2, dtype=torch.float32, device=dev).exponential_()
-    else:
-        if gumbel_exponential.numel() != S * M * N * 2:
-            raise ValueError("online.batch_noise: gumbel_exponential holds %d values, [S, M*N, 2] = [%d, %d, 2] needs %d"
-                             % (gumbel_exponential.numel(), S, M * N, S * M * N * 2))
-        expo = gumbel_exponential.to(device=dev, dtype=torch.float32).contiguous()
-    if model.policy_net.causality_modeling is not None:
-        expo = expo.reshape(S, M, N, 2)
-    else:
-        expo = expo.reshape(M, S, N, 2).transpose(0, 1)
-    return [dict(gumbel_exponential=expo[:, :, j]) for j in range(N)]
+    noise = _draw_noise("online.batch_noise", model, int(num_segments), int(batch_size), gumbel_exponential)
+    name = "rand" if model.rng_policy else "gumbel_exponential"
+    return [{name: noise[:, :, j]} for j in range(noise.size(2))]
 
 
 def stagger_schedule(n, num_segments, k):
@@ -455,28 +432,6 @@ def gather_videos(parts):
         if id(piece) not in decoded:
             decoded[id(piece)] = augmented(piece)
     return [_gather_one([(decoded[id(piece)][m], int(row)) for piece, row in parts]) for m in range(M)]
-
-
-def _run_selected(net, m_x, decisions, nsel, B):
-    """One main net on the videos of this segment whose decision is 1, gathered as `AdaMML._forward_skipping` gathers them.  m_x: the
-    data layer's tensor of ONE segment for this net; decisions: [B], nsel of them 1.  Returns ([B, classes] fp32 logits, exactly 0
-    for the videos not run, and the number run).  Nothing is launched on the net when no video is selected, and the selected clips
-    are never padded: the pad-to-8 of the whole-video forward (few call shapes for its launch plans) would make a stream of one
-    video run 8 clips per segment, and with B small the distinct shapes are few anyway."""
-    raw32 = m_x.dtype == torch.float32                                        # one-channel fp32 input [B, 1, H, W] (data_layer)
-    frames = m_x if raw32 else m_x.flatten(0, 1)                              # [B*F, H, W, C], clips contiguous
-    if nsel == B:
-        return net.forward_nhwc(frames, 1), nsel
-    ncls = net.fc.out_features if hasattr(net, "fc") else net.classifier[1].out_features
-    out = torch.zeros(B, ncls, dtype=torch.float32, device=m_x.device)
-    if nsel > 0:
-        idx = (decisions > 0.5).nonzero().flatten()
-        if raw32:
-            sel = frames.index_select(0, idx)                                 # [n, 1, H, W]: one group
-        else:
-            sel = frames.view(B, frames.shape[0] // B, *frames.shape[1:]).index_select(0, idx).flatten(0, 1)
-        out.index_copy_(0, idx, net.forward_nhwc(sel, 1))
-    return out, nsel
 
 
 # ---------------------------------------------------------------------------------------------------- split_segments

@@ -222,6 +222,59 @@ def test_session_refuses_a_step_too_many_another_batch_and_another_modality_coun
         assert s.t == 0
 
 
+# ---- the gated-clip runner of forward, Session and Pool: a stand-in net, nothing is launched -------------------------------------------
+
+class LinearNet:
+    """A main net whose `forward_nhwc` is a fixed linear map of each clip and which records the shapes it was called with.  Weights
+    and inputs are small integers: every sum is exact in fp32, whichever clips share a call."""
+
+    def __init__(self, clip_numel, frames_per_clip, classes=5):
+        g = torch.Generator().manual_seed(1)
+        self.fc = nn.Linear(clip_numel, classes)
+        self.fc.weight.data = torch.randint(-3, 4, (classes, clip_numel), generator=g).float()
+        self.fc.bias.data = torch.randint(-3, 4, (classes,), generator=g).float()
+        self.fpc, self.calls = frames_per_clip, []
+
+    def forward_nhwc(self, frames, groups):
+        self.calls.append((tuple(frames.shape), groups))
+        if frames.dtype == torch.float32 and groups > 1:                           # the whole [B, S, H, W]: segment = group
+            frames = frames.transpose(0, 1).reshape(-1, 1, *frames.shape[2:])
+        with torch.no_grad():
+            return self.fc(frames.reshape(frames.shape[0] // self.fpc, -1).float())
+
+
+@pytest.mark.parametrize("form", ["bf16", "raw32"])
+def test_run_selected_runs_exactly_the_selected_clips(form):
+    from adamml_amd.adamml import run_selected
+    S, B, F, H, W, C = 2, 3, 2, 3, 4, 2
+    g = torch.Generator().manual_seed(7)
+    if form == "bf16":
+        m_x = torch.randint(-4, 5, (S, B * F, H, W, C), generator=g).to(torch.bfloat16)      # [S, B*F, H, W, C]
+        net, whole, clip = LinearNet(F * H * W * C, F), ((S * B * F, H, W, C), 1), lambda k: (k * F, H, W, C)
+    else:
+        m_x = torch.randint(-4, 5, (B, S, H, W), generator=g).float()                         # [B, S, H, W]
+        net, whole, clip = LinearNet(H * W, 1), ((B, S, H, W), S), lambda k: (k, 1, H, W)
+    everything = net.forward_nhwc(m_x if form == "raw32" else m_x.flatten(0, 1), whole[1])    # [S*B, classes], row s*B + b
+    assert everything.shape == (S * B, 5) and len({tuple(r.tolist()) for r in everything}) == S * B     # every clip's row is its own
+    # (segment 0, video 1), (segment 1, video 0), (segment 1, video 2): read as b*S + s these rows would name three other clips
+    patterns = {"none": [0, 0, 0, 0, 0, 0], "all": [1, 1, 1, 1, 1, 1], "partial": [0, 1, 0, 1, 0, 1]}
+    for name, rows in patterns.items():
+        selected = torch.tensor(rows, dtype=torch.float32)
+        want = torch.where(selected[:, None] > 0.5, everything, torch.zeros(()))
+        for nsel in (None, sum(rows)):                                             # counted by the runner, or known to the caller
+            for pad_to in (0, 8):
+                net.calls = []
+                out, ran = run_selected(net, m_x, selected, S, B, nsel=nsel, pad_to=pad_to)
+                assert ran == sum(rows) and out.dtype == torch.float32
+                assert torch.equal(out, want), (form, name, nsel, pad_to)         # also: the padded call gives the same result
+                if name == "none":
+                    assert net.calls == []                                         # nothing runs on the net
+                elif name == "all":
+                    assert net.calls == [whole]                                    # the whole input, as it is, padded or not
+                else:
+                    assert net.calls == [(clip(8 if pad_to else sum(rows)), 1)], (form, nsel, pad_to, net.calls)
+
+
 # ---- the launcher's flag ----------------------------------------------------------------------------------------------------------------
 
 def test_online_without_evaluate_exits_with_the_reason():

@@ -170,10 +170,8 @@ def test_a_stream_draws_its_noise_as_a_one_video_session_does(rng_policy, causal
         assert pool._stream(b).slot == 1 and torch.equal(pool._noise[:, 0], pool._noise[:, 1])
         if rng_policy:
             assert torch.equal(pool._noise[:, 1], session._rand[:, :, 0])      # [S, M]
-        elif causality:
-            assert torch.equal(pool._noise[:, 1], session._expo[:, :, 0])      # [S, M, 2], segment-major in both
         else:
-            assert torch.equal(pool._noise[:, 1], session._expo[:, :, 0].transpose(0, 1))         # the session holds [M, S, N, 2]
+            assert torch.equal(pool._noise[:, 1], session._expo[:, :, 0])      # [S, M, 2], segment-major in both, for both heads
 
 
 @pytest.mark.parametrize("rng_policy,causality", [(False, "lstm"), (False, None), (True, "lstm")])
@@ -190,7 +188,7 @@ def test_batch_noise_is_the_sessions_draw_cut_into_columns(rng_policy, causality
         pool = online.Pool(model, S, capacity=N)
         for j in range(N):
             pool.open(**noise[j])
-            want = session._rand[:, :, j] if rng_policy else (session._expo[:, :, j] if causality else session._expo[:, :, j].transpose(0, 1))
+            want = session._rand[:, :, j] if rng_policy else session._expo[:, :, j]
             assert torch.equal(pool._noise[:, j], want), j
         assert torch.equal(torch.get_rng_state(), after)                       # a given noise draws nothing
         if not rng_policy:
@@ -198,7 +196,7 @@ def test_batch_noise_is_the_sessions_draw_cut_into_columns(rng_policy, causality
             cut = online.batch_noise(model, S, N, given)
             ref = online.Session(model, S, N, given)._expo
             for j in range(N):
-                assert torch.equal(cut[j]["gumbel_exponential"], ref[:, :, j] if causality else ref[:, :, j].transpose(0, 1))
+                assert torch.equal(cut[j]["gumbel_exponential"], ref[:, :, j])
             with pytest.raises(ValueError, match=r"holds 40 values.*needs 48"):
                 online.batch_noise(model, S, N, torch.rand(20, 2))
 
