@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import __graft_entry__ as ge
+from adamml_amd import abi
 from tests.golden_cases import CASES, CH
 from tests.oracle_harness import manifest
 
@@ -24,8 +25,7 @@ def built():
 
 
 def test_library_exports_every_declared_symbol(built):
-    hdr = open(os.path.join(ROOT, "include", "adamml_hip.h")).read()
-    declared = set(re.findall(r"\b(adamml_[a-z0-9_]+)\s*\(", hdr))
+    declared = set(abi.FUNCTIONS)
     assert len(declared) >= 28
     lib = ctypes.CDLL(built)
     for sym in sorted(declared):
@@ -59,8 +59,7 @@ def test_every_declared_entry_point_is_named_by_a_test_module():
     or is in ABI_TEST_EXEMPT with its reason (the error string, plan plumbing); the exemption list holds nothing stale.
     Dispatch probes are not exempt: a row asserts them (test_dispatch_probes_answer_as_documented for those no GPU row reads)."""
     import glob
-    hdr = open(os.path.join(ROOT, "include", "adamml_hip.h")).read()
-    declared = set(re.findall(r"\b(adamml_[a-z0-9_]+)\s*\(", hdr))
+    declared = set(abi.FUNCTIONS)
     text = "".join(open(f).read() for f in glob.glob(os.path.join(ROOT, "tests", "test_*.py")))
     text = re.sub(r"ABI_TEST_EXEMPT = \{.*?\n\}\n", "", text, flags=re.S)         # (the exemption list itself names nothing)
     # named = called: the name as a string literal (hip.call("name", ..)) or as an attribute of the loaded library (lib.name(..)); a mention
@@ -135,8 +134,7 @@ WORKSPACE_QUERY_EXEMPT = {
 def test_every_workspace_query_is_called_by_a_guarded_conformance_module():
     """A workspace-size query nobody checks against what the kernel touches is a gap: every adamml_*_workspace of the header is called by
     name in one of the GUARDED_MODULES (whose rows allocate exactly the answer inside guard bands), or is in WORKSPACE_QUERY_EXEMPT"""
-    hdr = open(os.path.join(ROOT, "include", "adamml_hip.h")).read()
-    queries = set(re.findall(r"\b(adamml_[a-z0-9_]+_workspace)\s*\(", hdr))
+    queries = {n for n in abi.FUNCTIONS if n.endswith("_workspace")}
     assert len(queries) >= 9
     text = "".join(open(os.path.join(ROOT, "tests", m)).read() for m in GUARDED_MODULES)
     called = {q for q in queries if re.search(r"\.%s\(" % q, text)}
@@ -152,8 +150,7 @@ def test_every_computing_entry_point_is_named_by_a_float64_conformance_module():
     """Being called by some test is not being checked: every function of include/adamml_hip.h that computes something -- everything but
     the size queries and dispatch probes (CONFORMANCE_QUERY_SUFFIXES) -- is called in one of the CONFORMANCE_MODULES, or is in
     CONFORMANCE_EXEMPT with its reason; the exemption list holds nothing stale (undeclared, a query, or named by a conformance module)."""
-    hdr = open(os.path.join(ROOT, "include", "adamml_hip.h")).read()
-    declared = set(re.findall(r"\b(adamml_[a-z0-9_]+)\s*\(", hdr))
+    declared = set(abi.FUNCTIONS)
     text = ""
     for m in CONFORMANCE_MODULES:
         path = os.path.join(ROOT, "tests", m)
@@ -737,8 +734,7 @@ def test_launch_plan_thunks_are_in_sync_with_the_c_abi(built):
     lib = ctypes.CDLL(built)
     assert lib.adamml_plan_num_entry_points() == len(names)
     assert ctypes.sizeof(plan.PlanOp) == 4 * 4 + 2 * 4 + 8 * plan.MAX_ARGS
-    hdr = open(os.path.join(ROOT, "include", "adamml_hip.h")).read()
-    assert ("#define ADAMML_PLAN_MAX_ARGS %d" % plan.MAX_ARGS) in hdr
+    assert abi.DEFINES["ADAMML_PLAN_MAX_ARGS"] == plan.MAX_ARGS
 
 
 def test_launch_plan_recorder_encodes_calls_slots_waits_and_segments():

@@ -5,12 +5,11 @@ damaged streams terminate in the CPU model with a status; EncodedFrames checks i
 import hashlib
 import io
 import os
-import re
 
 import numpy as np
 import pytest
 
-from adamml_amd import hip, jpeg as J, video as V
+from adamml_amd import abi, hip, jpeg as J, video as V
 from tests import jpeg_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -268,10 +267,11 @@ def test_encoded_frames_checks_its_files():
 # ---- C ABI ------------------------------------------------------------------------------------------------------------------------------
 
 def test_header_declares_and_library_exports_jpeg_decode():
-    hdr = open(os.path.join(ROOT, "include", "adamml_hip.h")).read()
-    assert re.search(r"ADAMML_API int adamml_jpeg_decode_u8\(const uint8_t\* src, int64_t src_bytes, const int32_t\* meta, int meta_len, "
-                     r"uint8_t\* y, int64_t y_bytes,\s+int32_t\* status, void\* workspace, int64_t workspace_bytes, int N, hipStream_t stream\);", hdr)
-    assert re.search(r"ADAMML_API size_t adamml_jpeg_decode_workspace\(int64_t total_blocks\);", hdr)
+    declared = abi.FUNCTIONS
+    assert str(declared["adamml_jpeg_decode_u8"]) == (
+        "int adamml_jpeg_decode_u8(const uint8_t* src, int64_t src_bytes, const int32_t* meta, int meta_len, "
+        "uint8_t* y, int64_t y_bytes, int32_t* status, void* workspace, int64_t workspace_bytes, int N, hipStream_t stream)")
+    assert str(declared["adamml_jpeg_decode_workspace"]) == "size_t adamml_jpeg_decode_workspace(int64_t total_blocks)"
     lib = hip.load()
     assert hasattr(lib, "adamml_jpeg_decode_u8") and hasattr(lib, "adamml_jpeg_decode_workspace")
     assert lib.adamml_jpeg_decode_workspace(10) == 1920 and lib.adamml_jpeg_decode_workspace(0) == 0

@@ -5,12 +5,11 @@ properties they were searched for and Pillow's pixels; damaged streams make the 
 `Batch.parallel` answer as documented."""
 import hashlib
 import os
-import re
 
 import numpy as np
 import pytest
 
-from adamml_amd import hip, jpeg as J
+from adamml_amd import abi, hip, jpeg as J
 from tests import jpeg_ref as R, jpeg_sync_ref as M
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -110,10 +109,9 @@ def test_probe_and_batch_parallel_answer_as_documented():
     lib = hip.load()
     probe = lib.adamml_jpeg_decode_parallel_supported
     S = J.SUBSEQ_BYTES
-    hdr = open(os.path.join(ROOT, "include", "adamml_hip.h")).read()
-    assert int(re.search(r"#define ADAMML_JPEG_SUBSEQ_BYTES (\d+)", hdr).group(1)) == S == 128
-    assert re.search(r"ADAMML_API int adamml_jpeg_decode_parallel_supported\(int H, int W, int components, int sampling, int segments, "
-                     r"int64_t coded_bytes\);", hdr)
+    assert abi.DEFINES["ADAMML_JPEG_SUBSEQ_BYTES"] == S == 128
+    assert str(abi.FUNCTIONS["adamml_jpeg_decode_parallel_supported"]) == (
+        "int adamml_jpeg_decode_parallel_supported(int H, int W, int components, int sampling, int segments, int64_t coded_bytes)")
     assert probe(256, 341, 3, 2, 1, 44000) == 1 and probe(256, 341, 3, 2, 16, 44000) == 0          # restart markers: today's path
     assert probe(1, 1, 3, 2, 1, 10) == 1 and probe(41, 30, 1, 1, 1, 1154) == 1 and probe(30, 41, 3, 1, 1, 5000) == 1
     assert probe(256, 341, 3, 2, 1, 2048 * S) == 1 and probe(256, 341, 3, 2, 1, 2048 * S + 1) == 0   # the record cap

@@ -6,14 +6,13 @@ import ctypes
 import json
 import os
 import random
-import re
 import types
 
 import numpy as np
 import pytest
 
 import __graft_entry__ as ge
-from adamml_amd import video as V
+from adamml_amd import abi, video as V
 from tests import video_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -223,9 +222,9 @@ def test_augmentor_for_reads_the_launcher_flags():
 
 
 def test_header_declares_and_library_exports_video_resample():
-    hdr = open(os.path.join(ROOT, "include", "adamml_hip.h")).read()
-    assert re.search(r"ADAMML_API int adamml_video_resample_u8\(const uint8_t\* src, int64_t src_bytes, const int32_t\* meta, int meta_len, "
-                     r"uint8_t\* y, int N, int OH,\s+int OW, int K_in, int K_out, int diffs, hipStream_t stream\);", hdr)
+    assert str(abi.FUNCTIONS["adamml_video_resample_u8"]) == (
+        "int adamml_video_resample_u8(const uint8_t* src, int64_t src_bytes, const int32_t* meta, int meta_len, "
+        "uint8_t* y, int N, int OH, int OW, int K_in, int K_out, int diffs, hipStream_t stream)")
     ge.build()
     lib = ctypes.CDLL(ge.LIB)
     assert hasattr(lib, "adamml_video_resample_u8")
