@@ -86,6 +86,43 @@ __device__ __forceinline__ void static_for(F&& f) {
     }
 }
 
+// ---- MFMA idioms that the tile kernels AND the wave-slice streaming kernels use (one definition for both families; tile.h cannot hold
+// them: it brings a device global, and conv3x3_c64.hip, conv_stem.hip and the wave-slice files do not include it).  A helper is used at a
+// site only where the kernel's device code stays byte-identical with it (tools/device_code_digest.py): profiles/tile_idioms.md.
+
+// MFMA fragment of pixel-major LDS data, pixels = the reduction dimension: two hardware transpose reads (ds_read_b64_tr_b16)
+__device__ __forceinline__ bf16x8 tr_pair(const char* p0, const char* p1) {
+    union { s16x4 h[2]; bf16x8 v; } f;
+    f.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p0));
+    f.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p1));
+    return f.v;
+}
+// ... of rows row_bytes apart: the second read is four rows below the first (its address is formed after the first read, as the sites
+// had it).  waveslice.h's tr_frag(base, row_bytes, blk, trow, li) is this at the lane's address of a 16-channel block.
+__device__ __forceinline__ bf16x8 tr_rows(const char* p, int row_bytes) {
+    union { s16x4 h[2]; bf16x8 v; } f;
+    f.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
+    f.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p + 4 * row_bytes));
+    return f.v;
+}
+
+// Per-channel statistics on the matrix cores: with F = a [32 pixels][16 channels] fragment, ones * F holds the per-channel sums in row 0
+// of D (lanes with lg == 0: dsum[0] is channel li) and F^T F the sums of squares on its diagonal -- exact products of the stored
+// values, fp32 accumulation.
+__device__ __forceinline__ bf16x8 bf16x8_ones() {
+    union { s16x4 h[2]; bf16x8 v; } ones;
+    ones.h[0] = s16x4{0x3F80, 0x3F80, 0x3F80, 0x3F80};
+    ones.h[1] = ones.h[0];
+    return ones.v;
+}
+// (the accumulate pair dsum = mfma(ones, f, dsum), dsq = mfma(f, f, dsq) stays as text at its sites: behind a function only
+// conv1x1_narrow_fwd_kernel kept its device code)
+// D rows = lg * 4 + r, column = li: the lane with (li >> 2) == lg owns diagonal element li, in register li & 3
+__device__ __forceinline__ float mfma_diag(f32x4 d, int li) {
+    const int r = li & 3;
+    return r == 0 ? d[0] : r == 1 ? d[1] : r == 2 ? d[2] : d[3];
+}
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE attribute of a kernel: raise it once per (kernel, device), thread-safely.
 // `done` = the call site's own bit set (one bit per device).  A process-wide `static bool` (rounds 4-5) left the limit at 64 KB on every
 // device but the first one a process drives, and was a data race between threads (round-5 advisor finding).

@@ -95,9 +95,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_narrow_fwd_kernel(N1P p) {
         const long t = wid + (long)u * nw;
         issue(u, t < ntile ? t : ntile - 1);
     }
-    union { s16x4 h[2]; bf16x8 v; } ones;
-    ones.h[0] = s16x4{0x3F80, 0x3F80, 0x3F80, 0x3F80};
-    ones.h[1] = ones.h[0];
+    const bf16x8 ones = bf16x8_ones();
     const int trow = 8 * lg + (li >> 2);
 
     for (long tb = wid; tb < ntile; tb += (long)TD * nw) {
@@ -156,13 +154,10 @@ __global__ __launch_bounds__(256, 2) void conv1x1_narrow_fwd_kernel(N1P p) {
                     f.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(fp));
                     f.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(fp + 4 * SROW));
                     const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-                    const f32x4 dsum = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones.v, f.v, z4, 0, 0, 0);
+                    const f32x4 dsum = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, f.v, z4, 0, 0, 0);
                     const f32x4 dsq = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.v, f.v, z4, 0, 0, 0);
                     if (lg == 0) csw[cb * 16 + li] += dsum[0];                        // (own row, one owner lane per entry, tile order)
-                    if ((li >> 2) == lg) {
-                        const int r = li & 3;
-                        csw[CW + cb * 16 + li] += r == 0 ? dsq[0] : r == 1 ? dsq[1] : r == 2 ? dsq[2] : dsq[3];
-                    }
+                    if ((li >> 2) == lg) csw[CW + cb * 16 + li] += mfma_diag(dsq, li);
                 }
             }
             // ---- the tile leaves as ONE contiguous run of npx * COUT * 2 bytes, 16 bytes per lane

@@ -97,9 +97,7 @@ __global__ __launch_bounds__(512, 1) void wide_all_kernel(WXP p) {
         const int oh = rem / p.OW, ow = rem - oh * p.OW;
         return ((size_t)(n * p.H + 2 * oh) * p.W + 2 * ow) * p.K;
     };
-    union { s16x4 h[2]; bf16x8 v; } ones;
-    ones.h[0] = s16x4{0x3F80, 0x3F80, 0x3F80, 0x3F80};
-    ones.h[1] = ones.h[0];
+    const bf16x8 ones = bf16x8_ones();
     const int trow = 8 * lg + (li >> 2);
     // weight slab loads of this thread: chunk e = tid + 512 j of the slab's SLAB x KP x 2 contiguous bytes
     bf16x8 wreg[WLD];
@@ -242,7 +240,7 @@ __global__ __launch_bounds__(512, 1) void wide_all_kernel(WXP p) {
             const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int cb = 0; cb < NCT; ++cb) {
-                dsum[cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones.v, fr[cb], z4, 0, 0, 0);
+                dsum[cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, fr[cb], z4, 0, 0, 0);
                 dsq[cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fr[cb], fr[cb], z4, 0, 0, 0);
             }
             // D rows = lg * 4 + r, column = li: row 0 of dsum (lanes lg == 0) holds the column sums, the diagonal of dsq sits in the lanes

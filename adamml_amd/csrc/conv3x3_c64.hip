@@ -425,27 +425,18 @@ __global__ __launch_bounds__(NT3, 1) void conv3x3_c64_kernel(C3P p) {
             }
             if (p.stats) {
                 // waves w and w+4 share channel block w & 3 and split the 32-pixel steps; ones*F and diag(F^T F)
-                union { s16x4 h[2]; bf16x8 v; } ones;
-                ones.h[0] = s16x4{0x3F80, 0x3F80, 0x3F80, 0x3F80};
-                ones.h[1] = ones.h[0];
+                const bf16x8 ones = bf16x8_ones();
                 const int cb = wave & 3;
                 const int trow = 8 * lg + (li >> 2);
                 f32x4 dsum = {0.f, 0.f, 0.f, 0.f}, dsq = {0.f, 0.f, 0.f, 0.f};
                 const int nps = (npx + 31) >> 5;
                 for (int ps = wave >> 2; ps < nps; ps += 2) {
-                    const char* fp = s_patch + (ps * 32 + trow) * SROW3 + (cb * 16 + 4 * (li & 3)) * 2;
-                    union { s16x4 h[2]; bf16x8 v; } f;
-                    f.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(fp));
-                    f.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(fp + 4 * SROW3));
-                    dsum = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones.v, f.v, dsum, 0, 0, 0);
-                    dsq = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.v, f.v, dsq, 0, 0, 0);
+                    const bf16x8 f = tr_rows(s_patch + (ps * 32 + trow) * SROW3 + (cb * 16 + 4 * (li & 3)) * 2, SROW3);
+                    dsum = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, f, dsum, 0, 0, 0);
+                    dsq = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f, f, dsq, 0, 0, 0);
                 }
                 if (lg == 0) atomicAdd(&csw[cb * 16 + li], dsum[0]);             // (own row: the only lane that ever adds to this entry)
-                if ((li >> 2) == lg) {
-                    const int r = li & 3;
-                    const float q2 = r == 0 ? dsq[0] : r == 1 ? dsq[1] : r == 2 ? dsq[2] : dsq[3];
-                    atomicAdd(&csw[64 + cb * 16 + li], q2);
-                }
+                if ((li >> 2) == lg) atomicAdd(&csw[64 + cb * 16 + li], mfma_diag(dsq, li));
             }
         } else {
             // data gradient w.r.t. a lazily normalised tensor: g' = g * act'(scale*z+shift); sums of g' and g'*zhat
@@ -678,16 +669,11 @@ __global__ __launch_bounds__(NT3, 1) void conv3x3_c64_wgrad_kernel(C3WP p) {
             const char* zb0 = s_dz + q0 * SROW3 + 4 * (li & 3) * 2;
             bf16x8 fa[4];
 #pragma unroll
-            for (int mt = 0; mt < 4; ++mt) {
-                union { s16x4 h[2]; bf16x8 v; } f;
-                f.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(zb0 + mt * 32));
-                f.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(zb0 + mt * 32 + 4 * SROW3));
-                fa[mt] = f.v;
-            }
+            for (int mt = 0; mt < 4; ++mt) fa[mt] = tr_rows(zb0 + mt * 32, SROW3);
 #pragma unroll
             for (int j = 0; j < 5; ++j) {
                 if (wave + 8 * j < 36) {                         // wave-uniform (only j == 4 can fail)
-                    union { s16x4 h[2]; bf16x8 v; } f;
+                    union { s16x4 h[2]; bf16x8 v; } f;              // (tr_pair in its own text: with the helper this kernel gets other instructions)
                     f.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(pb0 + noff[j]));
                     f.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(pb1 + noff[j]));
 #pragma unroll

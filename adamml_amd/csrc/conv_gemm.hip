@@ -135,13 +135,14 @@ __device__ __forceinline__ int lds_off(int row, int chunk) {
 // PF: see ConvP::pf_a (BC = 128, 64 channels of a; RES + GLDS + EID only).
 // Workgroups per CU the register allocation is sized for.  The fused instances (RES / DUAL / CAT / EID) take 256 registers; the plain
 // ones rely on occupancy (PD 1: 3-4 workgroups per CU) or on their register ring (PD 3).  The instances under "fewer" did not fit
-// that budget (2-13 registers in scratch, tools/kernel_resources.py) and get one workgroup less: the data-gradient epilogues that are
-// staged through registers at 64-wide tiles, the strided (MODE 2) loaders and the FADD epilogue without EID.
+// that budget (2-13 registers in scratch, tools/kernel_resources.py) and get one workgroup less: the data-gradient epilogues behind the
+// KxK loaders at 64-wide tiles (EPI 1 -- compiled behind LDS-DMA only, as is MODE 3: a gradient operand is never lazy -- and EPI 2), the
+// register-staged accumulating KxK epilogue at 128, the strided (MODE 2) loaders and the FADD epilogue without EID.
 constexpr int conv_gemm_wg_per_cu(int BC, int MODE, int PD, bool RES, bool DUAL, bool CAT, bool FADD, bool GLDS, int EID, int EPI) {
     if (RES || DUAL || CAT || EID) return 2;
     const int n = PD == 1 ? (BC == 128 ? 3 : 4) : (BC == 128 ? 2 : 3);
     const bool fewer = (MODE == 2 && !(BC == 128 && PD == 3)) || FADD ||
-                       (BC == 64 && PD == 1 && ((EPI == 1 && !(MODE == 0 && GLDS)) || (EPI == 2 && MODE == 1))) ||
+                       (BC == 64 && PD == 1 && ((EPI == 1 && MODE != 0) || (EPI == 2 && MODE == 1))) ||
                        (BC == 128 && MODE == 1 && EPI == 2 && !GLDS);
     return fewer ? n - 1 : n;
 }
@@ -237,6 +238,8 @@ __global__ __launch_bounds__(NTHREADS, conv_gemm_wg_per_cu(BC, MODE, PD, RES, DU
 
     // XCD-aware tile order: blocks b, b+8, b+16.. share an XCD (and its L2); give them consecutive
     // tiles so the cout tiles of one pixel tile hit the same L2 (cdna_hip_programming.md T1, bijective form)
+    // (common.h's xcd_contiguous in signed arithmetic, kept as text: through the unsigned helper every instance keeps its resources and
+    // gets other instructions -- bid feeds the two signed divisions below)
     const int nwg = gridDim.x;
     int bid = blockIdx.x;
     {
@@ -956,9 +959,7 @@ __global__ __launch_bounds__(NTHREADS, conv_gemm_wg_per_cu(BC, MODE, PD, RES, DU
         // fp32 accumulation.  The VALU form (convert + add + fma per element) cost 30 % on the HBM-bound 1x1 layers.
         // Rows past P and channels past Cout hold zeros (their operands were zero-filled).
         constexpr int NCB = BC / 64;                       // 16-channel blocks per wave
-        union { s16x4 h[2]; bf16x8 v; } ones;
-        ones.h[0] = s16x4{0x3F80, 0x3F80, 0x3F80, 0x3F80};
-        ones.h[1] = ones.h[0];
+        const bf16x8 ones = bf16x8_ones();
         const int trow = 8 * lg + (li >> 2);
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb) {
@@ -966,19 +967,13 @@ __global__ __launch_bounds__(NTHREADS, conv_gemm_wg_per_cu(BC, MODE, PD, RES, DU
             f32x4 dsum = {0.f, 0.f, 0.f, 0.f}, dsq = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int ps = 0; ps < BP / 32; ++ps) {
-                const char* fp = smem + (ps * 32 + trow) * CROW + (ch0 + 4 * (li & 3)) * 2;
-                union { s16x4 h[2]; bf16x8 v; } f;
-                f.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(fp));
-                f.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(fp + 4 * CROW));
-                dsum = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones.v, f.v, dsum, 0, 0, 0);
-                dsq = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.v, f.v, dsq, 0, 0, 0);
+                const bf16x8 f = tr_rows(smem + (ps * 32 + trow) * CROW + (ch0 + 4 * (li & 3)) * 2, CROW);
+                dsum = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, f, dsum, 0, 0, 0);
+                dsq = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f, f, dsq, 0, 0, 0);
             }
-            // D rows = lg*4 + r, column = li: row 0 of dsum is held by lanes 0..15; the diagonal of dsq by lanes with li>>2 == lg
+            // row 0 of dsum is held by lanes 0..15; the diagonal of dsq by lanes with li>>2 == lg
             if (lg == 0) cs[ch0 + li] += dsum[0];
-            if ((li >> 2) == lg) {
-                const int r = li & 3;
-                cs[BC + ch0 + li] += r == 0 ? dsq[0] : r == 1 ? dsq[1] : r == 2 ? dsq[2] : dsq[3];
-            }
+            if ((li >> 2) == lg) cs[BC + ch0 + li] += mfma_diag(dsq, li);
         }
     }
     if (p.stats && (epi_bnz || RES)) {
@@ -988,6 +983,8 @@ __global__ __launch_bounds__(NTHREADS, conv_gemm_wg_per_cu(BC, MODE, PD, RES, DU
         // per step) -- 24 VALU ops instead of 32-48 ds_bpermute, which had made this epilogue LDS-pipe-bound (-30 % on
         // the HBM-bound 1x1 layers).  16 values -> 4 registers per lane, then 4 LDS adds per lane, into this WAVE's row of the sums (one
         // owner lane per entry: the adds of an entry happen in tile order, whatever the timing of the other waves).
+        // (the same sequence as conv3x3_c64.hip's fold16_to_cs, kept as text: behind one function the instances that hold it keep their
+        // resources and get other instructions -- profiles/tile_idioms.md)
         auto fold = [&](const f32x8& s1, const f32x8& s2, float* dst) {
             dst += (NSR > 1 ? wave : 0) * 2 * BC;
             float v[16];
@@ -1039,21 +1036,12 @@ __global__ __launch_bounds__(NTHREADS, conv_gemm_wg_per_cu(BC, MODE, PD, RES, DU
         for (int ks = 0; ks < BP / 32; ++ks) {
             bf16x8 fa[4], fb[2];
 #pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const char* fp = smem + (ks * 32 + trow) * CROW + (wp * 64 + t * 16 + 4 * tq) * 2;
-                union { s16x4 h[2]; bf16x8 v; } f;
-                f.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(fp));
-                f.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(fp + 4 * CROW));
-                fa[t] = f.v;
-            }
+            for (int t = 0; t < 4; ++t) fa[t] = tr_rows(smem + (ks * 32 + trow) * CROW + (wp * 64 + t * 16 + 4 * tq) * 2, CROW);
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 const char* base = smem + PF_OFF + ks * 32 * 128;
                 const int u = (wc * 32 + t * 16) / 4 + tq;
-                union { s16x4 h[2]; bf16x8 v; } f;
-                f.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + trow * 128 + ((u ^ x_lo) << 3)));
-                f.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + (trow + 4) * 128 + ((u ^ x_hi) << 3)));
-                f32x8 q = bf8_to_f32(f.v);
+                f32x8 q = bf8_to_f32(tr_swz_frag(base, trow * 128, x_lo, (trow + 4) * 128, x_hi, u));
 #pragma unroll
                 for (int i = 0; i < 8; ++i) q[i] = clamp_act(fmaf(q[i], pfs[t], pfh[t]), plo, phi);
                 fb[t] = f32_to_bf8(q);
@@ -1167,15 +1155,20 @@ template <class F> static void with_tp(int tp, F f) { if (tp == 8) f(int_c<8>{})
 template <class F> static void with_flag(bool b, F f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
 
 // the plain instances of one (BC, MODE): LDS-DMA staging or the register-staged loader with the epilogue compiled in, deep prefetch (MODE
-// 0 / 1) or the strided loader (MODE 2) with the run-time epilogue
+// 0) or the strided loader (MODE 2) with the run-time epilogue.  `lazy` = the input has a lazy transform (register-staged loader); the
+// caller has refused a lazy GRADIENT operand (cls or bn_z), so MODE 3 and the bn_z epilogue (EPI 1) exist behind LDS-DMA only, and `deep`
+// is never set for MODE 1
 template <int BC, int MODE>
-static void launch_conv(bool glds, bool deep, int epi, const ConvGrid& g, const ConvP& p) {
+static void launch_conv(bool lazy, bool deep, int epi, const ConvGrid& g, const ConvP& p) {
     if constexpr (MODE == 2) {
         if (deep) launch_rt_epi<BC, 2, 3>(g, p); else launch_rt_epi<BC, 2, 1>(g, p);
+    } else if constexpr (MODE == 3) {
+        with_epi(epi, [&](auto e) { launch_plain<BC, 3, true, e()>(g, p); });
     } else {
-        if constexpr (MODE != 3)
-            if (!glds && deep) return launch_rt_epi<BC, MODE, 3>(g, p);
-        with_flag(glds, [&](auto gl) { with_epi(epi, [&](auto e) { launch_plain<BC, MODE, gl(), e()>(g, p); }); });
+        if (!lazy) return with_epi(epi, [&](auto e) { launch_plain<BC, MODE, true, e()>(g, p); });
+        if constexpr (MODE == 0)
+            if (deep) return launch_rt_epi<BC, 0, 3>(g, p);
+        if (epi == 0) launch_plain<BC, MODE, false, 0>(g, p); else launch_plain<BC, MODE, false, 2>(g, p);
     }
 }
 
@@ -1346,14 +1339,19 @@ static int conv_launch(const adamml_conv_desc_t* d, const void* x, const void* w
     // (the fragment-side lazy transform, LZF, is NOT used for the plain forward convs: measured 5-10 % slower than the register-staged
     // loader -- layer-1 conv3 1.77 vs 1.61 ms, layer 2 0.59 vs 0.54, layer 3 0.23 vs 0.21: each pixel half is transformed by two waves,
     // between the ds_read and the MFMA; it only pays together with the early identity loads of the FADD kernel)
-    const bool glds = !in_scale && mode != 2;
+    // operands without a lazy transform are staged by LDS-DMA (MODE 0 / 1 / 3)
+    const bool lazy = in_scale != nullptr;
     // the epilogue is a template parameter (EPI) of the LDS-DMA and one-step instances; deep-prefetch and MODE 2 keep the run-time form
     const int epi = bn_z ? 1 : (p.accumulate ? 2 : 0);
+    // a gradient operand (a parity class, or the input of the BatchNorm-fused epilogue) is plain in memory -- every caller passes it so -- and
+    // the register-staged loaders are not compiled for MODE 3 or with EPI 1
+    if (lazy && (mode == 3 || (mode != 2 && epi == 1)))
+        return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_data: the gradient operand is never lazy");
     with_bc(BC, [&](auto bc) {
-        if (mode == 0) launch_conv<bc(), 0>(glds, deep, epi, cg, p);
-        else if (mode == 1) launch_conv<bc(), 1>(glds, deep, epi, cg, p);
-        else if (mode == 2) launch_conv<bc(), 2>(glds, deep, epi, cg, p);
-        else launch_conv<bc(), 3>(glds, deep, epi, cg, p);
+        if (mode == 0) launch_conv<bc(), 0>(lazy, deep, epi, cg, p);
+        else if (mode == 1) launch_conv<bc(), 1>(lazy, deep, epi, cg, p);
+        else if (mode == 2) launch_conv<bc(), 2>(lazy, deep, epi, cg, p);
+        else launch_conv<bc(), 3>(lazy, deep, epi, cg, p);
     });
     return adamml_check_launch("conv_fwd");
 }

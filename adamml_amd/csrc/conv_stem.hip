@@ -178,25 +178,17 @@ __global__ __launch_bounds__(NT, 2) void conv_stem_kernel(StemP p) {
         }
         if (p.stats) {
             // wave w: channels 16w..16w+15; F = [32 pixels][16 channels] by transpose reads; ones*F and diag(F^T F)
-            union { s16x4 h[2]; bf16x8 v; } ones;
-            ones.h[0] = s16x4{0x3F80, 0x3F80, 0x3F80, 0x3F80};
-            ones.h[1] = ones.h[0];
+            const bf16x8 ones = bf16x8_ones();
             const int trow = 8 * lg + (li >> 2);
             f32x4 dsum = {0.f, 0.f, 0.f, 0.f}, dsq = {0.f, 0.f, 0.f, 0.f};
             const int nps = (npx + 31) >> 5;
             for (int ps = 0; ps < nps; ++ps) {
-                const char* fp = s_patch + (ps * 32 + trow) * SROW + (wave * 16 + 4 * (li & 3)) * 2;
-                union { s16x4 h[2]; bf16x8 v; } f;
-                f.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(fp));
-                f.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(fp + 4 * SROW));
-                dsum = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones.v, f.v, dsum, 0, 0, 0);
-                dsq = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.v, f.v, dsq, 0, 0, 0);
+                const bf16x8 f = tr_rows(s_patch + (ps * 32 + trow) * SROW + (wave * 16 + 4 * (li & 3)) * 2, SROW);
+                dsum = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, f, dsum, 0, 0, 0);
+                dsq = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f, f, dsq, 0, 0, 0);
             }
             if (lg == 0) cs[wave * 16 + li] += dsum[0];
-            if ((li >> 2) == lg) {
-                const int r = li & 3;
-                cs[64 + wave * 16 + li] += r == 0 ? dsq[0] : r == 1 ? dsq[1] : r == 2 ? dsq[2] : dsq[3];
-            }
+            if ((li >> 2) == lg) cs[64 + wave * 16 + li] += mfma_diag(dsq, li);
         }
         __syncthreads();                                     // staging consumed before the next patch lands
     }
@@ -328,23 +320,16 @@ __global__ __launch_bounds__(NT, 2) void conv_stem_wgrad_kernel(StemWP p) {
             const char* zb0 = s_dz + (ks * 32 + trow) * DZROW + 4 * (li & 3) * 2;
             bf16x8 fa[4];
 #pragma unroll
-            for (int mt = 0; mt < 4; ++mt) {
-                union { s16x4 h[2]; bf16x8 v; } f;
-                f.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(zb0 + mt * 32));
-                f.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(zb0 + mt * 32 + 4 * DZROW));
-                fa[mt] = f.v;
-            }
+            for (int mt = 0; mt < 4; ++mt) fa[mt] = tr_rows(zb0 + mt * 32, DZROW);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int nt = wave + 4 * j;
                 if (nt < 14) {                                   // wave-uniform
                     const int toff = ((nt >> 1) * p.PW + 4 * (nt & 1)) * 8;
-                    union { s16x4 h[2]; bf16x8 v; } f;
-                    f.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(pb0 + toff));
-                    f.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(pb1 + toff));
+                    const bf16x8 f = tr_pair(pb0 + toff, pb1 + toff);
 #pragma unroll
                     for (int mt = 0; mt < 4; ++mt)
-                        acc[mt][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[mt], f.v, acc[mt][j], 0, 0, 0);
+                        acc[mt][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[mt], f, acc[mt][j], 0, 0, 0);
                 }
             }
         }

@@ -152,7 +152,7 @@ __global__ __launch_bounds__(NTHREADS) void conv_wgrad_kernel(WgradP p) {
     const int trow = 8 * lg + (li >> 2), tq = li & 3;
     const int a_lo = trow * AROW, a_hi = (trow + 4) * AROW, b_lo = trow * BROW, b_hi = (trow + 4) * BROW;
     const int ax_lo = tr_swz<BM>(trow), ax_hi = tr_swz<BM>(trow + 4), bx_lo = tr_swz<BN>(trow), bx_hi = tr_swz<BN>(trow + 4);
-    auto compute = [&](int buf) {
+    auto compute = [&](int buf) {                        // (tr_swz_frag in its own text: with the helper the <64, 64, 1, true> instance gets other instructions)
         const char* base = smem + buf * TILE_BYTES;
         bf16x8 fa[MT], fb[NT];
 #pragma unroll
@@ -326,22 +326,10 @@ __global__ __launch_bounds__(NTHREADS) void conv_wgrad_glds_kernel(WgradP p) {
         const char* base = smem + st * TILE_BYTES;
         bf16x8 fa[MT], fb[NT];
 #pragma unroll
-        for (int t = 0; t < MT; ++t) {
-            const int u = (wm * (BM / 2) + t * 16) / 4 + tq;
-            s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + a_lo + ((u ^ ax_lo) << 3)));
-            s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + a_hi + ((u ^ ax_hi) << 3)));
-            union { struct { s16x4 a, b; } s; bf16x8 v; } cvt;
-            cvt.s.a = lo; cvt.s.b = hi;
-            fa[t] = cvt.v;
-        }
+        for (int t = 0; t < MT; ++t) fa[t] = tr_swz_frag(base, a_lo, ax_lo, a_hi, ax_hi, (wm * (BM / 2) + t * 16) / 4 + tq);
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
-            const int u = (wn * (BN / 2) + t * 16) / 4 + tq;
-            s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + 32 * AROW + b_lo + ((u ^ bx_lo) << 3)));
-            s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + 32 * AROW + b_hi + ((u ^ bx_hi) << 3)));
-            union { struct { s16x4 a, b; } s; bf16x8 v; } cvt;
-            cvt.s.a = lo; cvt.s.b = hi;
-            fb[t] = cvt.v;
+            fb[t] = tr_swz_frag(base + 32 * AROW, b_lo, bx_lo, b_hi, bx_hi, (wn * (BN / 2) + t * 16) / 4 + tq);
             if constexpr (LZB) {
                 f32x8 f = bf8_to_f32(fb[t]);
 #pragma unroll
@@ -523,14 +511,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv3x3_wgrad_kernel(W3P p) {
         const char* pb = base + 32 * 128;
         bf16x8 fa[4];
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int un = t * 4 + tq;
-            s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + a_lo + ((un ^ ax_lo) << 3)));
-            s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + a_hi + ((un ^ ax_hi) << 3)));
-            union { struct { s16x4 a, b; } s; bf16x8 v; } cvt;
-            cvt.s.a = lo; cvt.s.b = hi;
-            fa[t] = cvt.v;
-        }
+        for (int t = 0; t < 4; ++t) fa[t] = tr_swz_frag(base, a_lo, ax_lo, a_hi, ax_hi, t * 4 + tq);
 #pragma unroll
         for (int kh = 0; kh < 3; ++kh)
 #pragma unroll

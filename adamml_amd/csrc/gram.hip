@@ -97,9 +97,7 @@ __global__ __launch_bounds__(NTHREADS) void gram_colsum_kernel(GramP p) {
 #pragma unroll
         for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    union { s16x4 h[2]; bf16x8 v; } ones;
-    ones.h[0] = s16x4{0x3F80, 0x3F80, 0x3F80, 0x3F80};
-    ones.h[1] = ones.h[0];
+    const bf16x8 ones = bf16x8_ones();
 
     const int li = lane & 15, lg = lane >> 4;
     // transpose-read addressing (conv_wgrad_kernel): lane li of a 16-lane group supplies the 8-byte unit
@@ -109,7 +107,7 @@ __global__ __launch_bounds__(NTHREADS) void gram_colsum_kernel(GramP p) {
     const int x_lo = tr_swz<C>(trow), x_hi = tr_swz<C>(trow + 4);
     auto compute = [&](int buf) {
         const char* base = smem + buf * TILE_BYTES;
-        auto frag = [&](int blk) {
+        auto frag = [&](int blk) {                           // (tile.h's tr_swz_frag in its own text: with the helper the <256, 2> instance gets other instructions)
             const int u = blk * 4 + tq;
             union { s16x4 h[2]; bf16x8 v; } cvt;
             cvt.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + a_lo + ((u ^ x_lo) << 3)));
@@ -131,7 +129,7 @@ __global__ __launch_bounds__(NTHREADS) void gram_colsum_kernel(GramP p) {
                 if constexpr (SYM) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fr, frag((rb + j) & (NB - 1)), acc[i][j], 0, 0, 0);
                 else acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fr, f[j], acc[i][j], 0, 0, 0);
             }
-            asum[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones.v, fr, asum[i], 0, 0, 0);
+            asum[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, fr, asum[i], 0, 0, 0);
         }
     };
 

@@ -16,6 +16,12 @@ __device__ __forceinline__ int tr_swz(int row) {
     return (((row >> 1) & 1) | (((row >> 3) & 1) << 1)) << 2;               // 128-byte rows: parity picks the bank half
 }
 
+// MFMA fragment of the 8-byte unit column u of such an image (common.h: tr_pair).  lo / hi = byte offsets of this lane's row trow = 8 lg +
+// (li >> 2) and of row trow + 4, x_lo / x_hi = tr_swz of the two: loop-invariant, computed once by the caller.
+__device__ __forceinline__ bf16x8 tr_swz_frag(const char* base, int lo, int x_lo, int hi, int x_hi, int u) {
+    return tr_pair(base + lo + ((u ^ x_lo) << 3), base + hi + ((u ^ x_hi) << 3));
+}
+
 __device__ const uint4 g_zero_page[4] = {};          // 64 zero bytes: source of the out-of-range chunks of an LDS-DMA tile
 
 __device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst_uniform) {

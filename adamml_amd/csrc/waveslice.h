@@ -56,13 +56,9 @@ __device__ __forceinline__ bf16x8 unstage8(const char* src) {
 }
 
 // MFMA fragment of the 16-channel block `blk` of a staged 32-row tile, pixels = the reduction dimension: two hardware transpose reads
-// (trow = 8 lg + (li >> 2), computed once by the caller)
+// (trow = 8 lg + (li >> 2), computed once by the caller; the read pair itself is common.h's tr_rows, which the tile kernels use too)
 __device__ __forceinline__ bf16x8 tr_frag(const char* base, int row_bytes, int blk, int trow, int li) {
-    const char* q = base + trow * row_bytes + (blk * 16 + 4 * (li & 3)) * 2;
-    union { s16x4 h[2]; bf16x8 v; } f;
-    f.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(q));
-    f.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(q + 4 * row_bytes));
-    return f.v;
+    return tr_rows(base + trow * row_bytes + (blk * 16 + 4 * (li & 3)) * 2, row_bytes);
 }
 
 // acc[mt][nt] += Z^T X over the 32 rows of two staged tiles (the fragments of the NARROWER operand are held, the other side streams)
