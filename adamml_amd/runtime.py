@@ -42,15 +42,15 @@ class Lazy:
         self.vec = None             # train-mode BatchNorm vectors [G,4,C] (scale, shift, mean, invstd) of a lazy tensor
         self.src = None             # lazy tensor this plain tensor is the materialisation of
         self.pre_sums = None        # BatchNorm-backward sums already accumulated by the producer of .grad
-        self.pool_grad = None       # (g_y, idx, OH, OW): .grad = routed max-pool gradient, recomputed by the BatchNorm backward
-        self.res = None             # (z, idn, act, idn_sole) of the residual add that produced this tensor
+        self.pool_grad = None       # _PoolGrad: .grad = routed max-pool gradient, recomputed by the BatchNorm backward
+        self.res = None             # _Residual: the residual add that produced this tensor
         self.alg = False            # BatchNorm backward of this conv output is algebraic: producers of .grad need not read .data
         self.sums_partial = False   # .pre_sums holds sum(g') only; sum(g' zhat) is derived from g'^T a (adamml_alg_sumfix)
         self.res_done = False       # .grad is already act-masked and the add's BatchNorm-backward sums are in place
         self.recompute = None       # data is None: the raw tensor was never written (conv_bn_add); recompute() materialises it
-        self.alg_in = None          # (lazy input of the conv that produced this tensor, its descriptor): algebraic backward only
+        self.alg_in = None          # _AlgIn: the conv that produced this tensor (conv_bn_add's raw output: algebraic backward only)
         self.prod = None            # P = g'^T a [G, C, Cin] already accumulated by the producer of .grad (adamml_conv_bwd_data_res_prod)
-        self.next_pre = None        # (ConvState, raw output, statistics) of a conv of THIS tensor that its producer already ran (conv_bn_add next_cs)
+        self.next_pre = None        # _NextPre: a conv of THIS tensor that its producer already ran (conv_bn_add next_cs)
         self._shape = None
 
     @property
@@ -62,6 +62,43 @@ class Lazy:
         if self.data is None:
             self.data = self.recompute()
         return self.data
+
+
+# What a forward function leaves on a Lazy for the backward functions, and these for one another: plain records, no behaviour.
+# Lazy.res: out = act(value(z) + value(idn)); idn_sole: idn has no other consumer; mask: 1 bit per element of act'(out), or None
+_Residual = collections.namedtuple("_Residual", "z idn act idn_sole mask")
+# Lazy.pool_grad: pooled gradient g [.., oh, ow, C], arg-max indices idx and selected raw values zsel of the 3x3/2 max-pool
+_PoolGrad = collections.namedtuple("_PoolGrad", "g idx zsel oh ow")
+# Lazy.next_pre: raw output y and statistics accumulators stats of the conv cs, already run on this tensor
+_NextPre = collections.namedtuple("_NextPre", "cs y stats")
+# Lazy.alg_in: lazy input x and descriptor d of the conv that produced this tensor
+_AlgIn = collections.namedtuple("_AlgIn", "x d")
+# algorithmic work of one conv layer (true input channels, each tensor touched once), for the roofline report: multiply-adds, bytes of
+# the input, the output and the weights
+_Work = collections.namedtuple("_Work", "macs in_b out_b w_b")
+
+
+def _sums_open(t):
+    """t's BatchNorm-backward sums are still open: the kernel that writes t's gradient may apply t's mask and accumulate them (t.pre_sums)."""
+    return t.requires_grad and t.vec is not None and t.grad is None and t.pre_sums is None
+
+
+def _idn_sums_open(res):
+    """The same for the identity operand of the residual add `res`, which must have promised that the add is its only consumer
+    (its own text: no pre_sums term is asked of the identity)."""
+    idn = res.idn
+    return idn is not None and res.idn_sole and idn.requires_grad and idn.vec is not None and idn.grad is None
+
+
+def _residual_finished(x, sa, sb=None):
+    """Publishes "the backward of the residual add that produced x is finished": x.grad is, or is about to be, written masked by the add's
+    activation, sa holds the BatchNorm-backward sums of the add's operand z (sum(g') only where z's backward is algebraic: such a kernel
+    does not read z), sb those of its identity operand where the kernel took them too.  _add_backward then only hands x.grad on."""
+    z = x.res.z
+    z.pre_sums, z.sums_partial = sa, z.alg
+    if sb is not None:
+        x.res.idn.pre_sums = sb
+    x.res_done = True
 
 
 class Tape:
@@ -237,23 +274,11 @@ class ConvState:
             call("adamml_pack_stem_weight", ptr(w), ptr(self.w_stem), self.cout, self.cin_true)
 
     def repack(self, need_dgrad):
-        w = self.weight
-        if self.depthwise:
-            if self.w_fwd is None:
-                self.w_fwd = torch.empty(self.kh * self.kw, self.cout, dtype=torch.float32, device=w.device)
-            call("adamml_pack_conv_weight", ptr(w), ptr(self.w_fwd), self.cout, 1, 1, self.kh, self.kw, 2)
-            return
-        if self.w_fwd is None:
-            self.w_fwd = torch.empty(self.cout, self.kh * self.kw * self.cin, dtype=torch.bfloat16, device=w.device)
-        call("adamml_pack_conv_weight", ptr(w), ptr(self.w_fwd), self.cout, self.cin_true, self.cin, self.kh, self.kw, 0)
-        if self.stem:
-            if self.w_stem is None:
-                self.w_stem = torch.empty(self.cout, 7 * 8 * 4, dtype=torch.bfloat16, device=w.device)
-            call("adamml_pack_stem_weight", ptr(w), ptr(self.w_stem), self.cout, self.cin_true)
-        if need_dgrad:
-            if self.w_dgrad is None:
-                self.w_dgrad = torch.empty(self.cin, self.kh * self.kw * self.cout, dtype=torch.bfloat16, device=w.device)
-            call("adamml_pack_conv_weight", ptr(w), ptr(self.w_dgrad), self.cout, self.cin_true, self.cin, self.kh, self.kw, 1)
+        """One launch per pack of this conv alone: the forward pack, then the stem's, then the data gradient's (mode 1)."""
+        for w, out, cout, cin_true, cin, kh, kw, mode, _ in self.pack_rows(need_dgrad):
+            call("adamml_pack_conv_weight", ptr(w), ptr(out), cout, cin_true, cin, kh, kw, mode)
+            if mode != 1:
+                self.repack_stem()
 
     def desc(self, x_shape, act, groups=1, in_gstride=0):
         n, h, w, c = x_shape
@@ -263,13 +288,33 @@ class ConvState:
                         in_gstride)
 
 
-def _bn_vectors(rt, bn, stats, count, C, device):
+def _bn_finalize(rt, bn, sums, nslots, count, C, device):
+    """Train-mode BatchNorm vectors [G,4,C] from the (already exchanged) statistic sums in nslots slots; updates the running statistics."""
     G = rt.groups
     vec = torch.empty(G, 4, C, dtype=torch.float32, device=device)
-    stats, nslots = rt.sync.reduce(stats, C, G)
-    call("adamml_bn_finalize", ptr(stats), nslots, G, float(count * rt.sync.world), ptr(bn.weight), ptr(bn.bias),
+    call("adamml_bn_finalize", ptr(sums), nslots, G, float(count * rt.sync.world), ptr(bn.weight), ptr(bn.bias),
          ptr(bn.running_mean), ptr(bn.running_var), BN_MOMENTUM, BN_EPS, ptr(vec), C)
     return vec
+
+
+def _bn_vectors(rt, bn, stats, count, C, device):
+    stats, nslots = rt.sync.reduce(stats, C, rt.groups)
+    return _bn_finalize(rt, bn, stats, nslots, count, C, device)
+
+
+def _bn_tail(rt, bn, y, stats, count, act):
+    """Train / eval BatchNorm + activation of the raw conv output y as one lazy tensor -> (out, vec).  stats: the train-mode accumulators
+    the conv's epilogue filled."""
+    C, dev = y.shape[3], y.device
+    if rt.training:
+        vec = _bn_vectors(rt, bn, stats, count, C, dev)
+        rt.touched_bns.append(bn)
+        out = Lazy(y, vec[0, 0], vec[0, 1], act, gs=4 * C)
+        out.vec = vec
+    else:
+        vec = _bn_eval_vectors(rt, bn, C, dev)
+        out = Lazy(y, vec[0], vec[1], act)
+    return out, vec
 
 
 def _bn_eval_vectors(rt, bn, C, device):
@@ -308,10 +353,9 @@ def _bn_backward(rt, out, y, vec, bn, act, count, defer_apply=False):
     if pool is not None:
         # the only consumer was a 3x3/2 max-pool: its routed gradient is recomputed from the pooled gradient and the
         # arg-max indices inside both BatchNorm-backward passes instead of being written and re-read twice
-        gy, idx, zsel, poh, pow_ = pool
         sums = _take_sums(rt, C)
         # sums over the windows (g_y, z_sel): each pooled gradient lands on exactly one input pixel
-        call("adamml_bn_bwd_reduce", ptr(gy), ptr(zsel), ptr(vec), act, ptr(sums), n // G * poh * pow_, C, G)
+        call("adamml_bn_bwd_reduce", ptr(pool.g), ptr(pool.zsel), ptr(vec), act, ptr(sums), n // G * pool.oh * pool.ow, C, G)
     elif out.pre_sums is not None:          # reduction fused into the kernel that produced g (already activation-masked)
         sums, out.pre_sums = out.pre_sums, None
     else:
@@ -330,7 +374,7 @@ def _bn_backward(rt, out, y, vec, bn, act, count, defer_apply=False):
     call("adamml_bn_bwd_finalize", *finalize, C, 1.0 / rt.sync.world)
     dz = torch.empty_like(y)
     if pool is not None:
-        call("adamml_maxpool2d_bwd_bn_apply", ptr(gy), ptr(idx), ptr(y), ptr(vec), act, ptr(coef), ptr(dz), n // G, oh, ow, C, poh, pow_, G)
+        call("adamml_maxpool2d_bwd_bn_apply", ptr(pool.g), ptr(pool.idx), ptr(y), ptr(vec), act, ptr(coef), ptr(dz), n // G, oh, ow, C, pool.oh, pool.ow, G)
     else:
         call("adamml_bn_bwd_apply", ptr(g), ptr(y), ptr(vec), act, ptr(coef), ptr(dz), P, C, G)
     return dz
@@ -354,10 +398,17 @@ def materialize(rt, x):
     return a
 
 
+# Profiler labels of the backward launches of one conv layer (_ConvCall.lab).  Device kernels (bench.py groups launches by them): kern behind
+# adamml_conv_bwd_data_res / _alg, kern_dual behind adamml_conv_bwd_data_dual, kern_acc[acc] behind adamml_conv_bwd_data (acc = 1: it adds to
+# the gradient), kern_bn behind adamml_conv_bwd_data_bn; roles: role_b of a bare data gradient, role_bf of one with a fused epilogue.
+# nar[kind]: adamml_conv1x1_narrow_supported by kind -- 0 forward, 1 weight gradient, 2 dual data gradient, 3 data gradient writing,
+# 4 accumulating or with BatchNorm sums; nar[2] also decides in _conv_backward.  A depthwise conv has none of them.
+_Labels = collections.namedtuple("_Labels", "kern kern_dual kern_acc kern_bn role_b role_bf nar", defaults=(None,) * 6)
+
+
 def _conv_labels(cs, d):
-    """Profiler labels of one conv_bn layer -> (kern_f, role_f) of the forward launch and, for the backward (_ConvCall.lab),
-    (kern, kern_dual, kern_acc, kern_bn, role_b, role_bf, nar); nar, the narrow-kernel probes of a dense conv, also decides in _conv_backward."""
-    # device kernel behind adamml_conv_fwd / adamml_conv_bwd_data[_bn] for this layer (bench.py groups launches by it)
+    """Profiler labels of one conv_bn layer -> (kern_f, role_f) of the forward launch and the _Labels of the backward."""
+    # device kernel behind adamml_conv_fwd / adamml_conv_bwd_data[_bn] for this layer
     kern = kern_f = kern_dual = kern_acc = kern_bn = nar = None
     if not cs.depthwise:
         lib = hip.load()
@@ -366,31 +417,30 @@ def _conv_labels(cs, d):
         nar = [bool(lib.adamml_conv1x1_narrow_supported(byref(d), k)) for k in range(5)] if cs.kh * cs.kw == 1 else [False] * 5
         kern_f = "conv1x1_narrow_fwd_kernel" if nar[0] else kern
         kern_dual = "conv1x1_narrow_dgrad_kernel" if nar[2] else kern
-        kern_acc = ("conv1x1_narrow_dgrad_kernel" if nar[4] else kern, "conv1x1_narrow_fwd_kernel" if nar[3] else kern)      # [accumulating?]
+        kern_acc = ("conv1x1_narrow_fwd_kernel" if nar[3] else kern, "conv1x1_narrow_dgrad_kernel" if nar[4] else kern)      # [acc]
         kern_bn = "conv1x1_narrow_dgrad_kernel" if nar[4] else kern
         if cs.kh * cs.kw == 1 and d.Cin >= 256:
             # the wide 1x1 layers of ResNet layers 3-4 run on the activation-stationary streaming kernels of csrc/conv1x1_wide.hip
-            wide = [bool(lib.adamml_conv1x1_wide_supported(byref(d), k)) for k in (0, 3, 4)]
+            wide = {k: bool(lib.adamml_conv1x1_wide_supported(byref(d), k)) for k in (0, 3, 4)}      # (the kinds of nar it serves)
             if wide[0]:
                 kern_f = "wide_all_kernel"
-            kern_acc = ("wide_all_kernel" if wide[2] else kern_acc[0], "wide_all_kernel" if wide[1] else kern_acc[1])
+            kern_acc = ("wide_all_kernel" if wide[3] else kern_acc[0], "wide_all_kernel" if wide[4] else kern_acc[1])
     role_f = None if cs.depthwise else (R_KXK if cs.kh * cs.kw > 1 else R_1X1)
     role_b = None if cs.depthwise else (R_KXK if (cs.kh * cs.kw > 1 or cs.stride > 1) else R_1X1)
     role_bf = role_b if role_b != R_1X1 else R_FUSED          # data gradient with a fused BatchNorm-backward / residual epilogue
-    return kern_f, role_f, (kern, kern_dual, kern_acc, kern_bn, role_b, role_bf, nar)
+    return kern_f, role_f, _Labels(kern, kern_dual, kern_acc, kern_bn, role_b, role_bf, nar)
 
 
 class _ConvCall:
     """What the backward of one conv_bn / conv_bn_add call needs, complete when its forward creates it: x -> conv -> y (raw) -> out (lazy); the
-    decisions taken at forward time (sole_consumer, last_consumer, stem, lab[-1] = nar); the layer's algorithmic work and its labels
-    (_conv_labels) for the roofline report.  conv_bn_add: y is None (never stored), Gm / sv = the _gram_colsum of x its forward computed."""
-    __slots__ = ("rt", "x", "y", "out", "vec", "bn", "cs", "d", "count", "act", "sole_consumer", "last_consumer", "stem",
-                 "macs", "in_b", "out_b", "w_b", "lab", "Gm", "sv")
+    decisions taken at forward time (sole_consumer, last_consumer, stem, lab.nar); the layer's algorithmic work (_Work) and its labels
+    (_Labels) for the roofline report.  conv_bn_add: y is None (never stored), Gm / sv = the _gram_colsum of x its forward computed."""
+    __slots__ = ("rt", "x", "y", "out", "vec", "bn", "cs", "d", "count", "act", "sole_consumer", "last_consumer", "stem", "work", "lab", "Gm", "sv")
 
-    def __init__(self, rt, x, y, out, vec, bn, cs, d, count, act, sole_consumer, last_consumer, stem, macs, in_b, out_b, w_b, lab, Gm=None, sv=None):
+    def __init__(self, rt, x, y, out, vec, bn, cs, d, count, act, sole_consumer, last_consumer, stem, work, lab, Gm=None, sv=None):
         self.rt, self.x, self.y, self.out, self.vec, self.bn, self.cs, self.d, self.count, self.act = rt, x, y, out, vec, bn, cs, d, count, act
         self.sole_consumer, self.last_consumer, self.stem = sole_consumer, last_consumer, stem
-        self.macs, self.in_b, self.out_b, self.w_b, self.lab, self.Gm, self.sv = macs, in_b, out_b, w_b, lab, Gm, sv
+        self.work, self.lab, self.Gm, self.sv = work, lab, Gm, sv
 
 
 def _launch_conv_fwd(cs, d, x, y, stem, stats):
@@ -425,44 +475,36 @@ def conv_bn(rt, x, cs, bn, act, sole_consumer=False, last_consumer=False):
     # forward already run by the producer of x (conv_bn_add next_cs).  Only the conv the result was computed FOR consumes it; another
     # conv of x issued first (a downsample branch, a reordering) leaves it in place (round-5 advisor finding: it used to be cleared by
     # whichever conv came first, and the fused result was then silently recomputed) -- NetRT.end_forward counts the ones nobody claimed
-    pre = x.next_pre if (x.next_pre is not None and x.next_pre[0] is cs and rt.training) else None
+    pre = x.next_pre if (x.next_pre is not None and x.next_pre.cs is cs and rt.training) else None
     if pre is not None:
         x.next_pre = None
         rt.pre_pending -= 1
-    y = pre[1] if pre is not None else torch.empty(G * d.N, d.OH, d.OW, d.Cout, dtype=torch.bfloat16, device=dev)
+    y = pre.y if pre is not None else torch.empty(G * d.N, d.OH, d.OW, d.Cout, dtype=torch.bfloat16, device=dev)
     C = d.Cout
     count = d.N * d.OH * d.OW               # elements per channel per group
     stem = cs.stem and x.scale is None and hip.load().adamml_conv_stem_supported(byref(d))
     if x.shape[3] != cs.cin and not stem:
         raise RuntimeError("conv_bn: 4-channel pixels need the 7x7 stem kernel, which does not support this shape")
-    # algorithmic work of this layer (true input channels, each tensor touched once), for the roofline report
-    macs = float(count) * G * C * cs.kh * cs.kw * (1 if cs.depthwise else cs.cin_true)
-    in_b, out_b = 2.0 * G * d.N * d.H * d.W * cs.cin_true, 2.0 * G * count * C
-    w_b = 2.0 * C * cs.kh * cs.kw * (1 if cs.depthwise else cs.cin_true)
+    work = _Work(macs=float(count) * G * C * cs.kh * cs.kw * (1 if cs.depthwise else cs.cin_true),
+                 in_b=2.0 * G * d.N * d.H * d.W * cs.cin_true, out_b=2.0 * G * count * C,
+                 w_b=2.0 * C * cs.kh * cs.kw * (1 if cs.depthwise else cs.cin_true))
     kern_f, role_f, lab = _conv_labels(cs, d)
-    hip.next_meta = (2 * macs, in_b + out_b + w_b, "conv_stem_kernel" if stem else kern_f, role_f)
+    hip.next_meta = (2 * work.macs, work.in_b + work.out_b + work.w_b, "conv_stem_kernel" if stem else kern_f, role_f)
     if pre is not None:
         hip.next_meta = (0.0, 0.0)
-        stats = pre[2]
+        stats = pre.stats
     else:
         stats = rt.fwd_arena.take(G * 2 * C * STAT_SLOTS) if rt.training else None
         _launch_conv_fwd(cs, d, x, y, stem, stats)
     if rt.capture is not None:
         rt.capture.setdefault(id(cs.weight), []).append(y)
-    if rt.training:
-        vec = _bn_vectors(rt, bn, stats, count, C, dev)
-        rt.touched_bns.append(bn)
-        out = Lazy(y, vec[0, 0], vec[0, 1], act, gs=4 * C)
-        out.vec = vec
-        out.alg = bool(rt.tape.need_grad and act == ACT_NONE and not cs.depthwise and not stem and x.requires_grad
-                       and cs.weight.requires_grad and _alg_supported(cs, d))
-    else:
-        vec = _bn_eval_vectors(rt, bn, C, dev)
-        out = Lazy(y, vec[0], vec[1], act)
+    out, vec = _bn_tail(rt, bn, y, stats, count, act)
+    out.alg = bool(rt.training and rt.tape.need_grad and act == ACT_NONE and not cs.depthwise and not stem and x.requires_grad
+                   and cs.weight.requires_grad and _alg_supported(cs, d))
     # nothing below this tensor takes a gradient (a frozen conv and BatchNorm on an input that needs none): its consumers stop here
     out.requires_grad = bool(x.requires_grad or cs.weight.requires_grad or bn.weight.requires_grad or bn.bias.requires_grad)
     if rt.tape.need_grad:
-        c = _ConvCall(rt, x, y, out, vec, bn, cs, d, count, act, sole_consumer, last_consumer, stem, macs, in_b, out_b, w_b, lab)
+        c = _ConvCall(rt, x, y, out, vec, bn, cs, d, count, act, sole_consumer, last_consumer, stem, work, lab)
         rt.tape.record(lambda: _conv_backward(c))
     return out
 
@@ -472,35 +514,35 @@ def _conv_backward(c):
     rt, x, out, cs, d = c.rt, c.x, c.out, c.cs, c.d
     if out.grad is None and out.pool_grad is None:
         return
+    # what both dual arms ask: a dense train-mode conv, not the stem, whose input takes a gradient and whose gradient is not a pooled one
+    dual = not cs.depthwise and not c.stem and out.pool_grad is None and x.requires_grad and rt.training
     if out.alg and out.pool_grad is None:
         _conv1x1_backward_alg(c, c.y)
-    elif c.act == ACT_NONE and not cs.depthwise and not c.stem and out.pool_grad is None and x.requires_grad \
-            and rt.training and hip.load().adamml_conv_bwd_data_dual_supported(byref(d)):
+    elif dual and c.act == ACT_NONE and hip.load().adamml_conv_bwd_data_dual_supported(byref(d)):
         _conv1x1_backward_dual(c)
-    elif c.act != ACT_NONE and out.pre_sums is not None and not cs.depthwise and not c.stem and out.pool_grad is None \
-            and x.requires_grad and rt.training and cs.kh * cs.kw == 1 and c.lab[-1][2]:
+    elif dual and c.act != ACT_NONE and out.pre_sums is not None and cs.kh * cs.kw == 1 and c.lab.nar[2]:
         # expansion conv of an inverted residual (round 6): its gradient arrives ALREADY masked by its ReLU6 (the depthwise conv's fused
         # backward applied the mask and accumulated the sums), so the BatchNorm-backward apply is the same affine A g' + B z + C as for
-        # a linear BatchNorm and folds into the narrow streaming data gradient's loader the same way
+        # a linear BatchNorm and folds into the narrow streaming data gradient's loader (nar[2]) the same way
         _conv1x1_backward_dual(c)
+    # (besides x's open sums the fused kernel asks that x is no materialised copy and that its lazy scale / shift ARE its train-mode vectors)
     elif cs.depthwise and out.pool_grad is None and out.pre_sums is not None and rt.training and c.sole_consumer \
-            and cs.weight.requires_grad and x.requires_grad and x.grad is None and x.src is None and x.vec is not None \
-            and x.pre_sums is None and x.scale is not None and x.scale.data_ptr() == x.vec.data_ptr() \
-            and hip.load().adamml_dwconv_bwd_fused_supported(byref(d)):
+            and cs.weight.requires_grad and _sums_open(x) and x.src is None and x.scale is not None \
+            and x.scale.data_ptr() == x.vec.data_ptr() and hip.load().adamml_dwconv_bwd_fused_supported(byref(d)):
         _conv_backward_dw_fused(c)
     else:
         _conv_backward_plain(c)
 
 
 def _conv_backward_dw_fused(c):
-    rt, x, cs, d = c.rt, c.x, c.cs, c.d
+    rt, x, cs, d, w = c.rt, c.x, c.cs, c.d, c.work
     # g is already masked by this conv's activation (out.pre_sums: the projection's data gradient did that), so
     # dz = A g + B z + C in the loader; apply + weight gradient + data gradient (mask / sums of the expansion) in one pass
     g, coef, aff = _bn_backward(rt, c.out, c.y, c.vec, c.bn, c.act, c.count, defer_apply=True)
     x.grad = torch.empty_like(x.data)
     sums = _take_sums(rt, d.Cin)
     ws = hip.scratch(hip.load().adamml_dwconv_bwd_fused_workspace(byref(d)), x.data.device)
-    hip.next_meta = (4 * c.macs, 2 * c.in_b + 2 * c.out_b + 2 * c.w_b, "dwconv_bwd_fused_kernel", None)
+    hip.next_meta = (4 * w.macs, 2 * w.in_b + 2 * w.out_b + 2 * w.w_b, "dwconv_bwd_fused_kernel", None)
     call("adamml_dwconv_bwd_fused", byref(d), ptr(g), ptr(c.y), ptr(aff), ptr(cs.w_fwd), ptr(x.data), ptr(x.vec), x.act, ptr(x.grad),
          ptr(sums), ptr(cs.weight.grad), ptr(ws), ws.numel() * 4)
     x.pre_sums = sums
@@ -508,8 +550,7 @@ def _conv_backward_dw_fused(c):
 
 def _conv_backward_plain(c):
     """The unfused form: BatchNorm backward into dz, the weight gradient from dz, then the data gradient that fits the conv and x."""
-    x, cs, d = c.x, c.cs, c.d
-    kern, _, kern_acc, kern_bn, role_b, role_bf, _ = c.lab
+    x, cs, d, w, lab = c.x, c.cs, c.d, c.work, c.lab
     dz = _bn_backward(c.rt, c.out, c.y, c.vec, c.bn, c.act, c.count)
     if cs.weight.requires_grad:
         _launch_wgrad(c, dz)
@@ -518,7 +559,7 @@ def _conv_backward_plain(c):
     if cs.depthwise:
         # (the depthwise copy of _claim_grad_and_sums stays here: its kernel has a probe of its own and no accumulating form)
         acc = _claim_grad(x)
-        hip.next_meta = (2 * c.macs, c.in_b * (1 + acc) + c.out_b + c.w_b, kern, role_b)
+        hip.next_meta = (2 * w.macs, w.in_b * (1 + acc) + w.out_b + w.w_b, lab.kern, lab.role_b)
         tgt = x.src if x.src is not None else x
         if c.sole_consumer and acc == 0 and tgt.vec is not None and tgt.pre_sums is None \
                 and hip.load().adamml_dwconv_bwd_data_bn_supported(byref(d)):
@@ -533,18 +574,18 @@ def _conv_backward_plain(c):
     else:
         acc, sums, tail = _claim_grad_and_sums(c)
         if sums is not None:
-            hip.next_meta = (2 * c.macs, 2 * c.in_b + c.out_b + c.w_b, kern_bn, role_bf)
+            hip.next_meta = (2 * w.macs, 2 * w.in_b + w.out_b + w.w_b, lab.kern_bn, lab.role_bf)
             call("adamml_conv_bwd_data_bn", byref(d), ptr(dz), ptr(cs.w_dgrad), ptr(x.grad), *tail)
         else:
-            hip.next_meta = (2 * c.macs, c.in_b * (1 + acc) + c.out_b + c.w_b, kern_acc[0 if acc else 1], role_b)
+            hip.next_meta = (2 * w.macs, w.in_b * (1 + acc) + w.out_b + w.w_b, lab.kern_acc[acc], lab.role_b)
             call("adamml_conv_bwd_data", byref(d), ptr(dz), ptr(cs.w_dgrad), ptr(x.grad), acc)
 
 
 def _launch_wgrad(c, dz):
     """The weight gradient of a conv (depthwise / 7x7 stem / dense) from dz and its lazy input, on the weight-gradient stream."""
-    x, cs, d = c.x, c.cs, c.d
+    x, cs, d, w = c.x, c.cs, c.d, c.work
     with _on_wgrad_stream(c.rt, (dz, x.data, x.scale)):
-        hip.next_meta = (2 * c.macs, c.in_b + c.out_b + 2 * c.w_b, None, None if cs.depthwise else R_WGRAD)
+        hip.next_meta = (2 * w.macs, w.in_b + w.out_b + 2 * w.w_b, None, None if cs.depthwise else R_WGRAD)
         if cs.depthwise:
             ws = hip.wgrad_workspace(d, 0, dz.device, depthwise=True)
             call("adamml_dwconv_bwd_weight", byref(d), ptr(dz), ptr(x.data), ptr(x.scale), ptr(x.shift), ptr(cs.weight.grad),
@@ -574,6 +615,7 @@ def _claim_grad_and_sums(c):
     x = c.x
     acc = _claim_grad(x)
     tgt = x.src if x.src is not None else x
+    # (own text, not _sums_open(tgt): the unclaimed gradient asked for is x's, acc, and x may be the materialised copy of tgt)
     if not (c.sole_consumer and acc == 0 and tgt.vec is not None and tgt.pre_sums is None):
         return acc, None, (None, None, 0, None)
     sums = tgt.pre_sums = _take_sums(c.rt, c.d.Cin)
@@ -583,9 +625,10 @@ def _claim_grad_and_sums(c):
 def _dgrad_finish_residual(c, dz, acc):
     """Data gradient of the last consumer of a residual add's output x that also finishes the add's backward (conv_bn, last_consumer)."""
     rt, x, cs, d = c.rt, c.x, c.cs, c.d
-    G, macs, in_b, out_b, w_b, kern = rt.groups, c.macs, c.in_b, c.out_b, c.w_b, c.lab[0]
-    z, idn, ract, idn_sole, rmask = x.res
-    fb = idn is not None and idn_sole and idn.requires_grad and idn.vec is not None and idn.grad is None
+    G, (macs, in_b, out_b, w_b), kern = rt.groups, c.work, c.lab.kern
+    res = x.res
+    z, idn, ract, rmask = res.z, res.idn, res.act, res.mask
+    fb = _idn_sums_open(res)
     sa = _take_sums(rt, d.Cin)
     sb = _take_sums(rt, d.Cin) if fb else None
     fb_alg = fb and idn.alg               # the downsample BatchNorm shares sum(g'); its second moment comes from g'^T a too
@@ -593,33 +636,29 @@ def _dgrad_finish_residual(c, dz, acc):
                                        + (1 if (fb and not (fb and idn.alg)) else 0)) + out_b + w_b, kern, R_FUSED)
     fbk = fb and not fb_alg
     ain = z.alg_in
-    if (z.alg and ain is not None and (not fb or fb_alg) and acc == 1 and rmask is not None and ain[0].data is not None
-            and hip.load().adamml_conv_bwd_data_res_prod_supported(byref(d), ain[1].Cin)):
-        # the product g'^T a of the algebraic backward of the conv that produced z (its input a = ain[0]) is accumulated
+    if (z.alg and ain is not None and (not fb or fb_alg) and acc == 1 and rmask is not None and ain.x.data is not None
+            and hip.load().adamml_conv_bwd_data_res_prod_supported(byref(d), ain.d.Cin)):
+        # the product g'^T a of the algebraic backward of the conv that produced z (its input a = ain.x) is accumulated
         # from the gradient tile inside this kernel: no separate pass over g' and a
-        xa = ain[0]
-        z.prod = torch.empty(G, d.Cin, ain[1].Cin, dtype=torch.float32, device=dz.device)
+        xa, Ca = ain.x, ain.d.Cin
+        z.prod = torch.empty(G, d.Cin, Ca, dtype=torch.float32, device=dz.device)
         need = hip.load().adamml_conv_bwd_data_res_prod_workspace(byref(d))
         wsp = hip.scratch(need, dz.device)
         # (layer 1: the barrier-free streaming kernel of csrc/res_prod_stream.hip; its workspace is sized for it)
-        kern_rp = "res_prod_stream_kernel" if hip.load().adamml_conv_bwd_data_res_prod_streams(byref(d), ain[1].Cin) else kern
-        hip.next_meta = (2 * macs + 2.0 * G * d.N * d.H * d.W * d.Cin * ain[1].Cin, in_b * 2.0625 + out_b + w_b + 2.0 * G * d.N * d.H * d.W * ain[1].Cin, kern_rp, R_FUSED)
+        kern_rp = "res_prod_stream_kernel" if hip.load().adamml_conv_bwd_data_res_prod_streams(byref(d), Ca) else kern
+        hip.next_meta = (2 * macs + 2.0 * G * d.N * d.H * d.W * d.Cin * Ca, in_b * 2.0625 + out_b + w_b + 2.0 * G * d.N * d.H * d.W * Ca, kern_rp, R_FUSED)
         call("adamml_conv_bwd_data_res_prod", byref(d), ptr(dz), ptr(cs.w_dgrad), ptr(x.grad), ptr(rmask), ract, ptr(sa), ptr(xa.data),
-             ptr(xa.scale), ptr(xa.shift), xa.act, xa.gs, ain[1].Cin, ptr(z.prod), ptr(wsp), wsp.numel() * 4)
+             ptr(xa.scale), ptr(xa.shift), xa.act, xa.gs, Ca, ptr(z.prod), ptr(wsp), wsp.numel() * 4)
     else:
         if acc == 1 and rmask is not None and z.alg and hip.load().adamml_conv_bwd_data_res_streams(byref(d)) == 1:
             hip.next_meta = hip.next_meta[:2] + ("res_prod_stream_kernel", R_FUSED)       # (layer 2: csrc/res_prod_stream.hip)
         call("adamml_conv_bwd_data_res", byref(d), ptr(dz), ptr(cs.w_dgrad), ptr(x.grad), acc, ptr(x.data), ptr(rmask), ract,
              None if z.alg else ptr(z.data), ptr(z.vec), ptr(sa), ptr(idn.data) if fbk else None, ptr(idn.vec) if fbk else None,
              ptr(sb) if fbk else None)
-    z.pre_sums = sa
-    z.sums_partial = z.alg
-    if fb:
-        if fb_alg:
-            call("adamml_copy2d", ptr(sb), 2 * d.Cin * 8, ptr(sa), 2 * d.Cin * 8, d.Cin * 8, G * STAT_SLOTS)       # the sum(g') columns
-            idn.sums_partial = True
-        idn.pre_sums = sb
-    x.res_done = True
+    if fb_alg:
+        call("adamml_copy2d", ptr(sb), 2 * d.Cin * 8, ptr(sa), 2 * d.Cin * 8, d.Cin * 8, G * STAT_SLOTS)       # the sum(g') columns
+        idn.sums_partial = True
+    _residual_finished(x, sa, sb)
 
 
 def stem1_supported(cs, x):
@@ -650,17 +689,9 @@ def conv_stem1_bn(rt, x1, cs, bn, act):
     count = B * d.OH * d.OW
     istr, gstr = G * H * W, H * W
     hip.next_meta = (2.0 * count * G * C * 9, 4.0 * G * B * H * W + 2.0 * G * count * C)
-    if rt.training:
-        stats = rt.fwd_arena.take(G * 2 * C * STAT_SLOTS)
-        call("adamml_conv_stem1_fwd", byref(d), ptr(x1), istr, gstr, ptr(cs.w_fwd), ptr(y), ptr(stats))
-        vec = _bn_vectors(rt, bn, stats, count, C, dev)
-        rt.touched_bns.append(bn)
-        out = Lazy(y, vec[0, 0], vec[0, 1], act, gs=4 * C)
-        out.vec = vec
-    else:
-        call("adamml_conv_stem1_fwd", byref(d), ptr(x1), istr, gstr, ptr(cs.w_fwd), ptr(y), None)
-        vec = _bn_eval_vectors(rt, bn, C, dev)
-        out = Lazy(y, vec[0], vec[1], act)
+    stats = rt.fwd_arena.take(G * 2 * C * STAT_SLOTS) if rt.training else None
+    call("adamml_conv_stem1_fwd", byref(d), ptr(x1), istr, gstr, ptr(cs.w_fwd), ptr(y), ptr(stats))
+    out, vec = _bn_tail(rt, bn, y, stats, count, act)
     if rt.capture is not None:
         rt.capture.setdefault(id(cs.weight), []).append(y)
     if rt.tape.need_grad:
@@ -757,8 +788,8 @@ def _conv1x1_backward_alg(c, y):
         dx = (W^T diag(A)) g' + (W^T diag(B) W) a + W^T C,      dW = A (.) (g'^T a) + B (.) (W G) + C (x) s,  G = a^T a, s = sum a.
     The products over pixels (g'^T a, a^T a, sum a) run on the weight-gradient stream; the data gradient is one GEMM over the
     concatenated input [g' | a] with per-group weights.  c.Gm / c.sv: G and s where the forward already computed them (conv_bn_add)."""
-    rt, out, x, vec, cs, d, kern = c.rt, c.out, c.x, c.vec, c.cs, c.d, c.lab[0]
-    macs, in_b, out_b, w_b = c.macs, c.in_b, c.out_b, c.w_b
+    rt, out, x, vec, cs, d, kern = c.rt, c.out, c.x, c.vec, c.cs, c.d, c.lab.kern
+    macs, in_b, out_b, w_b = c.work
     G = rt.groups
     Cout, Cin = d.Cout, d.Cin
     dev = y.device
@@ -815,12 +846,12 @@ def _conv1x1_backward_dual(c):
     downsample BN of a bottleneck, the projection conv of an inverted residual.  After the BatchNorm-backward sums are
     finalised, the data-gradient kernel reads (g, z) directly and forms dz = A g + B z + C in its loader; dz is written
     once, as a side output, for the weight-gradient kernel.  Saves one full pass over the layer's largest tensor."""
-    x, y, cs, d = c.x, c.y, c.cs, c.d
+    x, y, cs, d, w = c.x, c.y, c.cs, c.d, c.work
     g, coef, aff = _bn_backward(c.rt, c.out, y, c.vec, c.bn, ACT_NONE, c.count, defer_apply=True)
     need_w = cs.weight.requires_grad
     dz = torch.empty_like(y) if need_w else None
     acc, sums, tail = _claim_grad_and_sums(c)
-    hip.next_meta = (2 * c.macs, c.in_b * (1 + acc + (0 if sums is None else 1)) + (3 if need_w else 2) * c.out_b + c.w_b, c.lab[1],
+    hip.next_meta = (2 * w.macs, w.in_b * (1 + acc + (0 if sums is None else 1)) + (3 if need_w else 2) * w.out_b + w.w_b, c.lab.kern_dual,
                      R_FUSED)
     call("adamml_conv_bwd_data_dual", byref(d), ptr(g), ptr(y), ptr(aff), ptr(dz), ptr(cs.w_dgrad), ptr(x.grad), acc,
          *tail)
@@ -833,8 +864,7 @@ def _residual_fusable(x, d):
     be finished by the data-gradient epilogue of the conv described by d."""
     if x.res is None or x.res_done or x.src is not None:
         return False
-    z = x.res[0]
-    if not (z.requires_grad and z.vec is not None and z.grad is None and z.pre_sums is None):
+    if not _sums_open(x.res.z):
         return False
     return bool(hip.load().adamml_conv_bwd_data_res_supported(byref(d)))
 
@@ -867,21 +897,21 @@ def add_act(rt, z, idn, act, idn_sole=False):
     mask_t = torch.empty(n, h, w, C // 8, dtype=torch.uint8, device=out_t.device) if (rt.tape.need_grad and act != ACT_NONE) else None
     call("adamml_bn_act_add_mask", ptr(z.data), ptr(z.scale), ptr(z.shift), z.gs, act, *_idn_args(idn), ptr(out_t), ptr(mask_t), P, C, G)
     out = Lazy(out_t)
-    out.res = (z, idn, act, idn_sole, mask_t)
+    out.res = _Residual(z, idn, act, idn_sole, mask_t)
     if rt.tape.need_grad:
-        rt.tape.record(lambda: _add_backward(rt, out, out_t, z, idn, act, idn_sole, P, C))
+        rt.tape.record(lambda: _add_backward(rt, out, out_t, P, C))
     return out
 
 
-def _add_backward(rt, out, out_t, z, idn, act, idn_sole, P, C):
-    """Backward of out = act(value(z) + value(idn)) (add_act / conv_bn_add)."""
+def _add_backward(rt, out, out_t, P, C):
+    """Backward of the residual add out.res (add_act / conv_bn_add); out_t: the add's stored output (None with conv_bn_add's pool fused:
+    that add arrives finished)."""
     G = rt.groups
+    z, idn, act = out.res.z, out.res.idn, out.res.act
     g = out.grad
     out.grad = None
     if g is None:
         return
-    fa = z.requires_grad and z.vec is not None and z.grad is None
-    fb = idn is not None and idn_sole and idn.requires_grad and idn.vec is not None and idn.grad is None
     if out.res_done:
         # the last consumer's data-gradient epilogue already masked g and accumulated the sums (conv_bn)
         out.res_done = False
@@ -889,6 +919,9 @@ def _add_backward(rt, out, out_t, z, idn, act, idn_sole, P, C):
         if idn is not None:
             _accum_grad(idn, g)
         return
+    # (the pre_sums term of _sums_open holds here: z's only consumer is this add, so only a kernel that finished this add's backward
+    # could have filled z.pre_sums, and that is the res_done arm above)
+    fa, fb = _sums_open(z), _idn_sums_open(out.res)
     g2 = torch.empty_like(g) if act != ACT_NONE else g
     if fa or fb:
         sa = _take_sums(rt, C) if fa else None
@@ -935,7 +968,7 @@ def conv_bn_add_tpool_supported(rt, x, cs, idn, act, frames, mode):
     return bool(hip.load().adamml_conv_fwd_bn_add_tpool_supported(byref(d), frames, act, 1 if x.scale is not None else 0))
 
 
-_ADD_LABELS = ("conv_gemm_kernel", None, None, None, None, None, None)      # the `lab` of a conv_bn_add record: only kern is read
+_ADD_LABELS = _Labels("conv_gemm_kernel")      # the `lab` of a conv_bn_add record: only kern is read
 
 
 def _bn_add_vectors(rt, x, cs, bn, d, count):
@@ -949,9 +982,7 @@ def _bn_add_vectors(rt, x, cs, bn, d, count):
         call("adamml_gram_stats", ptr(cs.w_fwd), ptr(Gm), ptr(sv), ptr(sums), C, Cin, G)
         if rt.sync.enabled:                  # SyncBatchNorm: the (already collapsed) sums are all-reduced, as SyncCtx.reduce does
             sums = interleave.exchange(sums, rt.sync.group)
-        vec = torch.empty(G, 4, C, dtype=torch.float32, device=dev)
-        call("adamml_bn_finalize", ptr(sums), 1, G, float(count * rt.sync.world), ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean),
-             ptr(bn.running_var), BN_MOMENTUM, BN_EPS, ptr(vec), C)
+        vec = _bn_finalize(rt, bn, sums, 1, count, C, dev)
         rt.touched_bns.append(bn)
         return vec, Gm, sv
     # [G][4][C] with (scale, shift) of the eval-mode affine in rows 0 / 1 of every group (the epilogue reads nothing else): stream-ordered
@@ -971,7 +1002,7 @@ def _bn_add_vectors(rt, x, cs, bn, d, count):
 def _bn_add_forward(rt, x, cs, d, vec, idn, act, tpool, next_cs, work):
     """The forward launch of conv_bn_add -> (out_t, mask_t, code_t, nxt): pooling too (out_t pooled, code_t for its backward), running the
     NEXT block's conv1 too (nxt, for Lazy.next_pre), or plain.  mask_t: 1 bit per element of act'(out), for the fused residual backward."""
-    (macs, in_b, out_b, w_b), kern = work, _ADD_LABELS[0]
+    (macs, in_b, out_b, w_b), kern = work, _ADD_LABELS.kern
     G, C, count, dev, need_grad = rt.groups, d.Cout, d.N * d.OH * d.OW, x.data.device, rt.tape.need_grad
     if tpool:
         to = tpool // 2
@@ -996,7 +1027,7 @@ def _bn_add_forward(rt, x, cs, d, vec, idn, act, tpool, next_cs, work):
                          + (out_b / 16 if mask_t is not None else 0), "conv1x1_fadd_next_kernel", R_FUSED)
         call("adamml_conv_fwd_bn_add_next", byref(d), ptr(x.data), ptr(cs.w_fwd), ptr(x.scale), ptr(x.shift), ptr(vec),
              *_idn_args(idn), act, ptr(out_t), ptr(mask_t), ptr(next_cs.w_fwd), ptr(y_n), ptr(st_n))
-        return out_t, mask_t, None, (next_cs, y_n, st_n)
+        return out_t, mask_t, None, _NextPre(next_cs, y_n, st_n)
     if idn is not None and hip.load().adamml_conv_fwd_bn_add_streams(byref(d)):
         hip.next_meta = hip.next_meta[:2] + ("conv1x1_fadd_stream_kernel", R_FUSED)       # (the layer-2 shape: csrc/conv1x1_fadd_stream.hip)
     call("adamml_conv_fwd_bn_add", byref(d), ptr(x.data), ptr(cs.w_fwd), ptr(x.scale), ptr(x.shift), ptr(vec),
@@ -1013,9 +1044,9 @@ def _bn_add_register_backward(c, out, out_t, mask_t, code_t, idn, idn_sole, tpoo
     blk = out if not tpool else Lazy(None)
     if tpool:
         blk._shape = z._shape
-    blk.res = (z, idn, c.act, idn_sole, mask_t)
+    blk.res = _Residual(z, idn, c.act, idn_sole, mask_t)
     rt.tape.record(lambda: _bn_add_conv_backward(c))
-    rt.tape.record(lambda: _add_backward(rt, blk, out_t if not tpool else None, z, idn, c.act, idn_sole, c.count, c.d.Cout))
+    rt.tape.record(lambda: _add_backward(rt, blk, out_t if not tpool else None, c.count, c.d.Cout))
     if tpool:
         rt.tape.record(lambda: _bn_add_pool_backward(c, out, blk, code_t, tpool))
 
@@ -1030,7 +1061,7 @@ def _bn_add_raw_output(rt, x, cs, d, vec):
     z.vec = vec
     z.alg = True
     z.recompute = lambda: _bn_add_recompute(x, cs, d, full_shape)
-    z.alg_in = (x, d)
+    z.alg_in = _AlgIn(x, d)
     return z
 
 
@@ -1066,14 +1097,13 @@ def _bn_add_pool_backward(c, out, blk, code_t, tpool):
         # kernel read the 4.6 GB of g' back)
         P = torch.empty(G, C, d.Cin, dtype=torch.float32, device=dev)
         ws = hip.scratch(lib.adamml_temporal_pool_bwd_code_prod_workspace(d.N // tpool, tpool, d.OH * d.OW, C, d.Cin, G), dev)
-        hip.next_meta = (2 * c.macs, c.in_b + 1.5 * c.out_b + c.out_b / 16, "tpool_bwd_prod_kernel", R_WGRAD)
+        hip.next_meta = (2 * c.work.macs, c.work.in_b + 1.5 * c.work.out_b + c.work.out_b / 16, "tpool_bwd_prod_kernel", R_WGRAD)
         call("adamml_temporal_pool_bwd_code_prod", ptr(g), ptr(code_t), ptr(gx), ptr(sa), ptr(x.data), ptr(x.scale), ptr(x.shift), x.gs, x.act,
              ptr(P), ptr(ws), ws.numel() * 4, d.N // tpool, tpool, d.OH * d.OW, C, d.Cin, G)
         z.prod = P
     else:
         call("adamml_temporal_pool_bwd_code", ptr(g), ptr(code_t), ptr(gx), ptr(sa), d.N // tpool, tpool, d.OH * d.OW, C, G)
-    z.pre_sums, z.sums_partial = sa, True
-    blk.res_done = True
+    _residual_finished(blk, sa)          # (sum(g') only: z is conv_bn_add's raw output, whose backward is always algebraic -- _bn_add_raw_output)
     blk.grad = gx
 
 
@@ -1093,10 +1123,9 @@ def conv_bn_add(rt, x, cs, bn, idn, act, idn_sole=False, tpool=0, next_cs=None):
     d = cs.desc(x.shape, x.act, G, x.gs)
     C = d.Cout
     count = d.N * d.OH * d.OW
-    macs = float(count) * G * C * cs.cin_true
-    in_b, out_b, w_b = 2.0 * G * count * cs.cin_true, 2.0 * G * count * C, 2.0 * C * cs.cin_true
+    work = _Work(macs=float(count) * G * C * cs.cin_true, in_b=2.0 * G * count * cs.cin_true, out_b=2.0 * G * count * C, w_b=2.0 * C * cs.cin_true)
     vec, Gm, sv = _bn_add_vectors(rt, x, cs, bn, d, count)
-    out_t, mask_t, code_t, nxt = _bn_add_forward(rt, x, cs, d, vec, idn, act, tpool, next_cs, (macs, in_b, out_b, w_b))
+    out_t, mask_t, code_t, nxt = _bn_add_forward(rt, x, cs, d, vec, idn, act, tpool, next_cs, work)
     out = Lazy(out_t)
     if rt.capture is not None and "aux" in rt.capture:           # (otherwise only reachable through the backward functions of this call)
         rt.capture["aux"][id(out)] = (code_t if tpool else None, mask_t, vec)
@@ -1106,7 +1135,7 @@ def conv_bn_add(rt, x, cs, bn, idn, act, idn_sole=False, tpool=0, next_cs=None):
             rt.pre_pending += 1
     if rt.tape.need_grad:
         z = _bn_add_raw_output(rt, x, cs, d, vec)
-        c = _ConvCall(rt, x, None, z, vec, bn, cs, d, count, act, True, False, False, macs, in_b, out_b, w_b, _ADD_LABELS, Gm, sv)
+        c = _ConvCall(rt, x, None, z, vec, bn, cs, d, count, act, True, False, False, work, _ADD_LABELS, Gm, sv)
         _bn_add_register_backward(c, out, out_t, mask_t, code_t, idn, idn_sole, tpool)
     return out
 
@@ -1138,13 +1167,10 @@ def maxpool3x3s2(rt, x, sole_consumer=False):
             out.grad = None
             if g is None or not x.requires_grad:
                 return
-            if sole_consumer and x.grad is None and x.vec is not None and x.pre_sums is None:
-                x.pool_grad = (g, idx, zsel, oh, ow)
+            if sole_consumer and _sums_open(x):
+                x.pool_grad = _PoolGrad(g, idx, zsel, oh, ow)
                 return
-            acc = 1
-            if x.grad is None:
-                x.grad = torch.empty_like(x.data)
-                acc = 0
+            acc = _claim_grad(x)
             call("adamml_maxpool2d_bwd", ptr(g), ptr(idx), ptr(x.grad), n, h, w, C, oh, ow, acc)
         rt.tape.record(bwd)
     return out
@@ -1173,15 +1199,12 @@ def temporal_pool(rt, x, frames, mode, sole_consumer=False):
             gx = torch.empty_like(x.data)
             if sole_consumer and x.grad is None and x.scale is None and x.res is not None and not x.res_done and \
                     hip.load().adamml_temporal_pool_bwd_res_supported(frames, C, m):
-                z, idn, ract, idn_sole, _ = x.res
-                fb = idn is not None and idn_sole and idn.requires_grad and idn.vec is not None and idn.grad is None
-                if z.requires_grad and z.vec is not None and z.grad is None and z.pre_sums is None and not fb:
-                    sa = rt.bwd_arena.take(G * 2 * C * STAT_SLOTS)
-                    call("adamml_temporal_pool_bwd_res", ptr(g), ptr(x.data), ract, ptr(gx), None if z.alg else ptr(z.data), ptr(z.vec), ptr(sa),
+                z = x.res.z
+                if _sums_open(z) and not _idn_sums_open(x.res):
+                    sa = _take_sums(rt, C)
+                    call("adamml_temporal_pool_bwd_res", ptr(g), ptr(x.data), x.res.act, ptr(gx), None if z.alg else ptr(z.data), ptr(z.vec), ptr(sa),
                          nb // G, frames, h * w, C, G)
-                    z.pre_sums = sa
-                    z.sums_partial = z.alg
-                    x.res_done = True
+                    _residual_finished(x, sa)
                     x.grad = gx
                     return
             call("adamml_temporal_pool_bwd", ptr(g), ptr(x.data), ptr(x.scale), ptr(x.shift), x.gs, x.act, ptr(gx), nb // G, frames,
