@@ -741,6 +741,152 @@ __global__ __launch_bounds__(NT) void gemm_f32_mfma_kernel(GemmP p) {
     }
 }
 
+// The gradient layouts of the same product: an operand whose reduction index is NOT its contiguous one (the weight gradient dW = g^T x
+// reads both operands down their columns, the data gradient dx = g W the weight).  The fragment-shaped loads of the kernel above would
+// gather 4-byte elements a row apart, so the tile goes through LDS: loaded along the contiguous dimension, read back as MFMA fragments.
+// Same numerics as gemm_f32_mfma_kernel: v_mfma_f32_16x16x4_f32 on the fp32 operands as they are, fp32 accumulators.
+//
+// Work split: a workgroup (4 waves, 2 x 2) owns 64 x 64 outputs, a wave 32 x 32 = 2 x 2 accumulator fragments; K advances in steps of
+// GT_K = 32 = 2 groups of 4 MFMA k-steps.  Per step and operand the tile is 64 x 32 floats = 512 16-byte quads, two per thread.
+//
+// LDS image of a TRANSPOSED operand (AT / BT: contiguous along m): k-major, [32 k][GT_PITCH = 68] floats.
+//   write: a thread stores the quad (k, m = 4 q .. 4 q + 3) it loaded (ds_write_b128); 16 consecutive lanes hold one k row = 64
+//          consecutive floats = the 64 banks once each, whatever the pitch.
+//   read:  MFMA step s of group g wants A[m = li][k = 16 g + 4 lg + s] from lane (li, lg): one ds_read_b32 at float
+//          (16 g + 4 lg + s) * 68 + m_wave + li.  68 = 64 + 4, so the row term is 4 (4 lg + s) = 16 lg + 4 s modulo 64: the four lane groups
+//          start 16 banks apart, li adds 0..15 -- 64 lanes, 64 banks, no conflict (pitch 64 would put all four groups on the same 16).
+//          The column read IS the transpose: the lane's four reads s = 0..3 are its K-contiguous fragment.
+// LDS image of a K-CONTIGUOUS operand (dx: g itself): m-major, [64 m][8 quads], no padding, quad q of row m kept at slot (q + (m >> 1)) & 7.
+//   write: 8 lanes hold one row (128 bytes); the 16 lanes of one ds_write_b128 pass hold rows m, m + 1 (m even): 32-quad rows alternate
+//          between the two halves of the 16 quad-banks and the rotation permutes within a half: 16 quads, 16 quad-banks.
+//   read:  lane (li, lg) reads quad 4 g + lg of row m_wave + li (ds_read_b128), element s feeds step s -- the same k = 16 g + 4 lg + s as
+//          above.  The 16 lanes of a pass (li = 0..15, one lg): row parity picks the half, (li >> 1) = 0..7 rotates the slot: 16 quad-banks.
+// Double buffer: two images per operand (2 x 2 x 8.5 KB = 34 KB).  The global loads of step t + 1 are issued before the 32 MFMAs of
+// step t and stored to the other image after them; one barrier per step (the image written in step t was last read in step t - 1,
+// whose barrier every wave has passed).
+// Alignment: the dispatch rule (adamml_gemm_f32_transposed_supported) admits operands with a 16-byte aligned base and a leading stride
+// that is a multiple of 4 only, so every quad is one 16-byte load.  Edges: a quad that is not wholly inside M / N / K is loaded element
+// by element under a predicate, missing elements are 0; the store is predicated per element.
+constexpr int GT_K = 32;
+constexpr int GT_PITCH = 64 + 4;
+constexpr int GT_IMG = GT_K * GT_PITCH;           // floats per image (>= 64 * GT_K, the m-major form)
+
+// four consecutive floats at p, the first n of them in range
+__device__ __forceinline__ f32x4 gt_load4(const float* p, int n) {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (n >= 4) return *reinterpret_cast<const f32x4*>(p);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (i < n) v[i] = p[i];
+    return v;
+}
+
+// the two quads of this thread in the 64 x 32 tile of one operand at (r0, k0); T: contiguous along the row index r (stride sk along k)
+template <bool T>
+__device__ __forceinline__ void gt_fetch(f32x4 (&v)[2], const float* base, int64_t sr, int64_t sk, int r0, int k0, int R, int K) {
+#pragma unroll
+    for (int l = 0; l < 2; ++l) {
+        const int e = threadIdx.x + l * NT;
+        if (T) {
+            const int r = r0 + 4 * (e & 15), k = k0 + (e >> 4);
+            v[l] = gt_load4(base + (int64_t)k * sk + r, k < K ? R - r : 0);
+        } else {
+            const int r = r0 + (e >> 3), k = k0 + 4 * (e & 7);
+            v[l] = gt_load4(base + (int64_t)r * sr + k, r < R ? K - k : 0);
+        }
+    }
+}
+
+template <bool T>
+__device__ __forceinline__ void gt_stage(float* img, const f32x4 (&v)[2]) {
+#pragma unroll
+    for (int l = 0; l < 2; ++l) {
+        const int e = threadIdx.x + l * NT;
+        if (T) *reinterpret_cast<f32x4*>(img + (e >> 4) * GT_PITCH + 4 * (e & 15)) = v[l];
+        else { const int r = e >> 3; *reinterpret_cast<f32x4*>(img + 4 * (r * 8 + (((e & 7) + (r >> 1)) & 7))) = v[l]; }
+    }
+}
+
+// fragment of rows r .. r + 15 (this lane: r + li), k = 16 g + 4 lg + s in element s
+template <bool T>
+__device__ __forceinline__ f32x4 gt_frag(const float* img, int r, int g, int lg) {
+    if (T) {
+        const float* q = img + (16 * g + 4 * lg) * GT_PITCH + r;
+        return f32x4{q[0], q[GT_PITCH], q[2 * GT_PITCH], q[3 * GT_PITCH]};
+    }
+    return *reinterpret_cast<const f32x4*>(img + 4 * (r * 8 + ((4 * g + lg + (r >> 1)) & 7)));
+}
+
+template <bool AT, bool BT>
+__global__ __launch_bounds__(NT) void gemm_f32_tr_kernel(GemmP p) {
+    __shared__ __attribute__((aligned(16))) float lds[2][2][GT_IMG];       // [buffer][operand]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int li = lane & 15, lg = lane >> 4;
+    const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
+    const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
+    f32x4 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int nstep = (p.K + GT_K - 1) / GT_K;
+    f32x4 av[2], bv[2];
+    if (nstep > 0) {
+        gt_fetch<AT>(av, p.a, p.a_sm, p.a_sk, m0, 0, p.M, p.K);
+        gt_fetch<BT>(bv, p.b, p.b_sn, p.b_sk, n0, 0, p.N, p.K);
+        gt_stage<AT>(lds[0][0], av);
+        gt_stage<BT>(lds[0][1], bv);
+        __syncthreads();
+    }
+    for (int t = 0; t < nstep; ++t) {
+        const bool more = t + 1 < nstep;                                   // (workgroup-uniform)
+        if (more) {
+            gt_fetch<AT>(av, p.a, p.a_sm, p.a_sk, m0, (t + 1) * GT_K, p.M, p.K);
+            gt_fetch<BT>(bv, p.b, p.b_sn, p.b_sk, n0, (t + 1) * GT_K, p.N, p.K);
+        }
+        const float* ia = lds[t & 1][0];
+        const float* ib = lds[t & 1][1];
+#pragma unroll
+        for (int g = 0; g < GT_K / 16; ++g) {
+            f32x4 fa[2], fb[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                fa[i] = gt_frag<AT>(ia, wm + 16 * i + li, g, lg);
+                fb[i] = gt_frag<BT>(ib, wn + 16 * i + li, g, lg);
+            }
+#pragma unroll
+            for (int s_ = 0; s_ < 4; ++s_)
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i][s_], fb[j][s_], acc[i][j], 0, 0, 0);
+        }
+        if (more) {
+            gt_stage<AT>(lds[(t + 1) & 1][0], av);
+            gt_stage<BT>(lds[(t + 1) & 1][1], bv);
+        }
+        __syncthreads();
+    }
+    // D fragment: lane (li, lg) holds rows 4 lg .. 4 lg + 3 of column li
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int nn = n0 + wn + 16 * j + li;
+        if (nn >= p.N) continue;
+        const float bias = p.bias ? p.bias[nn] : 0.f;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int mm = m0 + wm + 16 * i + 4 * lg + r;
+                if (mm >= p.M) continue;
+                float v = apply_act(acc[i][j][r] + bias, p.act);
+                float* dst = p.c + (int64_t)mm * p.c_sm + (int64_t)nn * p.c_sn;
+                if (p.accumulate) v += *dst;
+                *dst = v;
+            }
+    }
+}
+
 static int dw_blocks(size_t P, int C, size_t* ppb_out) {
     const int rows = rows_per_pass(C);
     size_t ppb = (size_t)rows * 8;
@@ -1011,6 +1157,22 @@ extern "C" int adamml_gemm_f32_uses_mfma(const float* a, int64_t a_sm, int64_t a
            ((uintptr_t)b & 15) == 0 ? 1 : 0;
 }
 
+// An operand is K-contiguous (k stride 1) or transposed (row stride 1), at least one of the two transposed, and -- as the K-contiguous
+// kernel asks (adamml_gemm_f32_uses_mfma) -- 16-byte aligned with a leading stride that is a multiple of 4: the kernel's loads are
+// 16-byte quads.  The policy stage's operands (widths 256, 1024, 2048, 2052, 2560) all are; the classifier heads' dW = g^T feat over
+// 31 classes (a k stride 31) is not and keeps the VALU kernel and its summation order.  M, N, K >= 8: the 2-row products of the policy
+// head's FC gradients (dW[2, H] = dlogits^T h, policy_net.py) would fill 1/32 of a 64 x 64 tile and stay on the VALU kernel too.
+static bool gt_operand_ok(const float* p, int64_t s_row, int64_t s_k) {
+    const int64_t lead = s_k == 1 ? s_row : s_k;
+    return (s_k == 1 || s_row == 1) && (lead & 3) == 0 && ((uintptr_t)p & 15) == 0;
+}
+
+extern "C" int adamml_gemm_f32_transposed_supported(const float* a, int64_t a_sm, int64_t a_sk, const float* b, int64_t b_sn, int64_t b_sk,
+                                                    int M, int N, int K) {
+    if (a_sk == 1 && b_sk == 1) return 0;
+    return gt_operand_ok(a, a_sm, a_sk) && gt_operand_ok(b, b_sn, b_sk) && M >= 8 && N >= 8 && K >= 8 ? 1 : 0;
+}
+
 extern "C" int adamml_gemm_f32(const float* a, int64_t a_sm, int64_t a_sk, const float* b, int64_t b_sn, int64_t b_sk, float* c,
                                int64_t c_sm, int64_t c_sn, const float* bias, int act, int accumulate, int M, int N, int K,
                                hipStream_t stream) {
@@ -1021,6 +1183,13 @@ extern "C" int adamml_gemm_f32(const float* a, int64_t a_sm, int64_t a_sk, const
         hipLaunchKernelGGL(gemm_f32_mfma_kernel, dim3(ceil_div(N, 64), ceil_div(M, 32)), dim3(NT), 0, stream, p);
         return adamml_check_launch("gemm_f32 (mfma)");
     }
-    hipLaunchKernelGGL(gemm_f32_kernel, dim3(ceil_div(N, 64), ceil_div(M, 64)), dim3(NT), 0, stream, p);
+    const dim3 grid(ceil_div(N, 64), ceil_div(M, 64));
+    if (adamml_gemm_f32_transposed_supported(a, a_sm, a_sk, b, b_sn, b_sk, M, N, K)) {
+        if (a_sk == 1) hipLaunchKernelGGL((gemm_f32_tr_kernel<false, true>), grid, dim3(NT), 0, stream, p);
+        else if (b_sk == 1) hipLaunchKernelGGL((gemm_f32_tr_kernel<true, false>), grid, dim3(NT), 0, stream, p);
+        else hipLaunchKernelGGL((gemm_f32_tr_kernel<true, true>), grid, dim3(NT), 0, stream, p);
+        return adamml_check_launch("gemm_f32 (transposed)");
+    }
+    hipLaunchKernelGGL(gemm_f32_kernel, grid, dim3(NT), 0, stream, p);
     return adamml_check_launch("gemm_f32");
 }

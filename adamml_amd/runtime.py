@@ -1274,6 +1274,10 @@ def head(rt, x, fc, frames, dropout_p, keep_mask=None):
     return logits, backward
 
 
+GEMM_TRANSPOSED = True       # test hook (tests/test_gemm_transposed_gpu.py): False hands gemm_f32's column-read operands over as K-contiguous copies,
+                             # so no call reaches gemm_f32_tr_kernel (csrc/dwconv_gemm32.hip); the product path never clears it
+
+
 def gemm_f32(a, b, out=None, bias=None, act=ACT_NONE, trans_a=False, trans_b=True, accumulate=False):
     """out[M,N] (+)= act(op(a) @ op(b)^T-ish + bias) on 2-D fp32 tensors via adamml_gemm_f32.
     trans_a=False: a is [M,K]; True: a is [K,M].  trans_b=True: b is [N,K]; False: b is [K,N]."""
@@ -1291,6 +1295,13 @@ def gemm_f32(a, b, out=None, bias=None, act=ACT_NONE, trans_a=False, trans_b=Tru
         b_sn, b_sk = b.stride(1), b.stride(0)
     if K != K2:
         raise RuntimeError("gemm_f32: inner dimensions differ (%d vs %d)" % (K, K2))
+    if not GEMM_TRANSPOSED:
+        if a_sk != 1:
+            a = (a.t() if trans_a else a).contiguous()
+            a_sm, a_sk = a.stride(0), 1
+        if b_sk != 1:
+            b = (b if trans_b else b.t()).contiguous()
+            b_sn, b_sk = b.stride(0), 1
     if out is None:
         out = torch.empty(M, N, dtype=torch.float32, device=a.device)
     call("adamml_gemm_f32", ptr(a), a_sm, a_sk, ptr(b), b_sn, b_sk, ptr(out), out.stride(0), out.stride(1), ptr(bias), act,

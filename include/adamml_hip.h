@@ -532,10 +532,21 @@ ADAMML_API int adamml_jpeg_decode_u8(const uint8_t* src, int64_t src_bytes, cons
                           int32_t* status, void* workspace, int64_t workspace_bytes, int N, hipStream_t stream);
 
 /* y[M,N] = act(x[M,K] @ w[N,K]^T + bias) in fp32 with arbitrary strides (nn.Linear / LSTMCell gates and their
- * gradients: policy_net.py:228-231,278-279,351-362; resnet.py:215; sound_mobilenet_v2.py:158) */
+ * gradients: policy_net.py:228-231,278-279,351-362; resnet.py:215; sound_mobilenet_v2.py:158).  c[m,n] (+)= act(sum_k a[m,k] b[n,k] +
+ * bias[n]) with a[m,k] at a + m a_sm + k a_sk, b[n,k] at b + n b_sn + k b_sk.  Three kernels, chosen from the arguments alone:
+ *   both operands K-contiguous (a_sk == b_sk == 1: the forward x W^T) and aligned   gemm_f32_mfma_kernel, matrix cores (adamml_gemm_f32_uses_mfma)
+ *   an operand read down its columns (a_sk != 1 with a_sm == 1, or b_sk != 1 with b_sn == 1: the data gradient g W and the weight
+ *   gradient g^T x), the other one the same or K-contiguous, both 16-byte aligned with a leading stride that is a multiple of 4,
+ *   M, N, K >= 8                                                                     gemm_f32_tr_kernel, matrix cores (adamml_gemm_f32_transposed_supported)
+ *   everything else (both strides of an operand != 1, unaligned operands such as the 31-class head gradient, the 2-row policy-head
+ *   gradients)                                                                       gemm_f32_kernel, VALU tiles
+ * All three multiply and accumulate in fp32. */
 /* 1 when adamml_gemm_f32 with these operands runs on the matrix cores (both operands K-contiguous and 16-byte aligned, row strides and
  * K multiples of 4, K >= 16), 0 when the VALU tile kernel serves it -- a label for profilers and tests. */
 ADAMML_API int adamml_gemm_f32_uses_mfma(const float* a, int64_t a_sm, int64_t a_sk, const float* b, int64_t b_sn, int64_t b_sk, int K);
+/* 1 when adamml_gemm_f32 with these operands runs on gemm_f32_tr_kernel (the rule above) -- a label for profilers and tests. */
+ADAMML_API int adamml_gemm_f32_transposed_supported(const float* a, int64_t a_sm, int64_t a_sk, const float* b, int64_t b_sn, int64_t b_sk, int M,
+                                         int N, int K);
 ADAMML_API int adamml_gemm_f32(const float* a, int64_t a_sm, int64_t a_sk, const float* b, int64_t b_sn, int64_t b_sk, float* c,
                     int64_t c_sm, int64_t c_sn, const float* bias, int act, int accumulate, int M, int N, int K,
                     hipStream_t stream);
