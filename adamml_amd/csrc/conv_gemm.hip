@@ -1180,6 +1180,9 @@ static int conv_launch(const adamml_conv_desc_t* d, const void* x, const void* w
     if (d->Cin % 8 || d->Cout % 8) return adamml_set_error(ADAMML_EINVAL, "conv_fwd: channels must be multiples of 8 (Cin=%d Cout=%d)", d->Cin, d->Cout);
     if (!cls && !fadd && !res && adamml_conv3x3_c64_supported(d))       // (the residual form of the 64-channel kernel: adamml_conv_bwd_data_res)
         return adamml_conv3x3_c64_launch(d, x, w_packed, in_scale, in_shift, y, stats, bn_z, bn_vec, bn_act, stream);
+    // 7x7 / 2 stem of a 16-channel image (flow / RGB-diff ResNets), plain input: LDS-patch kernel with resident weights (conv_stem16.hip)
+    if (!cls && !fadd && !res && !dual && !cat && !pf && !bn_z && !in_scale && !d->accumulate && adamml_conv_stem16_supported(d))
+        return adamml_conv_stem16_fwd_launch(d, x, w_packed, y, stats, stream);
     // narrow 1x1 convs of the MobileNetV2s (plain forward / plain data gradient): the barrier-free streaming kernel (conv1x1_narrow.hip)
     if (!cls && !fadd && !res && !dual && !cat && !pf && !bn_z && adamml_conv1x1_narrow_fwd_supported(d))
         return adamml_conv1x1_narrow_fwd_launch(d, x, w_packed, in_scale, in_shift, y, stats, stream);

@@ -33,6 +33,14 @@ int adamml_conv3x3_c64_wgrad_blocks(const adamml_conv_desc_t* d, int* tpb_out);
 int adamml_conv3x3_c64_wgrad_launch(const adamml_conv_desc_t* d, const void* dz, const void* x, const float* in_scale,
                                     const float* in_shift, float* ws, hipStream_t stream);
 
+// ---- conv_stem16.hip: 7x7 / 2 stem of a 16-channel image (flow / RGB-diff ResNets); the probe adamml_conv_stem16_supported is in the C ABI.
+// w_packed: the mode-0 pack [64][49][16]; plain input only
+int adamml_conv_stem16_fwd_launch(const adamml_conv_desc_t* d, const void* x, const void* w_packed, void* y, double* stats, hipStream_t stream);
+// bytes of one [64][784] fp32 partial per workgroup (0: not a stem16 shape); the launch writes them to ws and reduces them into dw (+=)
+size_t adamml_conv_stem16_wgrad_workspace(const adamml_conv_desc_t* d);
+int adamml_conv_stem16_wgrad_launch(const adamml_conv_desc_t* d, const void* dz, const void* x, float* dw, int cin_true, float* ws,
+                                    hipStream_t stream);
+
 // ---- conv1x1_narrow.hip: narrow 1x1 convs of the MobileNetV2s (barrier-free streaming kernels)
 bool adamml_conv1x1_narrow_fwd_supported(const adamml_conv_desc_t* d);
 int adamml_conv1x1_narrow_fwd_launch(const adamml_conv_desc_t* d, const void* x, const void* w_packed, const float* in_scale, const float* in_shift,

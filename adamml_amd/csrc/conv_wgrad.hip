@@ -718,6 +718,10 @@ extern "C" size_t adamml_conv_bwd_weight_workspace(const adamml_conv_desc_t* d, 
         const size_t n3 = (size_t)adamml_conv3x3_c64_wgrad_blocks(d, nullptr) * d->Cout * cin_true * 9 * sizeof(float);
         if (n3 > need) need = n3;
     }
+    if (cin_true >= 1 && cin_true <= 16) {
+        const size_t n16 = adamml_conv_stem16_wgrad_workspace(d);
+        if (n16 > need) need = n16;
+    }
     return need;
 }
 
@@ -774,6 +778,11 @@ static int wgrad_launch(const adamml_conv_desc_t* d, const void* dz, const void*
             if (rc) return rc;
             return adamml_launch_split_reduce((const float*)workspace, dw, dw_numel, nblk, stream, 9, cin_true);
         }
+    }
+    if (!ex && workspace && !in_scale && cin_true >= 1 && cin_true <= 16) {
+        // 7x7 / 2 stem of a 16-channel image, plain input: LDS-patch kernel with one partial per workgroup (conv_stem16.hip)
+        const size_t n16 = adamml_conv_stem16_wgrad_workspace(d);
+        if (n16 && workspace_bytes >= n16) return adamml_conv_stem16_wgrad_launch(d, dz, x, dw, cin_true, (float*)workspace, stream);
     }
     if (!ex && workspace && adamml_conv1x1_narrow_wgrad_supported(d, cin_true) && workspace_bytes >= (size_t)groups * pl.nsplit * dw_numel * sizeof(float)) {
         // narrow 1x1 convs of the MobileNetV2s: barrier-free streaming kernel, one partial per workgroup (conv1x1_narrow.hip)

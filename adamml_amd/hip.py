@@ -189,6 +189,8 @@ def load():
     lib.adamml_jpeg_decode_parallel_supported.restype = c_int
     lib.adamml_conv_stem_supported.argtypes = [_DESC]
     lib.adamml_conv_stem_supported.restype = c_int
+    lib.adamml_conv_stem16_supported.argtypes = [_DESC]
+    lib.adamml_conv_stem16_supported.restype = c_int
     lib.adamml_plan_run.argtypes = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int]
     lib.adamml_plan_run.restype = c_int
     lib.adamml_plan_events_create.argtypes = [c_void_p, c_int]

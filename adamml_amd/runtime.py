@@ -489,6 +489,9 @@ def conv_bn(rt, x, cs, bn, act, sole_consumer=False, last_consumer=False):
                  in_b=2.0 * G * d.N * d.H * d.W * cs.cin_true, out_b=2.0 * G * count * C,
                  w_b=2.0 * C * cs.kh * cs.kw * (1 if cs.depthwise else cs.cin_true))
     kern_f, role_f, lab = _conv_labels(cs, d)
+    # (the 16-channel stem of the flow / RGB-diff ResNets is dispatched inside adamml_conv_fwd, csrc/conv_stem16.hip: the probe only labels it)
+    if not stem and cs.kh == 7 and x.scale is None and hip.load().adamml_conv_stem16_supported(byref(d)):
+        kern_f, role_f = "conv_stem16_kernel", R_KXK
     hip.next_meta = (2 * work.macs, work.in_b + work.out_b + work.w_b, "conv_stem_kernel" if stem else kern_f, role_f)
     if pre is not None:
         hip.next_meta = (0.0, 0.0)
@@ -596,6 +599,8 @@ def _launch_wgrad(c, dz):
                  ws.numel() * 4)
         else:
             ws = hip.wgrad_workspace(d, cs.cin_true, dz.device)
+            if cs.kh == 7 and x.scale is None and hip.load().adamml_conv_stem16_supported(byref(d)):
+                hip.next_meta = hip.next_meta[:2] + ("conv_stem16_wgrad_kernel", R_WGRAD)          # (dispatched inside the entry point, as the forward)
             call("adamml_conv_bwd_weight", byref(d), ptr(dz), ptr(x.data), ptr(x.scale), ptr(x.shift),
                  ptr(cs.weight.grad), cs.cin_true, ptr(ws), ws.numel() * 4)
 

@@ -269,6 +269,13 @@ ADAMML_API int adamml_conv_stem_fwd(const adamml_conv_desc_t* d, const void* x, 
 ADAMML_API size_t adamml_conv_stem_bwd_weight_workspace(const adamml_conv_desc_t* d);
 ADAMML_API int adamml_conv_stem_bwd_weight(const adamml_conv_desc_t* d, const void* dz, const void* x, float* dw, int cin_true,
                                 void* workspace, size_t workspace_bytes, hipStream_t stream);
+/* 1 when adamml_conv_fwd (plain input: in_scale == NULL, no accumulate) and adamml_conv_bwd_weight (plain input, a workspace of
+ * adamml_conv_bwd_weight_workspace() bytes) serve the descriptor with the 16-channel stem kernels of csrc/conv_stem16.hip rather than the
+ * tile kernels: the 7x7 stride-2 pad-3 conv of the flow / RGB-diff ResNets (models/resnet.py:138; 10 and 15 channels stored as 16 per
+ * pixel) to 64 channels, even W <= 256, from an LDS-resident input patch and LDS-resident weights, K = 25 steps of two taps.  The weight
+ * operand is the mode-0 pack [64][49][16] both kernels families read, so the entry points and their arguments are the same; results
+ * agree within the rounding of another summation order -- a label for profilers, as adamml_conv1x1_narrow_supported. */
+ADAMML_API int adamml_conv_stem16_supported(const adamml_conv_desc_t* d);
 
 /* depthwise 3x3 conv (groups == channels; sound_mobilenet_v2.py:58, policy_net.py:66,80) */
 ADAMML_API int adamml_dwconv_fwd(const adamml_conv_desc_t* d, const void* x, const float* w_tapmajor, const float* in_scale,
