@@ -464,7 +464,7 @@ int adamml_conv1x1_fadd_next_launch(const adamml_conv_desc_t* d, const void* x, 
 // d: the forward descriptor of conv3 (1x1, 64 -> 256, N = clips * frames images per group)
 bool adamml_conv1x1_fadd_tpool_supported(const adamml_conv_desc_t* d, int frames) {
     return d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && d->up <= 1 && d->Cin == C3IN && d->Cout == CB &&
-           (frames == 2 || frames == 4 || frames == 8) && d->N % frames == 0;
+           (frames == 2 || frames == 4 || frames == 8 || frames == 16 || frames == 32) && d->N % frames == 0;       // (the frame walk is a run-time loop)
 }
 
 int adamml_conv1x1_fadd_tpool_launch(const adamml_conv_desc_t* d, const void* x, const void* w_packed, const float* in_scale, const float* in_shift,

@@ -367,7 +367,8 @@ int adamml_conv1x1_fadd_tpool_stream_supported(const adamml_conv_desc_t* d, int 
     const int mode = e ? atoi(e) : 1;                                                                              // 0: off, 1: layer 2, 2: layers 1 and 2
     if (!mode || !d) return 0;
     const bool l2 = d->Cin == 128 && d->Cout == 512, l1 = mode >= 2 && d->Cin == 64 && d->Cout == 256;
-    return d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && d->up <= 1 && (l1 || l2) && (frames == 2 || frames == 4 || frames == 8) &&
+    return d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && d->up <= 1 && (l1 || l2) &&
+           (frames == 2 || frames == 4 || frames == 8 || frames == 16 || frames == 32) &&       // (the window walk is a run-time loop)
            d->N % frames == 0 && (long)d->N * d->OH * d->OW >= 4096 ? 1 : 0;
 }
 

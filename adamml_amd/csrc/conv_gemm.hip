@@ -89,7 +89,10 @@ struct ConvP {
     // r % (BP / TP) of block tp_blk), the epilogue pools over the frames and writes the POOLED tensor tp_y [clips * TP / 2][Q][Cout] and
     // 2 bits per pooled element (tp_code, one uint16 per 8-channel chunk: window tap 0..2 of the first maximum, 3 = maximum <= 0, i.e.
     // no gradient passes the ReLU) -- the full-rate block output, its activation mask and the pool's own pass never touch HBM
-    int tp_nblk, tp_Q;           // pixel blocks per clip (ceil(Q / (BP / TP))), pixels per frame
+    // TP = 16 / 32: the clip is walked in segments of 8 frames.  The TP / 8 tiles of a (clip, pixel block) are consecutive tiles of ONE workgroup
+    // (tpb % (TP / 8) == 0), every tile has the TP = 8 row layout, and an epilogue thread -- it owns the same (pixel, 8-channel chunk) in
+    // every tile -- carries the last (odd) frame of a segment in registers: tap 0 of the next segment's first window.  Registers and LDS as TP = 8.
+    int tp_nblk, tp_Q;           // pixel blocks per clip (ceil(Q / (BP / min(TP, 8)))), pixels per frame
     bf16_t* tp_y;
     uint16_t* tp_code;
 };
@@ -150,8 +153,10 @@ constexpr int conv_gemm_wg_per_cu(int BC, int MODE, int PD, bool RES, bool DUAL,
 template <int BC, int MODE, int PD, bool RES = false, bool DUAL = false, bool CAT = false, bool FADD = false, bool GLDS = false, int EID = 0,
           bool LZF = false, int EPI = -1, bool PF = false, int TP = 0>
 __global__ __launch_bounds__(NTHREADS, conv_gemm_wg_per_cu(BC, MODE, PD, RES, DUAL, CAT, FADD, GLDS, EID, EPI)) void conv_gemm_kernel(ConvP p) {
-    static_assert(TP == 0 || (FADD && EID && MODE == 0 && BC == 128 && (TP == 2 || TP == 4 || TP == 8)), "TP: FADD + EID, 128-wide cout tiles");
-    constexpr int PPF = TP ? BP / TP : BP;  // TP: pixels of one frame in a tile
+    static_assert(TP == 0 || (FADD && EID && MODE == 0 && BC == 128 && (TP == 2 || TP == 4 || TP == 8 || TP == 16 || TP == 32)), "TP: FADD + EID, 128-wide cout tiles");
+    constexpr int TPF = TP > 8 ? 8 : TP;    // TP: frames of a clip in one tile (TP > 8: one segment of the clip), segments per clip
+    constexpr int NSEG = TP > 8 ? TP / 8 : 1;
+    constexpr int PPF = TP ? BP / TPF : BP; // TP: pixels of one frame in a tile
     constexpr int WCT = BC / 32;            // 16-wide cout tiles per wave
     constexpr int WROWS = BC / 64;          // weight rows staged per thread
     constexpr int TILE_BYTES = (BP + BC) * 64;
@@ -311,18 +316,22 @@ __global__ __launch_bounds__(NTHREADS, conv_gemm_wg_per_cu(BC, MODE, PD, RES, DU
             pfh[t] = p.pf_scale ? p.pf_shift[ch] : 0.f;
         }
     }
+    bf16x8 tp_carry;             // NSEG > 1: this thread's last frame of the previous segment (post-ReLU, as stored by the unfused path)
     // a workgroup walks `tpb` consecutive pixel tiles of its cout tile: statistics are published once per workgroup
     for (int it = 0; it < p.tpb; ++it) {
     const int ptile = pgrp * p.tpb + it;
     if (ptile >= p.n_ptiles) break;
     const int p0 = ptile * BP;
-    // TP: tile = (clip, pixel block); tile row r -> pixel (clip * TP + r / PPF) * Q + blk * PPF + r % PPF, valid while the pixel exists
-    const int tp_clip = TP ? ptile / p.tp_nblk : 0;
-    const int tp_q0 = TP ? (ptile - tp_clip * p.tp_nblk) * PPF : 0;
+    // TP: tile = (clip, pixel block[, segment]); tile row r -> pixel (clip * TP + seg * TPF + r / PPF) * Q + blk * PPF + r % PPF, valid while
+    // the pixel exists
+    const int tp_chain = NSEG > 1 ? ptile / NSEG : ptile;
+    const int tp_seg = NSEG > 1 ? ptile - tp_chain * NSEG : 0;
+    const int tp_clip = TP ? tp_chain / p.tp_nblk : 0;
+    const int tp_q0 = TP ? (tp_chain - tp_clip * p.tp_nblk) * PPF : 0;
     auto tp_row = [&](int r, bool& ok) -> int {
         const int q = tp_q0 + (r % PPF);
         ok = q < p.tp_Q;
-        return (tp_clip * TP + r / PPF) * p.tp_Q + (ok ? q : 0);
+        return (tp_clip * TP + tp_seg * TPF + r / PPF) * p.tp_Q + (ok ? q : 0);
     };
 
     // ---- per-thread staging coordinates -------------------------------------------------------
@@ -725,7 +734,14 @@ __global__ __launch_bounds__(NTHREADS, conv_gemm_wg_per_cu(BC, MODE, PD, RES, DU
             if constexpr (TP != 0) {
                 // this thread's NR = 8 rows are rows erow0 + 16 j: NPX = PPF / 16 pixels x TP frames (frame t of pixel s at j = t * NPX + s)
                 static_assert(RSTEP == 16 && NR == 8, "TP epilogue mapping");
-                constexpr int NPX = PPF / 16, To = TP / 2;
+                constexpr int NPX = PPF / 16, To = TPF / 2;
+                static_assert(NSEG == 1 || NPX == 1, "TP carry: one pixel per epilogue thread");
+                if constexpr (NSEG > 1) {
+                    if (tp_seg == 0) {                                      // window 0 of the clip has no tap 0: every ReLU output beats -inf
+                        const __bf16 ninf = (__bf16)(-INFINITY);
+                        tp_carry = bf16x8{ninf, ninf, ninf, ninf, ninf, ninf, ninf, ninf};
+                    }
+                }
                 bf16x8 vb[NR];
 #pragma unroll
                 for (int j = 0; j < NR; ++j) {
@@ -749,8 +765,8 @@ __global__ __launch_bounds__(NTHREADS, conv_gemm_wg_per_cu(BC, MODE, PD, RES, DU
 #pragma unroll
                         for (int k = 0; k < 3; ++k) {
                             const int tt = 2 * to - 1 + k;
-                            if (tt < 0 || tt >= TP) continue;
-                            const f32x8 v = bf8_to_f32(vb[tt * NPX + s]);
+                            if ((NSEG == 1 && tt < 0) || tt >= TPF) continue;
+                            const f32x8 v = bf8_to_f32(tt < 0 ? tp_carry : vb[(tt < 0 ? 0 : tt) * NPX + s]);
 #pragma unroll
                             for (int i = 0; i < 8; ++i)
                                 if (v[i] > best[i] || __builtin_isnan(v[i])) { best[i] = v[i]; code = (code & ~(3u << (2 * i))) | ((unsigned)k << (2 * i)); }   // first maximum in scan order
@@ -758,11 +774,12 @@ __global__ __launch_bounds__(NTHREADS, conv_gemm_wg_per_cu(BC, MODE, PD, RES, DU
 #pragma unroll
                         for (int i = 0; i < 8; ++i)
                             if (!(best[i] > rlo && best[i] < rhi)) code |= 3u << (2 * i);       // act'(maximum) == 0: no gradient through this window
-                        const size_t po = ((size_t)(tp_clip * To + to) * p.tp_Q + q) * p.Cout + eco;
+                        const size_t po = ((size_t)(tp_clip * (TP / 2) + tp_seg * To + to) * p.tp_Q + q) * p.Cout + eco;
                         *reinterpret_cast<bf16x8*>(p.tp_y + po) = f32_to_bf8(best);
                         if (p.tp_code) p.tp_code[po >> 3] = (uint16_t)code;
                     }
                 }
+                if constexpr (NSEG > 1) tp_carry = vb[(TPF - 1) * NPX];     // tap 0 of the next segment's first window
             } else
 #pragma unroll
             for (int b0 = 0; b0 < NR; b0 += EB) {
@@ -1151,7 +1168,9 @@ static void launch_dual(const ConvGrid& g, const ConvP& p) {
 template <int V> using int_c = std::integral_constant<int, V>;
 template <class F> static void with_bc(int BC, F f) { if (BC == 64) f(int_c<64>{}); else f(int_c<128>{}); }
 template <class F> static void with_epi(int epi, F f) { if (epi == 0) f(int_c<0>{}); else if (epi == 1) f(int_c<1>{}); else f(int_c<2>{}); }
-template <class F> static void with_tp(int tp, F f) { if (tp == 8) f(int_c<8>{}); else if (tp == 4) f(int_c<4>{}); else f(int_c<2>{}); }
+template <class F> static void with_tp(int tp, F f) {
+    if (tp == 32) f(int_c<32>{}); else if (tp == 16) f(int_c<16>{}); else if (tp == 8) f(int_c<8>{}); else if (tp == 4) f(int_c<4>{}); else f(int_c<2>{});
+}
 template <class F> static void with_flag(bool b, F f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
 
 // the plain instances of one (BC, MODE): LDS-DMA staging or the register-staged loader with the epilogue compiled in, deep prefetch (MODE
@@ -1248,10 +1267,12 @@ static int conv_launch(const adamml_conv_desc_t* d, const void* x, const void* w
     const int BC = narrow ? 64 : 128;
     p.n_ptiles = ceil_div(p.P, BP);
     if (tp) {
-        // tiles = (clip, block of BP / tp pixels); all frames of a clip's pixel block sit in one tile
+        // tiles = (clip, block of BP / tp pixels); all frames of a clip's pixel block sit in one tile -- or, beyond 8 frames, in the tp / 8
+        // consecutive tiles of its 8-frame segments (ConvP::tp_nblk)
+        const int tpf = tp > 8 ? 8 : tp;
         p.tp_Q = d->OH * d->OW;
-        p.tp_nblk = ceil_div(p.tp_Q, BP / tp);
-        p.n_ptiles = (d->N / tp) * p.tp_nblk;
+        p.tp_nblk = ceil_div(p.tp_Q, BP / tpf);
+        p.n_ptiles = (d->N / tp) * p.tp_nblk * (tp / tpf);
         p.tp_y = (bf16_t*)fadd->tp_y; p.tp_code = fadd->tp_code;
     }
     p.n_ctiles = ceil_div(d->Cout, BC);
@@ -1259,6 +1280,7 @@ static int conv_launch(const adamml_conv_desc_t* d, const void* x, const void* w
     p.tpb = (int)((long)p.n_ptiles * p.n_ctiles * groups / 2048);
     if (p.tpb < 1) p.tpb = 1;
     if (p.tpb > 8) p.tpb = 8;
+    if (tp > 8) p.tpb = p.tpb < tp / 8 ? tp / 8 : p.tpb / (tp / 8) * (tp / 8);      // whole segment chains per workgroup
     if (pf) {
         // one [BC][64] partial per workgroup: few, long-lived workgroups (~6 per CU slot pair over all groups and cout tiles)
         const long target = 1536;
@@ -1438,7 +1460,7 @@ extern "C" int adamml_conv_fwd_bn_add_next(const adamml_conv_desc_t* d, const vo
 
 extern "C" int adamml_conv_fwd_bn_add_tpool_supported(const adamml_conv_desc_t* d, int frames, int act, int lazy_input) {
     if (!adamml_conv_fwd_bn_add_supported(d)) return 0;
-    if (!(frames == 2 || frames == 4 || frames == 8) || d->N % frames || d->Cout % 128 || act != ADAMML_ACT_RELU) return 0;
+    if (!(frames == 2 || frames == 4 || frames == 8 || frames == 16 || frames == 32) || d->N % frames || d->Cout % 128 || act != ADAMML_ACT_RELU) return 0;
     if (lazy_input && d->Cin > 512) return 0;                         // (the fragment-side lazy transform keeps its vectors in LDS)
     return 1;
 }
@@ -1456,7 +1478,7 @@ extern "C" int adamml_conv_fwd_bn_add_tpool(const adamml_conv_desc_t* d, const v
                                             const float* id_shift, int id_gstride, int act, int frames, void* pooled, uint16_t* code,
                                             hipStream_t stream) {
     if (!adamml_conv_fwd_bn_add_tpool_supported(d, frames, act, in_scale != nullptr))
-        return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_fwd_bn_add_tpool: 1x1 / stride-1 conv, Cout %% 128 == 0, ReLU, 2 / 4 / 8 frames per clip");
+        return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_fwd_bn_add_tpool: 1x1 / stride-1 conv, Cout %% 128 == 0, ReLU, 2 / 4 / 8 / 16 / 32 frames per clip");
     if (!bn_vec || !idn || !pooled) return adamml_set_error(ADAMML_EINVAL, "conv_fwd_bn_add_tpool: null argument");
     if (adamml_conv1x1_fadd_tpool_stream_supported(d, frames))        // (csrc/conv1x1_fadd_stream.hip: the wave-slice streaming structure)
         return adamml_conv1x1_fadd_tpool_stream_launch(d, x, w_packed, in_scale, in_shift, bn_vec, idn, id_scale, id_shift, id_gstride, act, frames, pooled,

@@ -675,6 +675,268 @@ __global__ __launch_bounds__(NT) void temporal_pool_code_bwd_kernel(const bf16_t
     block_channel_publish(sa, qa, m, smem, C, sumsa);
 }
 
+// ---- rolling forms for long clips (T = 16, 32: an even run-time T).  The kernels above keep all T frames of a column in registers; these
+// walk the windows of a column upwards and carry only what two windows share -- the odd frame 2 to - 1 is tap 2 of window to - 1 and tap 0
+// of window `to` -- so registers do not grow with T.  The rows of window to + 1 are requested (clamped, unconditionally) before window `to` is
+// reduced.  Frames leave in the order 0, 1, .. T - 1 and every expression is the one of the kernels above: same values, same float partial sums.
+
+// temporal_pool_fwd_walk_kernel: carry = the transformed frame 2 to - 1 (max: -inf before window 0, avg: 0)
+__global__ __launch_bounds__(NT) void temporal_pool_fwd_roll_kernel(const bf16_t* x, const float* scale, const float* shift, int gs, int act, bf16_t* y,
+                                                                   int NB, int T, size_t hwc8, int C, int mode) {
+    const int To = T >> 1;
+    x += (size_t)blockIdx.y * NB * T * hwc8 * 8;
+    y += (size_t)blockIdx.y * NB * To * hwc8 * 8;
+    if (scale) { scale += (size_t)blockIdx.y * gs; shift += (size_t)blockIdx.y * gs; }
+    const size_t total = (size_t)NB * hwc8;
+    const int cpr = C >> 3;
+    const float lo = scale ? act_lo(act) : -INFINITY, hi = scale ? act_hi(act) : INFINITY;
+    for (size_t e = (size_t)blockIdx.x * NT + threadIdx.x; e < total; e += (size_t)gridDim.x * NT) {
+        const size_t in = e % hwc8, nb = e / hwc8;
+        const int c = (int)(in % cpr) * 8;
+        f32x8 sc, sh;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { sc[i] = 1.f; sh[i] = 0.f; }
+        if (scale) { sc = load_f32x8(scale + c); sh = load_f32x8(shift + c); }
+        const bf16_t* xp = x + (nb * T * hwc8 + in) * 8;
+        bf16_t* yp = y + (nb * To * hwc8 + in) * 8;
+        bf16x8 nx[2];
+#pragma unroll
+        for (int f = 0; f < 2; ++f) nx[f] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(xp + (size_t)f * hwc8 * 8));
+        f32x8 carry;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) carry[i] = mode == 0 ? -INFINITY : 0.f;
+#pragma unroll 1
+        for (int to = 0; to < To; ++to) {
+            const bf16x8 r0 = nx[0], r1 = nx[1];
+            const int wn = to + 1 < To ? to + 1 : to;
+#pragma unroll
+            for (int f = 0; f < 2; ++f) nx[f] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(xp + (size_t)(2 * wn + f) * hwc8 * 8));
+            f32x8 v0 = bf8_to_f32(r0), v1 = bf8_to_f32(r1), acc;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                v0[i] = clamp_act(fmaf(v0[i], sc[i], sh[i]), lo, hi);
+                v1[i] = clamp_act(fmaf(v1[i], sc[i], sh[i]), lo, hi);
+                acc[i] = mode == 0 ? __builtin_elementwise_maximum(__builtin_elementwise_maximum(carry[i], v0[i]), v1[i]) : (carry[i] + v0[i]) + v1[i];
+            }
+            if (mode == 1) acc *= (1.f / 3.f);
+            __builtin_nontemporal_store(f32_to_bf8(acc), reinterpret_cast<bf16x8*>(yp + (size_t)to * hwc8 * 8));
+            carry = v1;
+        }
+    }
+}
+
+// temporal_pool_bwd_kernel as a column walk: every x row and every gy row is read once (the per-element form reads 1.5 / 3 of them per output)
+__global__ __launch_bounds__(NT) void temporal_pool_bwd_roll_kernel(const bf16_t* gy, const bf16_t* x, const float* scale, const float* shift, int gs,
+                                                                   int act, bf16_t* gx, int NB, int T, size_t hwc8, int C, int mode) {
+    const int To = T >> 1;
+    gy += (size_t)blockIdx.y * NB * To * hwc8 * 8;
+    x += (size_t)blockIdx.y * NB * T * hwc8 * 8;
+    gx += (size_t)blockIdx.y * NB * T * hwc8 * 8;
+    if (scale) { scale += (size_t)blockIdx.y * gs; shift += (size_t)blockIdx.y * gs; }
+    const size_t total = (size_t)NB * hwc8;
+    const int cpr = C >> 3;
+    for (size_t e = (size_t)blockIdx.x * NT + threadIdx.x; e < total; e += (size_t)gridDim.x * NT) {
+        const size_t in = e % hwc8, nb = e / hwc8;
+        const int c = (int)(in % cpr) * 8;
+        const bf16_t* xp = x + (nb * T * hwc8 + in) * 8;
+        const bf16_t* gp = gy + (nb * To * hwc8 + in) * 8;
+        bf16_t* op = gx + (nb * T * hwc8 + in) * 8;
+        bf16x8 nx[2], ng;
+#pragma unroll
+        for (int f = 0; f < 2; ++f) nx[f] = *reinterpret_cast<const bf16x8*>(xp + (size_t)f * hwc8 * 8);
+        ng = *reinterpret_cast<const bf16x8*>(gp);
+        f32x8 cv, pend;                                          // frame 2 to - 1: its transformed value and what window to - 1 sent it
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { cv[i] = -INFINITY; pend[i] = 0.f; }
+#pragma unroll 1
+        for (int to = 0; to < To; ++to) {
+            const bf16x8 r0 = nx[0], r1 = nx[1];
+            const f32x8 g = bf8_to_f32(ng);
+            const int wn = to + 1 < To ? to + 1 : to;
+#pragma unroll
+            for (int f = 0; f < 2; ++f) nx[f] = *reinterpret_cast<const bf16x8*>(xp + (size_t)(2 * wn + f) * hwc8 * 8);
+            ng = *reinterpret_cast<const bf16x8*>(gp + (size_t)wn * hwc8 * 8);
+            f32x8 a0, a1, a2;                                    // this window's share of frames 2 to - 1, 2 to, 2 to + 1
+            if (mode == 1) {
+                a0 = a1 = a2 = g * (1.f / 3.f);
+            } else {
+                const f32x8 v1 = transform8(r0, scale, shift, c, act), v2 = transform8(r1, scale, shift, c, act);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {                    // first maximum in scan order, strict > (cv = -inf before window 0: never taken)
+                    float best = -INFINITY;
+                    int k = -1;
+                    if (cv[i] > best) { best = cv[i]; k = 0; }
+                    if (v1[i] > best) { best = v1[i]; k = 1; }
+                    if (v2[i] > best) { best = v2[i]; k = 2; }
+                    a0[i] = k == 0 ? g[i] : 0.f; a1[i] = k == 1 ? g[i] : 0.f; a2[i] = k == 2 ? g[i] : 0.f;
+                }
+                cv = v2;
+            }
+            if (to > 0) *reinterpret_cast<bf16x8*>(op + (size_t)(2 * to - 1) * hwc8 * 8) = f32_to_bf8(pend + a0);
+            *reinterpret_cast<bf16x8*>(op + (size_t)(2 * to) * hwc8 * 8) = f32_to_bf8(a1);
+            pend = a2;
+        }
+        *reinterpret_cast<bf16x8*>(op + (size_t)(T - 1) * hwc8 * 8) = f32_to_bf8(pend);
+    }
+}
+
+// temporal_pool_residual_bwd_kernel: carry = block output and z of frame 2 to - 1 and the gradient window to - 1 routed to it
+__global__ __launch_bounds__(NT) void temporal_pool_residual_bwd_roll_kernel(const bf16_t* gy, const bf16_t* out, int act, bf16_t* g2, const bf16_t* za,
+                                                                            const float* veca, double* sumsa, size_t NBHW, int HW, int C, size_t cpb,
+                                                                            int T) {
+    const int To = T >> 1;
+    __shared__ float smem[2 * MAXC];
+    const int NB = (int)(NBHW / HW);
+    {
+        const size_t goff = (size_t)blockIdx.y * NB * T * HW * C;
+        gy += (size_t)blockIdx.y * NB * To * HW * C;
+        out += goff; g2 += goff;
+        if (za) { za += goff; veca += (size_t)blockIdx.y * 4 * C; }
+        sumsa += (size_t)blockIdx.y * ADAMML_STAT_SLOTS * 2 * C;
+    }
+    ChanMap m(C, threadIdx.x);
+    float sa[8], qa[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) sa[i] = qa[i] = 0.f;
+    const size_t cb = (size_t)blockIdx.x * cpb;
+    const size_t ce = cb + cpb < NBHW ? cb + cpb : NBHW;
+    if (m.active) {
+        const int c = m.chunk * 8;
+        f32x8 mua, isa;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { mua[i] = 0.f; isa[i] = 0.f; }
+        if (za) { mua = load_f32x8(veca + 2 * C + c); isa = load_f32x8(veca + 3 * C + c); }
+        const float lo = act_lo(act), hi = act_hi(act);
+        const size_t fstride = (size_t)HW * C;
+        const bf16x8 zero8 = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+        for (size_t col = cb + m.rslot; col < ce; col += m.rows_per_pass) {
+            const size_t nb = col / HW, hw = col - nb * HW;
+            const size_t base = (nb * T * HW + hw) * C + c, gbase = (nb * To * HW + hw) * C + c;
+            // one frame leaves: round the routed gradient (as the unfused path stores it), mask, store, sums
+            auto emit = [&](int t, f32x8 acc, const bf16x8& ob, const bf16x8& zb) {
+                const f32x8 o = bf8_to_f32(ob);
+                acc = bf8_to_f32(f32_to_bf8(acc));
+#pragma unroll
+                for (int i = 0; i < 8; ++i) acc[i] *= mask_act(o[i], lo, hi);
+                const bf16x8 gb = f32_to_bf8(acc);
+                __builtin_nontemporal_store(gb, reinterpret_cast<bf16x8*>(g2 + base + t * fstride));
+                const f32x8 gq = bf8_to_f32(gb), z = bf8_to_f32(zb);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) { sa[i] += gq[i]; qa[i] += gq[i] * (z[i] - mua[i]) * isa[i]; }
+            };
+            bf16x8 no[2], nz[2], ng;
+            auto request = [&](int w) {
+#pragma unroll
+                for (int f = 0; f < 2; ++f) {
+                    no[f] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(out + base + (2 * w + f) * fstride));
+                    nz[f] = za ? __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(za + base + (2 * w + f) * fstride)) : zero8;
+                }
+                ng = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(gy + gbase + w * fstride));
+            };
+            request(0);
+            bf16x8 co = zero8, cz = zero8;                       // frame 2 to - 1
+            f32x8 cv, pend;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) { cv[i] = -INFINITY; pend[i] = 0.f; }
+#pragma unroll 1
+            for (int to = 0; to < To; ++to) {
+                const bf16x8 o0 = no[0], o1 = no[1], z0 = nz[0], z1 = nz[1];
+                const f32x8 g = bf8_to_f32(ng);
+                request(to + 1 < To ? to + 1 : to);
+                const f32x8 v1 = bf8_to_f32(o0), v2 = bf8_to_f32(o1);
+                f32x8 a0, a1, a2;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {                    // first maximum in scan order, strict > (cv = -inf before window 0: never taken)
+                    float best = -INFINITY;
+                    int k = -1;
+                    if (cv[i] > best) { best = cv[i]; k = 0; }
+                    if (v1[i] > best) { best = v1[i]; k = 1; }
+                    if (v2[i] > best) { best = v2[i]; k = 2; }
+                    a0[i] = k == 0 ? g[i] : 0.f; a1[i] = k == 1 ? g[i] : 0.f; a2[i] = k == 2 ? g[i] : 0.f;
+                }
+                if (to > 0) emit(2 * to - 1, pend + a0, co, cz);
+                emit(2 * to, a1, o0, z0);
+                pend = a2; cv = v2; co = o1; cz = z1;
+            }
+            emit(T - 1, pend, co, cz);
+        }
+    }
+    block_channel_publish(sa, qa, m, smem, C, sumsa);
+}
+
+// temporal_pool_code_bwd_kernel: carry = the gradient that tap 2 of window to - 1 sent to frame 2 to - 1
+__global__ __launch_bounds__(NT) void temporal_pool_code_bwd_roll_kernel(const bf16_t* gy, const uint16_t* code, bf16_t* g2, double* sumsa, size_t NBHW,
+                                                                        int HW, int C, size_t cpb, int T) {
+    const int To = T >> 1;
+    __shared__ float smem[2 * MAXC];
+    const int NB = (int)(NBHW / HW);
+    {
+        const size_t poff = (size_t)blockIdx.y * NB * To * HW * C;
+        gy += poff;
+        code += poff >> 3;
+        g2 += (size_t)blockIdx.y * NB * T * HW * C;
+        sumsa += (size_t)blockIdx.y * ADAMML_STAT_SLOTS * 2 * C;
+    }
+    ChanMap m(C, threadIdx.x);
+    float sa[8], qa[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) sa[i] = qa[i] = 0.f;
+    const size_t cb = (size_t)blockIdx.x * cpb;
+    const size_t ce = cb + cpb < NBHW ? cb + cpb : NBHW;
+    if (m.active) {
+        const int c = m.chunk * 8;
+        const size_t fstride = (size_t)HW * C;
+        for (size_t col = cb + m.rslot; col < ce; col += m.rows_per_pass) {
+            const size_t nb = col / HW, hw = col - nb * HW;
+            const size_t base = (nb * T * HW + hw) * C + c, gbase = (nb * To * HW + hw) * C + c;
+            auto emit = [&](int t, const f32x8& acc) {
+                const bf16x8 gb = f32_to_bf8(acc);
+                __builtin_nontemporal_store(gb, reinterpret_cast<bf16x8*>(g2 + base + t * fstride));
+                const f32x8 gq = bf8_to_f32(gb);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) sa[i] += gq[i];
+            };
+            // two windows in flight ahead of the one being expanded (a window is 18 bytes in for 32 bytes out per lane)
+            bf16x8 ng[2];
+            unsigned nc[2];
+#pragma unroll
+            for (int f = 0; f < 2; ++f) {
+                const int w = f < To ? f : To - 1;
+                ng[f] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(gy + gbase + w * fstride));
+                nc[f] = code[(gbase + w * fstride) >> 3];
+            }
+            f32x8 pend;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) pend[i] = 0.f;
+#pragma unroll 1
+            for (int to = 0; to < To; ++to) {
+                const f32x8 g = bf8_to_f32(ng[0]);
+                const unsigned cw = nc[0];
+                ng[0] = ng[1]; nc[0] = nc[1];
+                {
+                    const int w = to + 2 < To ? to + 2 : To - 1;
+                    ng[1] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(gy + gbase + w * fstride));
+                    nc[1] = code[(gbase + w * fstride) >> 3];
+                }
+                f32x8 a0, a1, a2;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    const unsigned k = (cw >> (2 * i)) & 3u;
+                    a0[i] = k == 0u ? g[i] : 0.f; a1[i] = k == 1u ? g[i] : 0.f; a2[i] = k == 2u ? g[i] : 0.f;
+                }
+                if (to > 0) emit(2 * to - 1, pend + a0);
+                emit(2 * to, a1);
+                pend = a2;
+            }
+            emit(T - 1, pend);
+        }
+    }
+    block_channel_publish(sa, qa, m, smem, C, sumsa);
+}
+
+// the frame counts of long clips: served by the rolling kernels
+inline bool long_clip(int T) { return T == 16 || T == 32; }
+
 }  // namespace
 
 extern "C" int adamml_temporal_pool_fwd(const void* x, const float* scale, const float* shift, int gstride, int act, void* y, int NB,
@@ -686,7 +948,10 @@ extern "C" int adamml_temporal_pool_fwd(const void* x, const float* scale, const
     const size_t n = (size_t)NB * To * (HWC / 8);
     if (!n) return ADAMML_OK;
     if (groups < 1) groups = 1;
-    if (T == 8 || T == 4 || T == 2) {
+    if (long_clip(T)) {
+        hipLaunchKernelGGL(temporal_pool_fwd_roll_kernel, dim3(grid_for((size_t)NB * (HWC / 8), NT, 8192 / groups + 1), groups), dim3(NT), 0, stream,
+                           (const bf16_t*)x, scale, shift, gstride, act, (bf16_t*)y, NB, T, HWC / 8, C, mode);
+    } else if (T == 8 || T == 4 || T == 2) {
         const dim3 grid(grid_for((size_t)NB * (HWC / 8), NT, 8192 / groups + 1), groups);
         dispatch_frames_8_4_2(T, [&](auto frames) {
             hipLaunchKernelGGL(temporal_pool_fwd_walk_kernel<decltype(frames)::value>, grid, dim3(NT), 0, stream, (const bf16_t*)x, scale, shift, gstride,
@@ -706,13 +971,17 @@ extern "C" int adamml_temporal_pool_bwd(const void* g_y, const void* x, const fl
     const size_t n = (size_t)NB * T * (HWC / 8);
     if (!n) return ADAMML_OK;
     if (groups < 1) groups = 1;
+    if (long_clip(T))
+        hipLaunchKernelGGL(temporal_pool_bwd_roll_kernel, dim3(grid_for((size_t)NB * (HWC / 8), NT, 8192 / groups + 1), groups), dim3(NT), 0, stream,
+                           (const bf16_t*)g_y, (const bf16_t*)x, scale, shift, gstride, act, (bf16_t*)g_x, NB, T, HWC / 8, C, mode);
+    else
     hipLaunchKernelGGL(temporal_pool_bwd_kernel, dim3(grid_for(n, NT, 4096 / groups + 1), groups), dim3(NT), 0, stream, (const bf16_t*)g_y,
                        (const bf16_t*)x, scale, shift, gstride, act, (bf16_t*)g_x, NB, T, To, HWC / 8, C, mode);
     return adamml_check_launch("temporal_pool_bwd");
 }
 
 extern "C" int adamml_temporal_pool_bwd_res_supported(int T, int C, int mode) {
-    return (T == 2 || T == 4 || T == 8) && mode == 0 && C % 8 == 0 && C <= MAXC ? 1 : 0;
+    return (T == 2 || T == 4 || T == 8 || long_clip(T)) && mode == 0 && C % 8 == 0 && C <= MAXC ? 1 : 0;
 }
 
 extern "C" int adamml_temporal_pool_bwd_res(const void* g_y, const void* out, int act, void* g2, const void* z_a, const float* vec_a,
@@ -724,6 +993,10 @@ extern "C" int adamml_temporal_pool_bwd_res(const void* g_y, const void* out, in
     if (!cols) return ADAMML_OK;
     if (groups < 1) groups = 1;
     const RowGrid rg = reduce_grid(cols, C, groups);
+    if (long_clip(T))
+        hipLaunchKernelGGL(temporal_pool_residual_bwd_roll_kernel, dim3((unsigned)rg.nblk, groups), dim3(NT), 0, stream, (const bf16_t*)g_y,
+                           (const bf16_t*)out, act, (bf16_t*)g2, (const bf16_t*)z_a, vec_a, sums_a, cols, HW, C, rg.ppb, T);
+    else
     dispatch_frames_8_4_2(T, [&](auto frames) {
         hipLaunchKernelGGL(temporal_pool_residual_bwd_kernel<decltype(frames)::value>, dim3((unsigned)rg.nblk, groups), dim3(NT), 0, stream,
                            (const bf16_t*)g_y, (const bf16_t*)out, act, (bf16_t*)g2, (const bf16_t*)z_a, vec_a, sums_a, cols, HW, C, rg.ppb);
@@ -740,6 +1013,10 @@ extern "C" int adamml_temporal_pool_bwd_code(const void* g_y, const uint16_t* co
     if (!cols) return ADAMML_OK;
     if (groups < 1) groups = 1;
     const RowGrid rg = reduce_grid(cols, C, groups);
+    if (long_clip(T))
+        hipLaunchKernelGGL(temporal_pool_code_bwd_roll_kernel, dim3((unsigned)rg.nblk, groups), dim3(NT), 0, stream, (const bf16_t*)g_y, code,
+                           (bf16_t*)g2, sums_a, cols, HW, C, rg.ppb, T);
+    else
     dispatch_frames_8_4_2(T, [&](auto frames) {
         hipLaunchKernelGGL(temporal_pool_code_bwd_kernel<decltype(frames)::value>, dim3((unsigned)rg.nblk, groups), dim3(NT), 0, stream,
                            (const bf16_t*)g_y, code, (bf16_t*)g2, sums_a, cols, HW, C, rg.ppb);

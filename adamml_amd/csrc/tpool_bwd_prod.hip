@@ -206,7 +206,8 @@ int tpp_blocks(int NB, int HW, int C, int groups) { return persistent_blocks((lo
 
 extern "C" int adamml_temporal_pool_bwd_code_prod_supported(int T, int C, int Cin) {
     // (the stage-2 form, T = 4 / C = 512 / Cin = 128 with eight waves and 4 x 8 accumulator tiles, does not fit the register file: not built)
-    return T == 8 && C == 256 && Cin == 64 ? 1 : 0;
+    // (T is a constant of the kernel's address arithmetic only: the window walk is a run-time loop, so longer clips are further instances)
+    return (T == 8 || T == 16 || T == 32) && C == 256 && Cin == 64 ? 1 : 0;
 }
 
 extern "C" size_t adamml_temporal_pool_bwd_code_prod_workspace(int NB, int T, int HW, int C, int Cin, int groups) {
@@ -219,7 +220,7 @@ extern "C" int adamml_temporal_pool_bwd_code_prod(const void* g_y, const uint16_
                                                   void* workspace, size_t workspace_bytes, int NB, int T, int HW, int C, int Cin, int groups,
                                                   hipStream_t stream) {
     if (!adamml_temporal_pool_bwd_code_prod_supported(T, C, Cin))
-        return adamml_set_error(ADAMML_EUNSUPPORTED, "temporal_pool_bwd_code_prod: (T, C, Cin) = (8, 256, 64)");
+        return adamml_set_error(ADAMML_EUNSUPPORTED, "temporal_pool_bwd_code_prod: (T, C, Cin) = (8 / 16 / 32, 256, 64)");
     if (!g_y || !code || !g2 || !sums_a || !a || !prod || !workspace) return adamml_set_error(ADAMML_EINVAL, "temporal_pool_bwd_code_prod: null argument");
     if (NB < 1 || HW < 1) return ADAMML_OK;
     if (groups < 1) groups = 1;
@@ -230,7 +231,11 @@ extern "C" int adamml_temporal_pool_bwd_code_prod(const void* g_y, const uint16_
     p.gy = (const bf16_t*)g_y; p.code = code; p.g2 = (bf16_t*)g2; p.sums = sums_a; p.a = (const bf16_t*)a;
     p.in_scale = in_scale; p.in_shift = in_scale ? in_shift : nullptr; p.ws = (float*)workspace;
     p.in_gs = in_gstride; p.act = in_act; p.clips = NB; p.HW = HW; p.C = C;
-    int rc = HW % 16 == 0 ? tpp_launch<8, 64, 4, true>(p, groups, nblk, stream) : tpp_launch<8, 64, 4, false>(p, groups, nblk, stream);
+    auto launch = [&](auto frames) {
+        constexpr int TT = decltype(frames)::value;
+        return HW % 16 == 0 ? tpp_launch<TT, 64, 4, true>(p, groups, nblk, stream) : tpp_launch<TT, 64, 4, false>(p, groups, nblk, stream);
+    };
+    const int rc = T == 32 ? launch(std::integral_constant<int, 32>{}) : T == 16 ? launch(std::integral_constant<int, 16>{}) : launch(std::integral_constant<int, 8>{});
     if (rc) return rc;
     return adamml_launch_split_reduce_grouped((const float*)workspace, prod, (size_t)C * Cin, nblk, groups, Cin, stream);
 }

@@ -967,7 +967,7 @@ def conv_bn_add_supported(rt, x, cs, need_grad, idn=None):
 def conv_bn_add_tpool_supported(rt, x, cs, idn, act, frames, mode):
     """Can conv_bn_add additionally run the temporal max-pool that is the block output's ONLY consumer in its epilogue
     (adamml_conv_fwd_bn_add_tpool)?  The identity must be a plain tensor (the last block of a stage has no downsample branch)."""
-    if mode != "max" or idn is None or idn.scale is not None or frames not in (2, 4, 8) or x.shape[0] % (rt.groups * frames):
+    if mode != "max" or idn is None or idn.scale is not None or frames not in (2, 4, 8, 16, 32) or x.shape[0] % (rt.groups * frames):
         return False
     d = cs.desc(x.shape, x.act, rt.groups, x.gs)
     return bool(hip.load().adamml_conv_fwd_bn_add_tpool_supported(byref(d), frames, act, 1 if x.scale is not None else 0))

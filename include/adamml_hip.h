@@ -116,7 +116,8 @@ ADAMML_API int adamml_conv_fwd_bn_add_next(const adamml_conv_desc_t* d, const vo
  * per group): the epilogue pools over the frames and writes pooled [groups * clips * frames / 2][OH*OW][Cout] and, when `code` is given,
  * 2 bits per pooled element (one uint16 per 8 channels: window tap 0..2 of the FIRST maximum, as nn.MaxPool3d, or 3 when the maximum
  * is <= 0, i.e. the ReLU passes no gradient) for adamml_temporal_pool_bwd_code.  The full-rate block output, its activation mask and the
- * pool's own pass (adamml_temporal_pool_fwd) never touch HBM.  frames in {2, 4, 8}, Cout % 128 == 0, act = ReLU, idn required. */
+ * pool's own pass (adamml_temporal_pool_fwd) never touch HBM.  frames in {2, 4, 8, 16, 32}, Cout % 128 == 0, act = ReLU, idn required.
+ * Beyond 8 frames every kernel walks the clip's frames for a fixed pixel tile and carries the odd frame two windows share: no cost grows with frames. */
 ADAMML_API int adamml_conv_fwd_bn_add_tpool_supported(const adamml_conv_desc_t* d, int frames, int act, int lazy_input);
 /* which device kernel serves the launch (a label for profilers): 0 = the tile kernel, 1 = the streaming kernel of csrc/conv1x1_fadd_next.hip
  * (64 -> 256 channels), 2 = the wave-slice streaming kernel of csrc/conv1x1_fadd_stream.hip (128 -> 512); same pooled tensor and codes. */
@@ -396,7 +397,7 @@ ADAMML_API int adamml_maxpool2d_bwd_bn_apply(const void* g_y, const uint8_t* idx
 /* Temporal MAX-pool backward fused with the residual-add backward of the block that produced the pool's input
  * (models/common.py:28-33 directly after models/resnet.py:110-111; the pool is that block output's only consumer):
  *   g2[n,t] = route(g_y)[n,t] * act'(out[n,t]),  sums_a += (sum g2, sum g2 * zhat_a)   per channel and group.
- * out / g2 / z_a: [groups*NB*T, HW, C]; g_y: [groups*NB*To, HW, C]; T in {2,4,8}.  Replaces adamml_temporal_pool_bwd +
+ * out / g2 / z_a: [groups*NB*T, HW, C]; g_y: [groups*NB*To, HW, C]; T in {2,4,8,16,32} (16, 32: a rolling walk over the windows).  Replaces adamml_temporal_pool_bwd +
  * adamml_residual_bwd (6.5 -> 3.5 passes over the block-output tensor). */
 ADAMML_API int adamml_temporal_pool_bwd_res_supported(int T, int C, int mode);
 ADAMML_API int adamml_temporal_pool_bwd_res(const void* g_y, const void* out, int act, void* g2, const void* z_a, const float* vec_a,
@@ -412,7 +413,7 @@ ADAMML_API int adamml_temporal_pool_bwd_code(const void* g_y, const uint16_t* co
  * BatchNorm in_scale / in_shift / in_act): prod [groups][C][Cin] = g2^T a per group, OVERWRITTEN -- the product
  * adamml_conv_bwd_weight_grouped(dz = g2) computes for the algebraic BatchNorm backward of conv3 (adamml_alg_sumfix needs it before the
  * coefficients exist), without reading g2 back.  g2 bit-identical, sums_a as adamml_temporal_pool_bwd_code.
- * (T, C, Cin) = (8, 256, 64): the end of ResNet-50 stage 1. */
+ * (T, C, Cin) = (8 / 16 / 32, 256, 64): the end of ResNet-50 stage 1 for clips of 8, 16 and 32 frames. */
 ADAMML_API int adamml_temporal_pool_bwd_code_prod_supported(int T, int C, int Cin);
 ADAMML_API size_t adamml_temporal_pool_bwd_code_prod_workspace(int NB, int T, int HW, int C, int Cin, int groups);
 ADAMML_API int adamml_temporal_pool_bwd_code_prod(const void* g_y, const uint16_t* code, void* g2, double* sums_a, const void* a, const float* in_scale,
