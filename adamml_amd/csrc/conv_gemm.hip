@@ -1421,6 +1421,10 @@ extern "C" int adamml_conv_fused_input_supported(const adamml_conv_desc_t* d) {
 
 extern "C" int adamml_conv_fwd(const adamml_conv_desc_t* d, const void* x, const void* w_packed, const float* in_scale,
                                const float* in_shift, void* y, double* stats, hipStream_t stream) {
+    // few pixels, many channels, no statistics (the eval / no-grad forward of a serving-size batch): the weight-streaming kernel of
+    // conv1x1_skinny.hip, bit-identical to the tile kernel.  Only this entry point: data gradients call conv_launch
+    if (d && x && w_packed && y && adamml_conv1x1_skinny_supported(d, stats != nullptr))
+        return adamml_conv1x1_skinny_launch(d, x, w_packed, in_scale, in_shift, y, stream);
     return conv_launch(d, x, w_packed, in_scale, in_shift, y, stats, nullptr, nullptr, 0, stream);
 }
 
@@ -1670,5 +1674,5 @@ extern "C" int adamml_conv_bwd_data(const adamml_conv_desc_t* d, const void* dz,
     if (!d) return adamml_set_error(ADAMML_EINVAL, "conv_bwd_data: null desc");
     if (dgrad_stride2_ok(d)) return conv_dgrad_stride2(d, dz, w_dgrad_packed, dx, accumulate, nullptr, nullptr, nullptr, 0, stream);
     const adamml_conv_desc_t g = dgrad_desc(d, accumulate, true);
-    return adamml_conv_fwd(&g, dz, w_dgrad_packed, nullptr, nullptr, dx, nullptr, stream);
+    return conv_launch(&g, dz, w_dgrad_packed, nullptr, nullptr, dx, nullptr, nullptr, nullptr, 0, stream);
 }

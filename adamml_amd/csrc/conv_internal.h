@@ -62,6 +62,11 @@ bool adamml_conv1x1_wide_expand_supported(const adamml_conv_desc_t* d);
 int adamml_conv1x1_wide_expand_launch(const adamml_conv_desc_t* d, const void* x, const void* w_packed, const float* in_scale, const float* in_shift,
                                       void* y, double* stats, hipStream_t stream);
 
+// ---- conv1x1_skinny.hip: forward 1x1 convs with few pixels and many channels (serving-size batches), weight-streaming form; the probe
+// adamml_conv1x1_skinny_supported is in the C ABI.  w_packed: the mode-0 pack; no statistics, no accumulation
+int adamml_conv1x1_skinny_launch(const adamml_conv_desc_t* d, const void* x, const void* w_packed, const float* in_scale, const float* in_shift,
+                                 void* y, hipStream_t stream);
+
 // ---- conv1x1_fadd_stream.hip: conv + BatchNorm + add (+ temporal pool) at the layer-2 shape, wave-slice streaming form
 int adamml_conv1x1_fadd_stream_supported(const adamml_conv_desc_t* d);
 int adamml_conv1x1_fadd_stream_launch(const adamml_conv_desc_t* d, const void* x, const void* w_packed, const float* in_scale, const float* in_shift,

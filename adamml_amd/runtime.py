@@ -492,6 +492,11 @@ def conv_bn(rt, x, cs, bn, act, sole_consumer=False, last_consumer=False):
     # (the 16-channel stem of the flow / RGB-diff ResNets is dispatched inside adamml_conv_fwd, csrc/conv_stem16.hip: the probe only labels it)
     if not stem and cs.kh == 7 and x.scale is None and hip.load().adamml_conv_stem16_supported(byref(d)):
         kern_f, role_f = "conv_stem16_kernel", R_KXK
+    # (likewise the serving-size 1x1 forward without statistics, csrc/conv1x1_skinny.hip; a training-mode launch passes statistics and is
+    # never asked: its host path is unchanged)
+    if not rt.training and not stem and not cs.depthwise and cs.kh * cs.kw == 1 and \
+            hip.load().adamml_conv1x1_skinny_supported(byref(d), 0):
+        kern_f = "conv1x1_skinny_kernel"
     hip.next_meta = (2 * work.macs, work.in_b + work.out_b + work.w_b, "conv_stem_kernel" if stem else kern_f, role_f)
     if pre is not None:
         hip.next_meta = (0.0, 0.0)

@@ -87,6 +87,13 @@ ADAMML_API int adamml_conv1x1_narrow_supported(const adamml_conv_desc_t* d, int 
  * tile-loop implicit GEMM (other kinds: 0).  Outputs are bit-identical either way (same K order and rounding points); the forward
  * statistics differ in summation order only.  ADAMML_WIDE_STREAM=0 in the environment disables the kernels (test hook; read at every call). */
 ADAMML_API int adamml_conv1x1_wide_supported(const adamml_conv_desc_t* d, int kind);
+/* 1 when adamml_conv_fwd serves the launch of descriptor d with the weight-streaming kernel of csrc/conv1x1_skinny.hip rather than the
+ * tile kernel: the serving-size forward (model.online(), online.Pool: one to eight videos per step) of the deep 1x1 convs, where the
+ * launch is its weight matrix read once.  has_stats: the call passes a statistics accumulator (train mode) -- those keep the tile kernel.
+ * 1x1 / stride 1, no accumulate, Cin and Cout multiples of 32, Cin <= 2048, not a narrow MobileNetV2 shape, and few pixels:
+ * ceil(P / 128) * ceil(Cout / 64) * groups < 256 (the tile kernel's grid below one workgroup per CU) and P = N * OH * OW per group at most
+ * 392, or 1568 for Cin >= 1024 (measured: profiles/conv1x1_skinny.json).  The output is bit-identical either way (same MFMA, K order and rounding point) -- a label for profilers. */
+ADAMML_API int adamml_conv1x1_skinny_supported(const adamml_conv_desc_t* d, int has_stats);
 /* Forward 1x1 / stride-1 conv with BatchNorm + residual add + activation in its epilogue (a bottleneck's conv3 + bn3 + add +
  * ReLU, models/resnet.py:104-112; a MobileNetV2 projection + add) -- for the cases where the BatchNorm vectors are known before
  * the launch: eval mode, or train mode with statistics from adamml_gram_stats.  bn_vec [groups][4][Cout] (scale, shift, ..) of
