@@ -713,7 +713,7 @@ int adamml_conv1x1_narrow_dual_launch(const adamml_conv_desc_t* d, const void* g
 }
 
 // ---- plain-loader data gradient of the EXPANSION convs (K = d->Cin = 96 / 144 / 192 gradient channels -> 16 / 24 / 32) with the BatchNorm-fused
-// epilogue (adamml_conv_bwd_data_bn) or accumulating into dx.  d: the data-gradient-shaped descriptor conv_launch works with.
+// epilogue (adamml_conv_bwd_data_bn) or accumulating into dx.  d: the data-gradient-shaped descriptor conv_plain works with.
 bool adamml_conv1x1_narrow_dgrad_epi_supported(const adamml_conv_desc_t* d) {
     if (d->KH != 1 || d->KW != 1 || d->stride != 1 || d->pad != 0 || d->up > 1) return false;
     const int ks = narrow_ks(d->Cin), co = d->Cout;

@@ -32,7 +32,7 @@ constexpr int SK_KP = 128;              // channels per panel = 4 MFMA K steps
 constexpr int SK_PD = 4;                // panels in flight per wave
 constexpr int SK_ROWB = SK_KP * 2;      // bytes of a pixel row of an LDS panel: 16 chunks of 16 bytes = all 64 banks
 constexpr int SK_MAXK = 2048;           // the lazy vectors live in LDS: 2 x 8 KB
-// the tile kernel's own grid arithmetic (conv_launch: 128 pixels x 64 channels per workgroup for small problems): the kernel serves
+// the tile kernel's own grid arithmetic (conv_plan: 128 pixels x 64 channels per workgroup for small problems): the kernel serves
 // launches that give the tile kernel fewer than one workgroup per CU ...
 constexpr int SK_TILE_WG = 256;
 // ... up to this many pixels per group (the measured cut-over: see adamml_conv1x1_skinny_supported): the tile kernel's time grows with

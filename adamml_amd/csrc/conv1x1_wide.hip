@@ -364,7 +364,7 @@ bool adamml_conv1x1_wide_expand_supported(const adamml_conv_desc_t* d) {
     return P >= 2048;
 }
 
-// d: forward-shaped descriptor of the launch conv_launch works with (for a data gradient: the data-gradient-shaped one)
+// d: forward-shaped descriptor of the launch conv_plain works with (for a data gradient: the data-gradient-shaped one)
 int adamml_conv1x1_wide_expand_launch(const adamml_conv_desc_t* d, const void* x, const void* w_packed, const float* in_scale, const float* in_shift,
                                       void* y, double* stats, hipStream_t stream) {
     WXP p;

@@ -4,9 +4,10 @@
 //     input patch is staged into LDS, and per-channel sum / sum-of-squares of the (bf16-rounded) output
 //     accumulated in the epilogue (train-mode BN statistics, SURVEY.md section 7 hard part 1);
 //   * data-gradient (same kernel on the flipped/transposed weight pack, `up` = forward stride).
-// This file: the tile kernel, conv_launch (which instance, or which streaming kernel of another file, serves a launch) and the
-// forward / data-gradient entry points.  Weight gradients: conv_wgrad.hip.  Small kernels of the algebraic BatchNorm backward:
-// conv_alg.hip.  Tile primitives: tile.h.  Launchers of the other files: conv_internal.h.
+// This file: the tile kernel, its host dispatch -- conv_plan (geometry, tile shape and grid of a launch) and one function per instance
+// family (conv_plain, which also routes to the streaming kernels of other files, conv_class, conv_fadd, conv_res, conv_res_prod, conv_cat,
+// conv_dual) -- and the forward / data-gradient entry points.  Weight gradients: conv_wgrad.hip.  Small kernels of the algebraic
+// BatchNorm backward: conv_alg.hip.  Tile primitives: tile.h.  Launchers of the other files: conv_internal.h.
 //
 // Replaces the torch operators called at models/resnet.py:83-113,138,199-210,
 // models/sound_mobilenet_v2.py:33-69 and models/policy_net.py:38-95 (nn.Conv2d + nn.BatchNorm2d + ReLU/ReLU6).
@@ -24,66 +25,67 @@ constexpr int BP = 128;      // pixels per block tile
 constexpr int BK = 32;       // K step (one MFMA K)
 
 struct ConvP {
-    const bf16_t* x;
-    const bf16_t* w;
-    const float* in_scale;
-    const float* in_shift;
-    bf16_t* y;
-    double* stats;
-    int N, H, W, Cin, OH, OW, Cout, KH, KW, stride, pad, up, up_shift, act, accumulate;
-    int P, K, cin_shift, n_ptiles, n_ctiles, tpb;
+    // every member has an initialiser (null / 0, up = 1): conv_plan fills the geometry and the tiling, a family writes its own fields and no others
+    const bf16_t* x = nullptr;
+    const bf16_t* w = nullptr;
+    const float* in_scale = nullptr;
+    const float* in_shift = nullptr;
+    bf16_t* y = nullptr;
+    double* stats = nullptr;
+    int N = 0, H = 0, W = 0, Cin = 0, OH = 0, OW = 0, Cout = 0, KH = 0, KW = 0, stride = 0, pad = 0, up = 1, up_shift = 0, act = 0, accumulate = 0;
+    int P = 0, K = 0, cin_shift = 0, n_ptiles = 0, n_ctiles = 0, tpb = 0;
     // data-gradient epilogue fused with the BatchNorm backward reduction of the tensor the gradient flows into
-    size_t gx, gy;               // element strides between BatchNorm groups of x / y (blockIdx.y = group)
-    int in_gstride;
-    const bf16_t* bn_z;          // raw conv output that produced the consumer's input (same shape as y), or null
-    const float* bn_vec;         // [4][Cout']: scale, shift, mean, invstd of that BatchNorm
-    int bn_act;
+    size_t gx = 0, gy = 0;               // element strides between BatchNorm groups of x / y (blockIdx.y = group)
+    int in_gstride = 0;
+    const bf16_t* bn_z = nullptr;          // raw conv output that produced the consumer's input (same shape as y), or null
+    const float* bn_vec = nullptr;         // [4][Cout']: scale, shift, mean, invstd of that BatchNorm
+    int bn_act = 0;
     // residual form of that epilogue (RES kernels; the gradient flows into the OUTPUT of a residual add,
     // out = act(bn(z) [+ bn2(z2)] + ..)): the activation mask comes from the stored block output, `accumulate` adds the
     // identity-path gradient already in y, and the sums of a second BatchNorm feeding the same add (downsample branch)
     // are accumulated alongside
-    const bf16_t* res_out;       // block output [same shape as y]
-    const uint8_t* res_mask;     // or: 1 bit per element, act'(block output) != 0 (adamml_bn_act_add_mask) -- 1/16 of the bytes
-    int res_act;
-    const bf16_t* bn_z2;         // raw output of the second BatchNorm'd operand of the add, or null
-    const float* bn_vec2;
-    double* stats2;
+    const bf16_t* res_out = nullptr;       // block output [same shape as y]
+    const uint8_t* res_mask = nullptr;     // or: 1 bit per element, act'(block output) != 0 (adamml_bn_act_add_mask) -- 1/16 of the bytes
+    int res_act = 0;
+    const bf16_t* bn_z2 = nullptr;         // raw output of the second BatchNorm'd operand of the add, or null
+    const float* bn_vec2 = nullptr;
+    double* stats2 = nullptr;
     // DUAL kernels (1x1 data gradient whose input dz is the BatchNorm backward of (g, z)): the loader reads g (= x) and z
     // (= x2) and forms dz = A[c] g + B[c] z + C[c] on the way into LDS (aff = [3][K] per group); `side` (optional) receives
     // dz for the weight-gradient kernel, written by the workgroups of cout tile 0 -- adamml_bn_bwd_apply never runs
-    const bf16_t* x2;
-    const float* aff;
-    bf16_t* side;
+    const bf16_t* x2 = nullptr;
+    const float* aff = nullptr;
+    bf16_t* side = nullptr;
     // K-concatenated second input (MODE 0): K steps k >= K1 read xb [pixels][C2] (with the lazy in_scale / in_shift transform,
     // which then applies to xb ONLY) instead of x [pixels][K1]; weights are per group (gw elements apart); epi_add [Cout] per
     // group is added to every output row before the epilogue's mask / store.  Used by the algebraic BatchNorm backward
     // (adamml_conv_bwd_data_alg): dx = (W^T diag(A)) g' + (W^T diag(B) W) a + W^T C without ever forming dz.
-    const bf16_t* xb;
-    int K1, C2;
-    size_t gw;
-    const float* epi_add;
+    const bf16_t* xb = nullptr;
+    int K1 = 0, C2 = 0;
+    size_t gw = 0;
+    const float* epi_add = nullptr;
     // FADD kernels (forward 1x1 conv whose BatchNorm vectors are known BEFORE the launch -- eval mode, or train mode with the
     // statistics derived from the Gram matrix of the input, adamml_gram_stats): the epilogue applies bn_vec (scale, shift of
     // THIS conv's BatchNorm), adds the identity operand res_out (optionally lazily normalised with id_scale / id_shift),
     // applies res_act and writes the block output + its 1-bit activation mask; the raw conv output never reaches HBM
-    const float* id_scale;
-    const float* id_shift;
-    int id_gstride;
-    uint8_t* mask_out;
+    const float* id_scale = nullptr;
+    const float* id_shift = nullptr;
+    int id_gstride = 0;
+    uint8_t* mask_out = nullptr;
     // PF (RES + EID kernels): the per-group product P[g][cout][c] = sum_p g'[p][cout] * a[p][c] of the gradient tile this kernel
     // has just formed with a second, lazily normalised tensor a [pixels][pf_C] (the input of the conv whose output gradient g'
     // is -- the g'^T a of the algebraic BatchNorm backward) is accumulated on the matrix cores from the staged tile: the separate
     // pass over g' and a (adamml_conv_bwd_weight_grouped) disappears.  One partial [BC][pf_C] per workgroup -> pf_ws.
-    const bf16_t* pf_a;
-    const float* pf_scale;
-    const float* pf_shift;
-    float* pf_ws;                // [group][cout tile][split = workgroup of that pair][BC][pf_C]
-    int pf_act, pf_gs, pf_nsplit;
+    const bf16_t* pf_a = nullptr;
+    const float* pf_scale = nullptr;
+    const float* pf_shift = nullptr;
+    float* pf_ws = nullptr;                // [group][cout tile][split = workgroup of that pair][BC][pf_C]
+    int pf_act = 0, pf_gs = 0, pf_nsplit = 0;
     // MODE 3 (one parity class of the data gradient of a stride-2 conv, see conv_dgrad_stride2)
-    int wK;                      // weight row stride in elements (== K except in MODE 3, where K covers the class taps only)
-    int cls_nt;                  // taps of this class (0..4)
-    unsigned cls_code;           // per tap, 8 bits: dh | dw << 1 | weight-pack tap index << 2
-    int oH, oW, o_ph, o_pw;      // output rows are scattered: pixel (i, j) of the class grid -> (2i + o_ph, 2j + o_pw) of [oH, oW]
+    int wK = 0;                      // weight row stride in elements (== K except in MODE 3, where K covers the class taps only)
+    int cls_nt = 0;                  // taps of this class (0..4)
+    unsigned cls_code = 0;           // per tap, 8 bits: dh | dw << 1 | weight-pack tap index << 2
+    int oH = 0, oW = 0, o_ph = 0, o_pw = 0;      // output rows are scattered: pixel (i, j) of the class grid -> (2i + o_ph, 2j + o_pw) of [oH, oW]
     // TP (FADD kernels): the block output feeds ONLY a temporal max-pool (models/common.py:4-33 after the last block of a ResNet stage,
     // models/resnet.py:205-209).  A pixel tile then holds the TP frames of a clip for BP / TP pixels (row r = frame r / (BP / TP), pixel
     // r % (BP / TP) of block tp_blk), the epilogue pools over the frames and writes the POOLED tensor tp_y [clips * TP / 2][Q][Cout] and
@@ -92,9 +94,9 @@ struct ConvP {
     // TP = 16 / 32: the clip is walked in segments of 8 frames.  The TP / 8 tiles of a (clip, pixel block) are consecutive tiles of ONE workgroup
     // (tpb % (TP / 8) == 0), every tile has the TP = 8 row layout, and an epilogue thread -- it owns the same (pixel, 8-channel chunk) in
     // every tile -- carries the last (odd) frame of a segment in registers: tap 0 of the next segment's first window.  Registers and LDS as TP = 8.
-    int tp_nblk, tp_Q;           // pixel blocks per clip (ceil(Q / (BP / min(TP, 8)))), pixels per frame
-    bf16_t* tp_y;
-    uint16_t* tp_code;
+    int tp_nblk = 0, tp_Q = 0;           // pixel blocks per clip (ceil(Q / (BP / min(TP, 8)))), pixels per frame
+    bf16_t* tp_y = nullptr;
+    uint16_t* tp_code = nullptr;
 };
 
 __device__ __forceinline__ int lds_off(int row, int chunk) {
@@ -1116,7 +1118,7 @@ struct ResEpi { const void* res_out; const uint8_t* res_mask; int res_act; const
 struct DualIn { const void* z; const float* aff; void* side; };
 // K-concatenated second input, per-group weights, epilogue constant (ConvP::xb ..)
 struct CatIn { const void* xb; int C2; size_t gw; const float* epi_add; };
-// product with a second tensor accumulated from the gradient tile (ConvP::pf_a ..); ws: partial workspace, nsplit: out
+// product with a second tensor accumulated from the gradient tile (ConvP::pf_a ..); ws: workspace of the per-workgroup partials (pf_split), out: their sum
 struct PfIn { const void* a; const float* scale; const float* shift; int act, gs, C; float* out; void* ws; size_t ws_bytes; };
 // forward BatchNorm + residual-add epilogue (ConvP::id_scale ..)
 struct FaddEpi { const float* vec; const void* idn; const float* id_scale; const float* id_shift; int id_gstride; int act; uint8_t* mask_out;
@@ -1125,6 +1127,8 @@ struct FaddEpi { const float* vec; const void* idn; const float* id_scale; const
 // ---- the instances of conv_gemm_kernel, one launcher per family.  The kernel's positional template list
 //   <BC, MODE, PD, RES, DUAL, CAT, FADD, GLDS, EID, LZF, EPI, PF, TP>
 // is written out HERE and nowhere else; a launcher's own parameters are the ones that vary inside its family, under the kernel's names.
+// Each family's launchers are called from its one host function further down (conv_plain / conv_class: launch_plain, launch_rt_epi;
+// conv_fadd; conv_res: launch_res, launch_res_kxk; conv_res_prod; conv_cat; conv_dual), which receives the family's record above.
 struct ConvGrid { dim3 grid; hipStream_t stream; };
 
 template <int BC, int MODE, bool GLDS, int EPI>         // plain conv, one K step of look-ahead, the epilogue compiled in
@@ -1173,16 +1177,14 @@ template <class F> static void with_tp(int tp, F f) {
 }
 template <class F> static void with_flag(bool b, F f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
 
-// the plain instances of one (BC, MODE): LDS-DMA staging or the register-staged loader with the epilogue compiled in, deep prefetch (MODE
-// 0) or the strided loader (MODE 2) with the run-time epilogue.  `lazy` = the input has a lazy transform (register-staged loader); the
-// caller has refused a lazy GRADIENT operand (cls or bn_z), so MODE 3 and the bn_z epilogue (EPI 1) exist behind LDS-DMA only, and `deep`
-// is never set for MODE 1
+// the plain instances of one (BC, MODE 0 .. 2): LDS-DMA staging or the register-staged loader with the epilogue compiled in, deep prefetch
+// (MODE 0) or the strided loader (MODE 2) with the run-time epilogue.  `lazy` = the input has a lazy transform (register-staged loader);
+// conv_plain has refused a lazy GRADIENT operand (bn_z), so the bn_z epilogue (EPI 1) exists behind LDS-DMA only, and `deep` is never set
+// for MODE 1.  (MODE 3, whose operand is a gradient too, has the LDS-DMA instances alone: conv_class)
 template <int BC, int MODE>
 static void launch_conv(bool lazy, bool deep, int epi, const ConvGrid& g, const ConvP& p) {
     if constexpr (MODE == 2) {
         if (deep) launch_rt_epi<BC, 2, 3>(g, p); else launch_rt_epi<BC, 2, 1>(g, p);
-    } else if constexpr (MODE == 3) {
-        with_epi(epi, [&](auto e) { launch_plain<BC, 3, true, e()>(g, p); });
     } else {
         if (!lazy) return with_epi(epi, [&](auto e) { launch_plain<BC, MODE, true, e()>(g, p); });
         if constexpr (MODE == 0)
@@ -1191,80 +1193,81 @@ static void launch_conv(bool lazy, bool deep, int epi, const ConvGrid& g, const 
     }
 }
 
-static int conv_launch(const adamml_conv_desc_t* d, const void* x, const void* w_packed, const float* in_scale,
-                       const float* in_shift, void* y, double* stats, const void* bn_z, const float* bn_vec, int bn_act,
-                       hipStream_t stream, const DgradClass* cls = nullptr, const ResEpi* res = nullptr, const DualIn* dual = nullptr,
-                       const CatIn* cat = nullptr, const FaddEpi* fadd = nullptr, const PfIn* pf = nullptr) {
+// ---- host dispatch.  conv_plan turns a descriptor into the geometry, the tile shape and the grid of a launch; the few things a family changes
+// about that plan are its named inputs (PlanOpts).  Below it, one function per instance family: each takes exactly its operands, runs the checks
+// every launch shares (conv_check), plans, writes its own ConvP fields (the others keep their initialisers) and launches.  Only conv_plain
+// routes to the kernels of other files.
+
+static int conv_check(const adamml_conv_desc_t* d, const void* x, const void* w_packed, const void* y) {
     if (!d || !x || !w_packed || !y) return adamml_set_error(ADAMML_EINVAL, "conv_fwd: null argument");
     if (d->Cin % 8 || d->Cout % 8) return adamml_set_error(ADAMML_EINVAL, "conv_fwd: channels must be multiples of 8 (Cin=%d Cout=%d)", d->Cin, d->Cout);
-    if (!cls && !fadd && !res && adamml_conv3x3_c64_supported(d))       // (the residual form of the 64-channel kernel: adamml_conv_bwd_data_res)
-        return adamml_conv3x3_c64_launch(d, x, w_packed, in_scale, in_shift, y, stats, bn_z, bn_vec, bn_act, stream);
-    // 7x7 / 2 stem of a 16-channel image (flow / RGB-diff ResNets), plain input: LDS-patch kernel with resident weights (conv_stem16.hip)
-    if (!cls && !fadd && !res && !dual && !cat && !pf && !bn_z && !in_scale && !d->accumulate && adamml_conv_stem16_supported(d))
-        return adamml_conv_stem16_fwd_launch(d, x, w_packed, y, stats, stream);
-    // narrow 1x1 convs of the MobileNetV2s (plain forward / plain data gradient): the barrier-free streaming kernel (conv1x1_narrow.hip)
-    if (!cls && !fadd && !res && !dual && !cat && !pf && !bn_z && adamml_conv1x1_narrow_fwd_supported(d))
-        return adamml_conv1x1_narrow_fwd_launch(d, x, w_packed, in_scale, in_shift, y, stats, stream);
-    // expanding 1x1 convs of ResNet layers 3-4 (K = 256 / 512 -> >= 2 K channels; plain forward, stride-2 downsample forward, plain or
-    // accumulating data gradient): activation-stationary streaming kernel (conv1x1_wide.hip; it has no accumulating form of a lazy input:
-    // that call stays with conv_gemm_kernel)
-    if (!cls && !fadd && !res && !dual && !cat && !pf && !bn_z && !(d->accumulate && in_scale) && adamml_conv1x1_wide_expand_supported(d))
-        return adamml_conv1x1_wide_expand_launch(d, x, w_packed, in_scale, in_shift, y, stats, stream);
-    // ... their data gradients with the BatchNorm-fused epilogue (bn_z) or accumulating into the output
-    if (!cls && !fadd && !res && !dual && !cat && !pf && !in_scale && (bn_z ? stats != nullptr && !d->accumulate : d->accumulate != 0) &&
-        adamml_conv1x1_narrow_dgrad_epi_supported(d))
-        return adamml_conv1x1_narrow_dgrad_epi_launch(d, x, w_packed, y, bn_z, bn_vec, bn_act, stats, stream);
+    return ADAMML_OK;
+}
+
+// the operands every family has; bn_z / bn_vec / bn_act: the BatchNorm-fused data-gradient epilogue (ConvP::bn_z), where the family has it
+static ConvP conv_operands(const void* x, const void* w_packed, const float* in_scale, const float* in_shift, void* y, double* stats,
+                           const void* bn_z = nullptr, const float* bn_vec = nullptr, int bn_act = 0) {
     ConvP p;
     p.x = (const bf16_t*)x; p.w = (const bf16_t*)w_packed; p.in_scale = in_scale; p.in_shift = in_shift;
     p.y = (bf16_t*)y; p.stats = stats;
     p.bn_z = (const bf16_t*)bn_z; p.bn_vec = bn_vec; p.bn_act = bn_act;
-    p.res_out = res ? (const bf16_t*)res->res_out : nullptr; p.res_act = res ? res->res_act : 0;
-    p.res_mask = res ? res->res_mask : nullptr;
-    p.bn_z2 = res ? (const bf16_t*)res->bn_z2 : nullptr; p.bn_vec2 = res ? res->bn_vec2 : nullptr; p.stats2 = res ? res->stats2 : nullptr;
-    p.x2 = dual ? (const bf16_t*)dual->z : nullptr; p.aff = dual ? dual->aff : nullptr; p.side = dual ? (bf16_t*)dual->side : nullptr;
-    p.xb = cat ? (const bf16_t*)cat->xb : nullptr; p.K1 = d->Cin; p.C2 = cat ? cat->C2 : 0; p.gw = cat ? cat->gw : 0;
-    p.epi_add = cat ? cat->epi_add : nullptr;
-    p.id_scale = fadd ? fadd->id_scale : nullptr; p.id_shift = fadd ? fadd->id_shift : nullptr; p.id_gstride = fadd ? fadd->id_gstride : 0;
-    p.mask_out = fadd ? fadd->mask_out : nullptr;
-    p.tp_nblk = p.tp_Q = 0; p.tp_y = nullptr; p.tp_code = nullptr;
-    p.pf_a = nullptr; p.pf_scale = p.pf_shift = nullptr; p.pf_ws = nullptr; p.pf_act = p.pf_gs = p.pf_nsplit = 0;
-    if (fadd) { p.bn_vec = fadd->vec; p.res_out = (const bf16_t*)fadd->idn; p.res_act = fadd->act; }
-    const int groups = d->groups < 1 ? 1 : d->groups;
+    return p;
+}
+
+// PF: one [128][64] fp32 partial per workgroup -> few, long-lived workgroups (~6 per CU slot pair over all groups and cout tiles).  The launch
+// and the workspace query (adamml_conv_bwd_data_res_prod_workspace) both ask here
+struct PfSplit { int tpb, nsplit; size_t ws_bytes; };
+static PfSplit pf_split(int n_ptiles, int n_ctiles, int groups) {
+    long nsp = 1536 / ((long)n_ctiles * groups);
+    if (nsp < 1) nsp = 1;
+    int tpb = ceil_div(n_ptiles, (int)nsp);
+    if (tpb < 1) tpb = 1;
+    const int nsplit = ceil_div(n_ptiles, tpb);
+    return {tpb, nsplit, (size_t)groups * n_ctiles * nsplit * 128 * 64 * sizeof(float)};
+}
+
+struct PlanOpts {
+    const DgradClass* cls = nullptr;   // MODE 3: the class's taps and pixel grid replace K, P and OH / OW; output rows are scattered into d's OH x OW
+    int cat_C2 = 0;                    // CAT: channels of the second input, appended to K
+    int tp = 0;                        // TP: frames per clip -- a pixel tile holds whole clips (or 8-frame segments); 128-wide cout tile
+    bool pf = false;                   // PF: pixel tiles per workgroup from pf_split
+};
+struct Plan { int BC, mode, groups; bool deep; int rc; };
+
+// Fills the geometry, group strides, mode and shifts, tiling (n_ptiles, n_ctiles, tpb) and PF split of p, the grid of g and pl.  false: nothing
+// to launch and pl.rc is the answer -- a refusal, or ADAMML_OK for an empty problem
+static bool conv_plan(const adamml_conv_desc_t* d, const PlanOpts& o, hipStream_t stream, ConvP& p, ConvGrid& g, Plan& pl) {
+    const auto stop = [&](int rc) { pl.rc = rc; return false; };
+    const int groups = pl.groups = d->groups < 1 ? 1 : d->groups;
     p.gx = (size_t)d->N * d->H * d->W * d->Cin;
     p.gy = (size_t)d->N * d->OH * d->OW * d->Cout;
     p.in_gstride = d->in_gstride;
     p.N = d->N; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.OH = d->OH; p.OW = d->OW; p.Cout = d->Cout;
     p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.up = d->up < 1 ? 1 : d->up;
     p.up_shift = ilog2_exact(p.up);
-    if (p.up_shift < 0) return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_fwd: up=%d is not a power of two", p.up);
+    if (p.up_shift < 0) return stop(adamml_set_error(ADAMML_EUNSUPPORTED, "conv_fwd: up=%d is not a power of two", p.up));
     p.act = d->act; p.accumulate = d->accumulate;
-    p.P = d->N * d->OH * d->OW; p.K = d->KH * d->KW * d->Cin;
-    if (cat) {
-        if (d->KH * d->KW != 1 || d->stride != 1 || (d->up > 1) || d->Cin % BK || cat->C2 % 8 || cls || res || dual)
-            return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_data_alg: 1x1 / stride-1 convs with Cout %% 32 == 0 only");
-        p.K = d->Cin + cat->C2;
+    p.P = d->N * d->OH * d->OW;
+    p.wK = p.K = d->KH * d->KW * d->Cin + o.cat_C2;
+    p.oH = d->OH; p.oW = d->OW;
+    if (o.cls) {
+        p.cls_nt = o.cls->nt; p.cls_code = o.cls->code; p.o_ph = o.cls->ph; p.o_pw = o.cls->pw;
+        p.OH = o.cls->OHc; p.OW = o.cls->OWc;
+        p.P = d->N * o.cls->OHc * o.cls->OWc;
+        p.K = o.cls->nt * d->Cin;
     }
-    p.wK = p.K;
-    p.cls_nt = 0; p.cls_code = 0; p.oH = d->OH; p.oW = d->OW; p.o_ph = p.o_pw = 0;
-    if (cls) {
-        p.cls_nt = cls->nt; p.cls_code = cls->code; p.o_ph = cls->ph; p.o_pw = cls->pw;
-        p.OH = cls->OHc; p.OW = cls->OWc;
-        p.P = d->N * cls->OHc * cls->OWc;
-        p.K = cls->nt * d->Cin;
-    }
-    const bool multitap = d->KH * d->KW > 1 || cls;
-    p.cin_shift = 0;
+    const bool multitap = d->KH * d->KW > 1 || o.cls;
     if (multitap) {
         p.cin_shift = ilog2_exact(d->Cin);
-        if (p.cin_shift < 0) return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_fwd: KxK conv needs power-of-two Cin (got %d)", d->Cin);
+        if (p.cin_shift < 0) return stop(adamml_set_error(ADAMML_EUNSUPPORTED, "conv_fwd: KxK conv needs power-of-two Cin (got %d)", d->Cin));
     }
-    if (p.P <= 0) return ADAMML_OK;
+    if (p.P <= 0) return stop(ADAMML_OK);
     bool narrow = d->Cout <= 64 || (d->Cout % 128 != 0 && d->Cout < 256);
     // small problems: halve the cout tile so that at least ~2 workgroups per CU exist
     if (!narrow && (long)ceil_div(p.P, BP) * ceil_div(d->Cout, 128) * groups < 512) narrow = true;
-    const int tp = fadd ? fadd->tp_frames : 0;
+    const int tp = o.tp;
     if (tp) narrow = false;
-    const int BC = narrow ? 64 : 128;
+    pl.BC = narrow ? 64 : 128;
     p.n_ptiles = ceil_div(p.P, BP);
     if (tp) {
         // tiles = (clip, block of BP / tp pixels); all frames of a clip's pixel block sit in one tile -- or, beyond 8 frames, in the tp / 8
@@ -1273,115 +1276,200 @@ static int conv_launch(const adamml_conv_desc_t* d, const void* x, const void* w
         p.tp_Q = d->OH * d->OW;
         p.tp_nblk = ceil_div(p.tp_Q, BP / tpf);
         p.n_ptiles = (d->N / tp) * p.tp_nblk * (tp / tpf);
-        p.tp_y = (bf16_t*)fadd->tp_y; p.tp_code = fadd->tp_code;
     }
-    p.n_ctiles = ceil_div(d->Cout, BC);
+    p.n_ctiles = ceil_div(d->Cout, pl.BC);
     // consecutive pixel tiles per workgroup (amortises the statistics publication), keeping >= ~2048 workgroups
     p.tpb = (int)((long)p.n_ptiles * p.n_ctiles * groups / 2048);
     if (p.tpb < 1) p.tpb = 1;
     if (p.tpb > 8) p.tpb = 8;
     if (tp > 8) p.tpb = p.tpb < tp / 8 ? tp / 8 : p.tpb / (tp / 8) * (tp / 8);      // whole segment chains per workgroup
-    if (pf) {
-        // one [BC][64] partial per workgroup: few, long-lived workgroups (~6 per CU slot pair over all groups and cout tiles)
-        const long target = 1536;
-        long nsp = target / ((long)p.n_ctiles * groups);
-        if (nsp < 1) nsp = 1;
-        p.tpb = (int)ceil_div(p.n_ptiles, (int)nsp);
-        if (p.tpb < 1) p.tpb = 1;
+    if (o.pf) {
+        const PfSplit s = pf_split(p.n_ptiles, p.n_ctiles, groups);
+        p.tpb = s.tpb; p.pf_nsplit = s.nsplit;
     }
-    const dim3 grid(ceil_div(p.n_ptiles, p.tpb) * p.n_ctiles, groups);
-    const ConvGrid cg{grid, stream};
+    g.grid = dim3(ceil_div(p.n_ptiles, p.tpb) * p.n_ctiles, groups);
+    g.stream = stream;
     const int taps = d->KH * d->KW;
     // MODE 0 needs the whole row base in 32-bit element offsets (true for every layer of the hot path)
-    if ((long)d->N * d->H * d->W * d->Cin >= (1L << 31)) return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_fwd: input tensor exceeds 2^31 elements");
-    const int mode = cls ? 3 : (p.up > 1 ? 2 : (multitap ? (taps <= 64 ? 1 : 2) : 0));
-    if (mode == 2 && !multitap) { p.cin_shift = 30; }      // 1x1 strided dgrad: tap = k >> 30 = 0, ci = k
+    if ((long)d->N * d->H * d->W * d->Cin >= (1L << 31))
+        return stop(adamml_set_error(ADAMML_EUNSUPPORTED, "conv_fwd: input tensor exceeds 2^31 elements"));
+    pl.mode = o.cls ? 3 : (p.up > 1 ? 2 : (multitap ? (taps <= 64 ? 1 : 2) : 0));
+    if (pl.mode == 2 && !multitap) { p.cin_shift = 30; }      // 1x1 strided dgrad: tap = k >> 30 = 0, ci = k
     const int nk = ceil_div(p.K, BK);
     // < 1 wave of workgroups per CU slot and a long K loop: explicit look-ahead instead of occupancy.  Measured (tools/bench_conv.py,
     // B = 72): it pays for the 1x1 layers of layer 4 (0.115 vs 0.137 ms) and costs on its 3x3 layers (0.189 vs 0.139 ms forward,
     // 0.197 vs 0.146 ms data gradient: the tap gathers of MODE 1 hit L2 and the deeper ring only lowers the occupancy)
-    const bool deep = (long)grid.x * grid.y <= 768 && nk >= 8 && mode != 1;
-    if (fadd) {
-        if (mode != 0 || res || dual || cat || stats) return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_fwd_bn_add: only 1x1 / stride-1 convs");
-        if (!in_scale || p.K <= 512) {
-            // operands by LDS-DMA (a lazily normalised input is transformed at the fragment: LZF); with an identity operand, that one is
-            // requested at the start of each tile (EID)
-            const bool eid = p.res_out != nullptr;
-            if (tp) {
-                with_flag(in_scale != nullptr, [&](auto lzf) { with_tp(tp, [&](auto tv) { launch_fadd_tp<lzf(), tv()>(cg, p); }); });
-                return adamml_check_launch("conv_fwd_bn_add_tpool");
-            }
-            with_bc(BC, [&](auto bc) {
-                with_flag(in_scale != nullptr, [&](auto lzf) {
-                    if (eid) launch_fadd<bc(), true, 1, lzf()>(cg, p); else launch_fadd<bc(), true, 0, lzf()>(cg, p);
-                });
-            });
-        } else
-        if (tp) return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_fwd_bn_add_tpool: needs the LDS-DMA kernel (K <= 512 for a lazy input)");
-        else with_bc(BC, [&](auto bc) { launch_fadd<bc(), false, 0, false>(cg, p); });
-        return adamml_check_launch("conv_fwd_bn_add");
-    }
-    if (res) {
-        // MODE 1 (3x3 / pad 1 / stride 1, dense dz): the epilogue only needs tile row r to be output pixel p0 + r, as in MODE 0
-        if (mode != 0 && !(mode == 1 && !pf && p.up == 1 && p.stride == 1))
-            return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_data_res: only 1x1 / stride-1 and 3x3 / pad-1 / stride-1 convs");
-        if (pf) {
-            if (BC != 128 || d->Cout % 128 || pf->C != 64 || in_scale || !p.res_mask || !p.accumulate || p.bn_z || p.bn_z2 || !stats)
-                return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_data_res_prod: needs Cout %% 128 == 0, a 64-channel product operand, "
-                                                             "the accumulate + 1-bit-mask + sum(g')-only form");
-            p.pf_nsplit = ceil_div(p.n_ptiles, p.tpb);
-            const size_t need = (size_t)groups * p.n_ctiles * p.pf_nsplit * 128 * 64 * sizeof(float);
-            if (!pf->ws || pf->ws_bytes < need) return adamml_set_error(ADAMML_EINVAL, "conv_bwd_data_res_prod: workspace too small (need %zu bytes)", need);
-            p.pf_a = (const bf16_t*)pf->a; p.pf_scale = pf->scale; p.pf_shift = pf->scale ? pf->shift : nullptr; p.pf_act = pf->act; p.pf_gs = pf->gs;
-            p.pf_ws = (float*)pf->ws;
-            launch_res_prod(cg, p);
-            int rc = adamml_check_launch("conv_bwd_data_res_prod");
-            if (rc) return rc;
-            // P[g][ctile * 128 + r][c] = sum over the workgroups of (g, ctile), in workgroup order
-            launch_wgrad_reduce((const float*)pf->ws, pf->out, (size_t)128 * 64, p.pf_nsplit, 1, 64, 1, groups * p.n_ctiles, stream);
-            return adamml_check_launch("conv_bwd_data_res_prod (reduce)");
-        }
-        if (in_scale) return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_data_res: the gradient operand is never lazy");
-        if (mode == 1) {
-            with_bc(BC, [&](auto bc) { launch_res_kxk<bc()>(cg, p); });
-            return adamml_check_launch("conv_bwd_data_res (3x3)");
-        }
-        // the algebraic backward's form (identity gradient + 1-bit mask, sum(g') only): identity-side loads at the start of each tile (EID)
-        const bool eid = p.res_mask && p.accumulate && !p.bn_z && !p.bn_z2;
-        with_bc(BC, [&](auto bc) { if (eid) launch_res<bc(), 1>(cg, p); else launch_res<bc(), 0>(cg, p); });
-        return adamml_check_launch("conv_bwd_data_res");
-    }
-    if (cat) {
-        if (mode != 0) return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_data_alg: only 1x1 / stride-1 convs");
-        with_bc(BC, [&](auto bc) { launch_cat<bc()>(cg, p); });
-        return adamml_check_launch("conv_bwd_data_alg");
-    }
-    if (dual) {
-        if (mode != 0 || res) return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_data_dual: only 1x1 / stride-1 convs");
-        with_bc(BC, [&](auto bc) { launch_dual<bc()>(cg, p); });
-        return adamml_check_launch("conv_bwd_data_dual");
-    }
+    pl.deep = (long)g.grid.x * g.grid.y <= 768 && nk >= 8 && pl.mode != 1;
+    return true;
+}
+
+static int plain_epi(const ConvP& p) { return p.bn_z ? 1 : (p.accumulate ? 2 : 0); }      // EPI of the plain instances (launch_plain)
+
+// plain forward conv / plain data gradient, the latter with the BatchNorm-fused epilogue (bn_z) or accumulating into y (d->accumulate)
+static int conv_plain(const adamml_conv_desc_t* d, const void* x, const void* w_packed, const float* in_scale, const float* in_shift, void* y,
+                      double* stats, const void* bn_z, const float* bn_vec, int bn_act, hipStream_t stream) {
+    if (int rc = conv_check(d, x, w_packed, y)) return rc;
+    if (adamml_conv3x3_c64_supported(d))                                // (the residual form of the 64-channel kernel: adamml_conv_bwd_data_res)
+        return adamml_conv3x3_c64_launch(d, x, w_packed, in_scale, in_shift, y, stats, bn_z, bn_vec, bn_act, stream);
+    // 7x7 / 2 stem of a 16-channel image (flow / RGB-diff ResNets), plain input: LDS-patch kernel with resident weights (conv_stem16.hip)
+    if (!bn_z && !in_scale && !d->accumulate && adamml_conv_stem16_supported(d))
+        return adamml_conv_stem16_fwd_launch(d, x, w_packed, y, stats, stream);
+    // narrow 1x1 convs of the MobileNetV2s (plain forward / plain data gradient): the barrier-free streaming kernel (conv1x1_narrow.hip)
+    if (!bn_z && adamml_conv1x1_narrow_fwd_supported(d))
+        return adamml_conv1x1_narrow_fwd_launch(d, x, w_packed, in_scale, in_shift, y, stats, stream);
+    // expanding 1x1 convs of ResNet layers 3-4 (K = 256 / 512 -> >= 2 K channels; plain forward, stride-2 downsample forward, plain or
+    // accumulating data gradient): activation-stationary streaming kernel (conv1x1_wide.hip; it has no accumulating form of a lazy input:
+    // that call stays with conv_gemm_kernel)
+    if (!bn_z && !(d->accumulate && in_scale) && adamml_conv1x1_wide_expand_supported(d))
+        return adamml_conv1x1_wide_expand_launch(d, x, w_packed, in_scale, in_shift, y, stats, stream);
+    // ... their data gradients with the BatchNorm-fused epilogue (bn_z) or accumulating into the output
+    if (!in_scale && (bn_z ? stats != nullptr && !d->accumulate : d->accumulate != 0) && adamml_conv1x1_narrow_dgrad_epi_supported(d))
+        return adamml_conv1x1_narrow_dgrad_epi_launch(d, x, w_packed, y, bn_z, bn_vec, bn_act, stats, stream);
+    ConvP p = conv_operands(x, w_packed, in_scale, in_shift, y, stats, bn_z, bn_vec, bn_act);
+    ConvGrid g; Plan pl;
+    if (!conv_plan(d, PlanOpts{}, stream, p, g, pl)) return pl.rc;
     // (the fragment-side lazy transform, LZF, is NOT used for the plain forward convs: measured 5-10 % slower than the register-staged
     // loader -- layer-1 conv3 1.77 vs 1.61 ms, layer 2 0.59 vs 0.54, layer 3 0.23 vs 0.21: each pixel half is transformed by two waves,
     // between the ds_read and the MFMA; it only pays together with the early identity loads of the FADD kernel)
-    // operands without a lazy transform are staged by LDS-DMA (MODE 0 / 1 / 3)
+    // operands without a lazy transform are staged by LDS-DMA (MODE 0 / 1)
     const bool lazy = in_scale != nullptr;
     // the epilogue is a template parameter (EPI) of the LDS-DMA and one-step instances; deep-prefetch and MODE 2 keep the run-time form
-    const int epi = bn_z ? 1 : (p.accumulate ? 2 : 0);
-    // a gradient operand (a parity class, or the input of the BatchNorm-fused epilogue) is plain in memory -- every caller passes it so -- and
-    // the register-staged loaders are not compiled for MODE 3 or with EPI 1
-    if (lazy && (mode == 3 || (mode != 2 && epi == 1)))
-        return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_data: the gradient operand is never lazy");
-    with_bc(BC, [&](auto bc) {
-        if (mode == 0) launch_conv<bc(), 0>(lazy, deep, epi, cg, p);
-        else if (mode == 1) launch_conv<bc(), 1>(lazy, deep, epi, cg, p);
-        else if (mode == 2) launch_conv<bc(), 2>(lazy, deep, epi, cg, p);
-        else launch_conv<bc(), 3>(lazy, deep, epi, cg, p);
+    const int epi = plain_epi(p);
+    // a gradient operand (the input of the BatchNorm-fused epilogue) is plain in memory -- every caller passes it so -- and the register-staged
+    // loaders are not compiled with EPI 1
+    if (lazy && pl.mode != 2 && epi == 1) return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_data: the gradient operand is never lazy");
+    with_bc(pl.BC, [&](auto bc) {
+        if (pl.mode == 0) launch_conv<bc(), 0>(lazy, pl.deep, epi, g, p);
+        else if (pl.mode == 1) launch_conv<bc(), 1>(lazy, pl.deep, epi, g, p);
+        else launch_conv<bc(), 2>(lazy, pl.deep, epi, g, p);
     });
     return adamml_check_launch("conv_fwd");
 }
 
-// The descriptor conv_launch dispatches on for the data gradient of the forward conv d: a stride-1 conv of dz (pixels and channels of d's
+// one parity class of a stride-2 data gradient (MODE 3, conv_dgrad_stride2); never a kernel of another file
+static int conv_class(const adamml_conv_desc_t* d, const void* x, const void* w_packed, void* y, double* stats, const void* bn_z,
+                      const float* bn_vec, int bn_act, hipStream_t stream, const DgradClass& cls) {
+    if (int rc = conv_check(d, x, w_packed, y)) return rc;
+    ConvP p = conv_operands(x, w_packed, nullptr, nullptr, y, stats, bn_z, bn_vec, bn_act);
+    ConvGrid g; Plan pl; PlanOpts o;
+    o.cls = &cls;
+    if (!conv_plan(d, o, stream, p, g, pl)) return pl.rc;
+    with_bc(pl.BC, [&](auto bc) { with_epi(plain_epi(p), [&](auto e) { launch_plain<bc(), 3, true, e()>(g, p); }); });
+    return adamml_check_launch("conv_fwd");
+}
+
+// forward 1x1 conv + BatchNorm + residual add + activation, optionally with the temporal max-pool (f.tp_frames); y: the block output, or the pooled one
+static int conv_fadd(const adamml_conv_desc_t* d, const void* x, const void* w_packed, const float* in_scale, const float* in_shift, void* y,
+                     hipStream_t stream, const FaddEpi& f) {
+    if (int rc = conv_check(d, x, w_packed, y)) return rc;
+    ConvP p = conv_operands(x, w_packed, in_scale, in_shift, y, nullptr);
+    p.bn_vec = f.vec; p.res_out = (const bf16_t*)f.idn; p.res_act = f.act;
+    p.id_scale = f.id_scale; p.id_shift = f.id_shift; p.id_gstride = f.id_gstride; p.mask_out = f.mask_out;
+    p.tp_y = (bf16_t*)f.tp_y; p.tp_code = f.tp_code;
+    const int tp = f.tp_frames;
+    ConvGrid g; Plan pl; PlanOpts o;
+    o.tp = tp;
+    if (!conv_plan(d, o, stream, p, g, pl)) return pl.rc;
+    if (pl.mode != 0) return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_fwd_bn_add: only 1x1 / stride-1 convs");
+    if (in_scale && p.K > 512) {               // register-staged loader
+        if (tp) return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_fwd_bn_add_tpool: needs the LDS-DMA kernel (K <= 512 for a lazy input)");
+        with_bc(pl.BC, [&](auto bc) { launch_fadd<bc(), false, 0, false>(g, p); });
+        return adamml_check_launch("conv_fwd_bn_add");
+    }
+    // operands by LDS-DMA (a lazily normalised input is transformed at the fragment: LZF); with an identity operand, that one is
+    // requested at the start of each tile (EID)
+    const bool eid = p.res_out != nullptr;
+    if (tp) {
+        with_flag(in_scale != nullptr, [&](auto lzf) { with_tp(tp, [&](auto tv) { launch_fadd_tp<lzf(), tv()>(g, p); }); });
+        return adamml_check_launch("conv_fwd_bn_add_tpool");
+    }
+    with_bc(pl.BC, [&](auto bc) {
+        with_flag(in_scale != nullptr, [&](auto lzf) {
+            if (eid) launch_fadd<bc(), true, 1, lzf()>(g, p); else launch_fadd<bc(), true, 0, lzf()>(g, p);
+        });
+    });
+    return adamml_check_launch("conv_fwd_bn_add");
+}
+
+// data gradient (the gradient operand x is never lazy) with the residual form of the BatchNorm-fused epilogue
+static int conv_res(const adamml_conv_desc_t* d, const void* x, const void* w_packed, void* y, double* stats, const void* bn_z,
+                    const float* bn_vec, hipStream_t stream, const ResEpi& r) {
+    if (int rc = conv_check(d, x, w_packed, y)) return rc;
+    ConvP p = conv_operands(x, w_packed, nullptr, nullptr, y, stats, bn_z, bn_vec, ACT_NONE);
+    p.res_out = (const bf16_t*)r.res_out; p.res_mask = r.res_mask; p.res_act = r.res_act;
+    p.bn_z2 = (const bf16_t*)r.bn_z2; p.bn_vec2 = r.bn_vec2; p.stats2 = r.stats2;
+    ConvGrid g; Plan pl;
+    if (!conv_plan(d, PlanOpts{}, stream, p, g, pl)) return pl.rc;
+    // MODE 1 (3x3 / pad 1 / stride 1, dense dz): the epilogue only needs tile row r to be output pixel p0 + r, as in MODE 0
+    if (pl.mode != 0 && !(pl.mode == 1 && p.up == 1 && p.stride == 1))
+        return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_data_res: only 1x1 / stride-1 and 3x3 / pad-1 / stride-1 convs");
+    if (pl.mode == 1) {
+        with_bc(pl.BC, [&](auto bc) { launch_res_kxk<bc()>(g, p); });
+        return adamml_check_launch("conv_bwd_data_res (3x3)");
+    }
+    // the algebraic backward's form (identity gradient + 1-bit mask, sum(g') only): identity-side loads at the start of each tile (EID)
+    const bool eid = p.res_mask && p.accumulate && !p.bn_z && !p.bn_z2;
+    with_bc(pl.BC, [&](auto bc) { if (eid) launch_res<bc(), 1>(g, p); else launch_res<bc(), 0>(g, p); });
+    return adamml_check_launch("conv_bwd_data_res");
+}
+
+// 1x1 data gradient in the algebraic backward's residual form (accumulate + 1-bit mask + sum(g') only) with the product of its gradient tile
+// and pf.a accumulated alongside (PF), and the reduction of the per-workgroup partials into pf.out
+static int conv_res_prod(const adamml_conv_desc_t* d, const void* x, const void* w_packed, void* y, double* stats, const uint8_t* res_mask,
+                         int res_act, hipStream_t stream, const PfIn& pf) {
+    if (int rc = conv_check(d, x, w_packed, y)) return rc;
+    ConvP p = conv_operands(x, w_packed, nullptr, nullptr, y, stats);
+    p.res_out = p.y; p.res_mask = res_mask; p.res_act = res_act;       // (res_out is never read in the mask form)
+    ConvGrid g; Plan pl; PlanOpts o;
+    o.pf = true;
+    if (!conv_plan(d, o, stream, p, g, pl)) return pl.rc;
+    if (pl.mode != 0) return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_data_res: only 1x1 / stride-1 and 3x3 / pad-1 / stride-1 convs");
+    if (pl.BC != 128 || d->Cout % 128 || pf.C != 64 || !p.res_mask || !p.accumulate || !stats)
+        return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_data_res_prod: needs Cout %% 128 == 0, a 64-channel product operand, "
+                                                     "the accumulate + 1-bit-mask + sum(g')-only form");
+    const size_t need = pf_split(p.n_ptiles, p.n_ctiles, pl.groups).ws_bytes;
+    if (!pf.ws || pf.ws_bytes < need) return adamml_set_error(ADAMML_EINVAL, "conv_bwd_data_res_prod: workspace too small (need %zu bytes)", need);
+    p.pf_a = (const bf16_t*)pf.a; p.pf_scale = pf.scale; p.pf_shift = pf.scale ? pf.shift : nullptr; p.pf_act = pf.act; p.pf_gs = pf.gs;
+    p.pf_ws = (float*)pf.ws;
+    launch_res_prod(g, p);
+    if (int rc = adamml_check_launch("conv_bwd_data_res_prod")) return rc;
+    // P[g][ctile * 128 + r][c] = sum over the workgroups of (g, ctile), in workgroup order
+    launch_wgrad_reduce((const float*)pf.ws, pf.out, (size_t)128 * 64, p.pf_nsplit, 1, 64, 1, pl.groups * p.n_ctiles, stream);
+    return adamml_check_launch("conv_bwd_data_res_prod (reduce)");
+}
+
+// 1x1 data gradient over the K-concatenated inputs x and c.xb (the lazy transform in_scale / in_shift applies to c.xb only)
+static int conv_cat(const adamml_conv_desc_t* d, const void* x, const void* w_packed, const float* in_scale, const float* in_shift, void* y,
+                    double* stats, const void* bn_z, const float* bn_vec, int bn_act, hipStream_t stream, const CatIn& c) {
+    if (int rc = conv_check(d, x, w_packed, y)) return rc;
+    if (d->KH * d->KW != 1 || d->stride != 1 || (d->up > 1) || d->Cin % BK || c.C2 % 8)       // (hence MODE 0)
+        return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_data_alg: 1x1 / stride-1 convs with Cout %% 32 == 0 only");
+    ConvP p = conv_operands(x, w_packed, in_scale, in_shift, y, stats, bn_z, bn_vec, bn_act);
+    p.xb = (const bf16_t*)c.xb; p.K1 = d->Cin; p.C2 = c.C2; p.gw = c.gw; p.epi_add = c.epi_add;
+    ConvGrid g; Plan pl; PlanOpts o;
+    o.cat_C2 = c.C2;
+    if (!conv_plan(d, o, stream, p, g, pl)) return pl.rc;
+    with_bc(pl.BC, [&](auto bc) { launch_cat<bc()>(g, p); });
+    return adamml_check_launch("conv_bwd_data_alg");
+}
+
+// 1x1 data gradient whose input is the BatchNorm backward of (x = g, di.z), formed in the loader
+static int conv_dual(const adamml_conv_desc_t* d, const void* x, const void* w_packed, void* y, double* stats, const void* bn_z,
+                     const float* bn_vec, int bn_act, hipStream_t stream, const DualIn& di) {
+    if (int rc = conv_check(d, x, w_packed, y)) return rc;
+    ConvP p = conv_operands(x, w_packed, nullptr, nullptr, y, stats, bn_z, bn_vec, bn_act);
+    p.x2 = (const bf16_t*)di.z; p.aff = di.aff; p.side = (bf16_t*)di.side;
+    ConvGrid g; Plan pl;
+    if (!conv_plan(d, PlanOpts{}, stream, p, g, pl)) return pl.rc;
+    if (pl.mode != 0) return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_data_dual: only 1x1 / stride-1 convs");
+    with_bc(pl.BC, [&](auto bc) { launch_dual<bc()>(g, p); });
+    return adamml_check_launch("conv_bwd_data_dual");
+}
+
+// a dense 1x1 conv; each caller keeps its own extras (up, channel counts) next to the call
+static bool is_1x1_s1(const adamml_conv_desc_t* d) { return d && d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0; }
+
+// The descriptor the family functions dispatch on for the data gradient of the forward conv d: a stride-1 conv of dz (pixels and channels of d's
 // output) into dx (those of d's input) with the flipped / transposed weight pack.  `upsampled`: dz is read zero-upsampled by d's stride and
 // padded for the flipped taps (the generic form of any conv); otherwise dense -- 1x1 / stride-1 convs and the parity classes of
 // conv_dgrad_stride2.  The gradient operand is never lazily normalised (act / in_gstride are cleared).
@@ -1422,14 +1510,14 @@ extern "C" int adamml_conv_fused_input_supported(const adamml_conv_desc_t* d) {
 extern "C" int adamml_conv_fwd(const adamml_conv_desc_t* d, const void* x, const void* w_packed, const float* in_scale,
                                const float* in_shift, void* y, double* stats, hipStream_t stream) {
     // few pixels, many channels, no statistics (the eval / no-grad forward of a serving-size batch): the weight-streaming kernel of
-    // conv1x1_skinny.hip, bit-identical to the tile kernel.  Only this entry point: data gradients call conv_launch
+    // conv1x1_skinny.hip, bit-identical to the tile kernel.  Only this entry point: data gradients call conv_plain
     if (d && x && w_packed && y && adamml_conv1x1_skinny_supported(d, stats != nullptr))
         return adamml_conv1x1_skinny_launch(d, x, w_packed, in_scale, in_shift, y, stream);
-    return conv_launch(d, x, w_packed, in_scale, in_shift, y, stats, nullptr, nullptr, 0, stream);
+    return conv_plain(d, x, w_packed, in_scale, in_shift, y, stats, nullptr, nullptr, 0, stream);
 }
 
 extern "C" int adamml_conv_fwd_bn_add_supported(const adamml_conv_desc_t* d) {
-    return d && d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && (d->up <= 1) && d->Cin % 8 == 0 && d->Cout % 8 == 0 ? 1 : 0;
+    return is_1x1_s1(d) && (d->up <= 1) && d->Cin % 8 == 0 && d->Cout % 8 == 0 ? 1 : 0;
 }
 
 extern "C" int adamml_conv_fwd_bn_add_streams(const adamml_conv_desc_t* d) {
@@ -1444,7 +1532,7 @@ extern "C" int adamml_conv_fwd_bn_add(const adamml_conv_desc_t* d, const void* x
     if (idn && adamml_conv1x1_fadd_stream_supported(d))
         return adamml_conv1x1_fadd_stream_launch(d, x, w_packed, in_scale, in_shift, bn_vec, idn, id_scale, id_shift, id_gstride, act, out, mask_out, stream);
     FaddEpi f{bn_vec, idn, id_scale, id_shift, id_gstride, act, mask_out, 0, nullptr, nullptr};
-    return conv_launch(d, x, w_packed, in_scale, in_shift, out, nullptr, nullptr, nullptr, 0, stream, nullptr, nullptr, nullptr, nullptr, &f);
+    return conv_fadd(d, x, w_packed, in_scale, in_shift, out, stream, f);
 }
 
 extern "C" int adamml_conv_fwd_bn_add_next_supported(const adamml_conv_desc_t* d, int next_cout) {
@@ -1492,7 +1580,7 @@ extern "C" int adamml_conv_fwd_bn_add_tpool(const adamml_conv_desc_t* d, const v
                                                 stream);
     FaddEpi f{bn_vec, idn, id_scale, id_shift, id_gstride, act, nullptr, frames, pooled, code};
     // (`pooled` doubles as the kernel's y pointer: the full-rate output is never written)
-    return conv_launch(d, x, w_packed, in_scale, in_shift, pooled, nullptr, nullptr, nullptr, 0, stream, nullptr, nullptr, nullptr, nullptr, &f);
+    return conv_fadd(d, x, w_packed, in_scale, in_shift, pooled, stream, f);
 }
 
 // Data gradient of a stride-2 conv (3x3 pad 1 / 1x1 pad 0: every strided conv of the hot path) WITHOUT the 4x wasted work
@@ -1522,8 +1610,7 @@ static int conv_dgrad_stride2(const adamml_conv_desc_t* d, const void* dz, const
                 }
             }
             if (c.nt == 0 && accumulate) continue;
-            int rc = conv_launch(&g, dz, w, nullptr, nullptr, dx, sums, z_in, bn_vec, act, stream, &c);
-            if (rc) return rc;
+            if (int rc = conv_class(&g, dz, w, dx, sums, z_in, bn_vec, act, stream, c)) return rc;
         }
     return ADAMML_OK;
 }
@@ -1539,14 +1626,14 @@ extern "C" int adamml_conv_bwd_data_bn(const adamml_conv_desc_t* d, const void* 
     if (!d || !z_in || !bn_vec || !sums) return adamml_set_error(ADAMML_EINVAL, "conv_bwd_data_bn: null argument");
     if (dgrad_stride2_ok(d)) return conv_dgrad_stride2(d, dz, w_dgrad_packed, dx, 0, sums, z_in, bn_vec, act, stream);
     const adamml_conv_desc_t g = dgrad_desc(d, 0, true);
-    return conv_launch(&g, dz, w_dgrad_packed, nullptr, nullptr, dx, sums, z_in, bn_vec, act, stream);
+    return conv_plain(&g, dz, w_dgrad_packed, nullptr, nullptr, dx, sums, z_in, bn_vec, act, stream);
 }
 
 // Measured on MI355X (tools/bench_fused.py, B = 72): against apply + data gradient the dual loader wins for K = Cout <= 512
 // (layer 1: 3.8 vs 4.2 ms, layer 2: 1.01 vs 1.05 ms) and loses beyond (layer 3: 0.33 vs 0.30 ms; layer 4: every one of
 // the 4 cout tiles repeats the affine and the vectors no longer fit the LDS table).
 extern "C" int adamml_conv_bwd_data_dual_supported(const adamml_conv_desc_t* d) {
-    return d && d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && d->Cout <= 512 && d->Cin % 8 == 0 && d->Cout % 8 == 0 ? 1 : 0;
+    return is_1x1_s1(d) && d->Cout <= 512 && d->Cin % 8 == 0 && d->Cout % 8 == 0 ? 1 : 0;
 }
 
 extern "C" int adamml_conv_bwd_data_dual(const adamml_conv_desc_t* d, const void* g, const void* z, const float* aff, void* dz_side,
@@ -1562,11 +1649,11 @@ extern "C" int adamml_conv_bwd_data_dual(const adamml_conv_desc_t* d, const void
         return adamml_conv1x1_narrow_dual_launch(d, g, z, aff, dz_side, w_dgrad_packed, dx, accumulate, z_in, bn_vec, act, sums, stream);
     const adamml_conv_desc_t gd = dgrad_desc(d, accumulate);
     DualIn di{z, aff, dz_side};
-    return conv_launch(&gd, g, w_dgrad_packed, nullptr, nullptr, dx, sums, z_in, bn_vec, act, stream, nullptr, nullptr, &di);
+    return conv_dual(&gd, g, w_dgrad_packed, dx, sums, z_in, bn_vec, act, stream, di);
 }
 
 extern "C" int adamml_conv_bwd_data_alg_streams(const adamml_conv_desc_t* d) {
-    return d && d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && adamml_alg_stream_supported(d->Cout, d->Cin) ? 1 : 0;
+    return is_1x1_s1(d) && adamml_alg_stream_supported(d->Cout, d->Cin) ? 1 : 0;
 }
 
 extern "C" int adamml_conv_bwd_data_alg(const adamml_conv_desc_t* d, const void* g, const void* a, const float* a_scale, const float* a_shift,
@@ -1574,7 +1661,7 @@ extern "C" int adamml_conv_bwd_data_alg(const adamml_conv_desc_t* d, const void*
                                         const float* bn_vec, int act, double* sums, hipStream_t stream) {
     // d describes the FORWARD conv (1x1, stride 1); d->act / d->in_gstride describe the lazy transform of its input a
     if (!d || !g || !a || !w_alg || !epi_add || !dx) return adamml_set_error(ADAMML_EINVAL, "conv_bwd_data_alg: null argument");
-    if (!(d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0)) return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_data_alg: only 1x1 / stride-1 convs");
+    if (!is_1x1_s1(d)) return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_data_alg: only 1x1 / stride-1 convs");
     if ((z_in != nullptr) != (bn_vec != nullptr) || (z_in != nullptr) != (sums != nullptr))
         return adamml_set_error(ADAMML_EINVAL, "conv_bwd_data_alg: incomplete BatchNorm epilogue operands");
     if (z_in && accumulate) return adamml_set_error(ADAMML_EUNSUPPORTED, "conv_bwd_data_alg: the BatchNorm epilogue does not accumulate");
@@ -1583,11 +1670,11 @@ extern "C" int adamml_conv_bwd_data_alg(const adamml_conv_desc_t* d, const void*
     adamml_conv_desc_t gd = dgrad_desc(d, accumulate);
     gd.act = d->act; gd.in_gstride = d->in_gstride;          // the lazy transform of the concatenated operand a (the loader applies it to a only)
     CatIn c{a, d->Cin, (size_t)d->Cin * (d->Cout + d->Cin), epi_add};
-    return conv_launch(&gd, g, w_alg, a_scale, a_shift, dx, sums, z_in, bn_vec, act, stream, nullptr, nullptr, nullptr, &c);
+    return conv_cat(&gd, g, w_alg, a_scale, a_shift, dx, sums, z_in, bn_vec, act, stream, c);
 }
 
 static bool res_1x1(const adamml_conv_desc_t* d) {
-    return d && d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && d->Cin % 8 == 0 && d->Cout % 8 == 0;
+    return is_1x1_s1(d) && d->Cin % 8 == 0 && d->Cout % 8 == 0;
 }
 
 // 3x3 / pad 1 / stride 1 with as many output as input channels (conv1 of a BasicBlock without a downsample branch): the tile kernel's
@@ -1628,7 +1715,7 @@ extern "C" int adamml_conv_bwd_data_res(const adamml_conv_desc_t* d, const void*
     if (!z_b && res_3x3_c64(d))
         return adamml_conv3x3_c64_res_launch(&g, dz, w_dgrad_packed, dx, res_out, res_mask, res_act, z_a, vec_a, sums_a, stream);
     ResEpi r{res_out, res_mask, res_act, z_b, vec_b, sums_b};
-    return conv_launch(&g, dz, w_dgrad_packed, nullptr, nullptr, dx, sums_a, z_a, vec_a, ACT_NONE, stream, nullptr, &r);
+    return conv_res(&g, dz, w_dgrad_packed, dx, sums_a, z_a, vec_a, stream, r);
 }
 
 extern "C" size_t adamml_conv_bwd_data_res_prod_workspace(const adamml_conv_desc_t* d) {
@@ -1636,10 +1723,7 @@ extern "C" size_t adamml_conv_bwd_data_res_prod_workspace(const adamml_conv_desc
     if (adamml_res_prod_stream_supported(d, 64)) return adamml_res_prod_stream_workspace(d);
     const int groups = d->groups < 1 ? 1 : d->groups;
     const int n_ptiles = ceil_div(d->N * d->OH * d->OW, BP), n_ctiles = ceil_div(d->Cin, 128);      // (dgrad: the output channels are d->Cin)
-    long nsp = 1536 / ((long)n_ctiles * groups);
-    if (nsp < 1) nsp = 1;
-    const int tpb = ceil_div(n_ptiles, (int)nsp);
-    return (size_t)groups * n_ctiles * ceil_div(n_ptiles, tpb < 1 ? 1 : tpb) * 128 * 64 * sizeof(float);
+    return pf_split(n_ptiles, n_ctiles, groups).ws_bytes;
 }
 
 extern "C" int adamml_conv_bwd_data_res_prod_supported(const adamml_conv_desc_t* d, int a_channels) {
@@ -1662,9 +1746,8 @@ extern "C" int adamml_conv_bwd_data_res_prod(const adamml_conv_desc_t* d, const 
         return adamml_res_prod_stream_launch(d, dz, w_dgrad_packed, dx, res_mask, sums_a, a, a_scale, a_shift, a_act, a_gstride, prod, workspace,
                                              workspace_bytes, stream);
     const adamml_conv_desc_t dd = dgrad_desc(d, 1);
-    ResEpi r{dx, res_mask, res_act, nullptr, nullptr, nullptr};       // (res_out is never read in the mask form)
     PfIn pf{a, a_scale, a_shift, a_act, a_gstride, a_channels, prod, workspace, workspace_bytes};
-    return conv_launch(&dd, dz, w_dgrad_packed, nullptr, nullptr, dx, sums_a, nullptr, nullptr, 0, stream, nullptr, &r, nullptr, nullptr, nullptr, &pf);
+    return conv_res_prod(&dd, dz, w_dgrad_packed, dx, sums_a, res_mask, res_act, stream, pf);
 }
 
 extern "C" int adamml_conv_bwd_data(const adamml_conv_desc_t* d, const void* dz, const void* w_dgrad_packed, void* dx,
@@ -1674,5 +1757,5 @@ extern "C" int adamml_conv_bwd_data(const adamml_conv_desc_t* d, const void* dz,
     if (!d) return adamml_set_error(ADAMML_EINVAL, "conv_bwd_data: null desc");
     if (dgrad_stride2_ok(d)) return conv_dgrad_stride2(d, dz, w_dgrad_packed, dx, accumulate, nullptr, nullptr, nullptr, 0, stream);
     const adamml_conv_desc_t g = dgrad_desc(d, accumulate, true);
-    return conv_launch(&g, dz, w_dgrad_packed, nullptr, nullptr, dx, nullptr, nullptr, nullptr, 0, stream);
+    return conv_plain(&g, dz, w_dgrad_packed, nullptr, nullptr, dx, nullptr, nullptr, nullptr, 0, stream);
 }

@@ -4,14 +4,14 @@
 // Declarations only: no .hip file keeps a prototype of a function it does not define (tests/test_host_cpu.py checks both).  The C ABI is
 // include/adamml_hip.h; the error plumbing every file uses is in common.h.
 //
-// `d` is the descriptor conv_launch (conv_gemm.hip) dispatches on -- for a data gradient the flipped one (dgrad_desc) -- unless noted.
+// `d` is the descriptor conv_plain (conv_gemm.hip) dispatches on -- for a data gradient the flipped one (dgrad_desc) -- unless noted.
 #pragma once
 #include "common.h"
 #include "../../include/adamml_hip.h"
 
 // ---- conv_wgrad.hip: the split reduce behind every kernel that writes one partial per workgroup
 // dw[perm(i)] (+)= sum_{s<nsplit} ws[g][s][i] for the `groups` outputs of n indices each; taps > 1: ws is [co][tap][cin], dw [co][cin][tap];
-// store: overwrite instead of accumulate.  No launch check: the callers below and conv_launch's product form add their own
+// store: overwrite instead of accumulate.  No launch check: the callers below and conv_res_prod (conv_gemm.hip) add their own
 void launch_wgrad_reduce(const float* ws, float* dw, size_t n, int nsplit, int taps, int cin, int store, int groups, hipStream_t stream);
 // dw[perm(i)] += sum_{s<nsplit} ws[s*n + i]
 int adamml_launch_split_reduce(const float* ws, float* dw, size_t n, int nsplit, hipStream_t stream, int taps = 1, int cin = 1);

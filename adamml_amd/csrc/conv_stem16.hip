@@ -23,7 +23,7 @@
 // N = 360 and 108 vs 110 us at N = 45 (a tie within the spread; 512 workgroups instead of 256 lost there: 116 us); weight gradient 643 vs
 // 1275 us and 102 vs 167 us.
 //
-// Both kernels are reached through adamml_conv_fwd / adamml_conv_bwd_weight (conv_launch / wgrad_launch dispatch on
+// Both kernels are reached through adamml_conv_fwd / adamml_conv_bwd_weight (conv_plain / wgrad_launch dispatch on
 // adamml_conv_stem16_supported, as they do for the 3x3 / 64 -> 64 kernels): plain input only, no data gradient (network input).
 #include "common.h"
 #include "conv_internal.h"

@@ -46,7 +46,6 @@ def test_library_exports_every_declared_symbol(built):
 
 # entry points no test module has to name, with the reason (everything else declared in the header must appear in a tests/test_*.py)
 ABI_TEST_EXEMPT = {
-    "adamml_last_error_string": "query: hip.call reads it on every failing launch",
     "adamml_plan_run": "plan plumbing: every model row replayed through adamml_amd/plan.py, bit for bit against eager (tests/test_launch_plan_rows_gpu.py, "
                        "tests/test_launch_plan_gpu.py); its records decoded against the eager launch list (tests/test_launch_plan_cpu.py)",
     "adamml_plan_events_create": "plan plumbing: the weight-gradient stream rows of tests/test_launch_plan_rows_gpu.py replay through its events",
@@ -56,7 +55,7 @@ ABI_TEST_EXEMPT = {
 
 def test_every_declared_entry_point_is_named_by_a_test_module():
     """A kernel entry point the suite never calls by name is a gap: every function of include/adamml_hip.h is called in some tests/test_*.py,
-    or is in ABI_TEST_EXEMPT with its reason (the error string, plan plumbing); the exemption list holds nothing stale.
+    or is in ABI_TEST_EXEMPT with its reason (plan plumbing); the exemption list holds nothing stale.
     Dispatch probes are not exempt: a row asserts them (test_dispatch_probes_answer_as_documented for those no GPU row reads)."""
     import glob
     declared = set(abi.FUNCTIONS)
